@@ -2,13 +2,20 @@
 """bench.py — trajectory frames/s of the per-frame order-parameter path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload NAME] [--frames F] [--scaling strong|weak]
+                    [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (gorder_hip_submit_device: box check + P2 kernels + leaflet kernels if
 enabled) over one batch of synthetic frames that are ALREADY resident in HBM.
 
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, roofline of the timed steps).
+--full adds the secondary measurements below (cpu_baseline, end_to_end, scaling_reference; N > 1: allreduce_ms,
+lib_allreduce, the sharded end_to_end); the --no-* switches leave single blocks of --full out.
+--dump-outputs DIR writes what the timed path computed, per step, as DIR/<name>.npy (see dump_outputs()).
+
 N = 1 (default): BASELINE.json configs[1] — AAOrder, 256-lipid membrane (25 088 selected atoms, 16 384 C-H bonds per
   frame), 10 000 frames per step.  The JSON line also carries
     roofline          the dominant kernel against the HBM roofline (HIP events on the launch stream),
+  and with --full
     cpu_baseline      the oracle (C restatement of the reference algorithm, libm trig like the Rust code) on this box's
                       host cores, at 1 thread and at all cores,
     end_to_end        the same workload from an XTC FILE (gorder_hip_run_trajectory): frames/s from file with the frames
@@ -642,6 +649,32 @@ def scaling_reference(device, steps=5):
             "result_ok": ok}
 
 
+def dump_outputs(res, passes, out_dir, max_bytes=64 << 20):
+    """What a caller of the timed path receives (Results of gorder_hip_finish), per step: the accumulators hold `passes`
+    identical steps (warm-up included, whose number depends on the clock), so sums and counts are divided by it and the
+    order parameters, ratios of the two, are what one step gives.  float64 holds the i64 per-step sums exactly
+    (< 2^53).  Every value is finite: a slot or ordermap tile without samples (its count is 0, e.g. the leaflet rows
+    when leaflets are off) holds 0 where the caller's arrays hold NaN.  Ordermaps larger than what is left of
+    `max_bytes` are written as a fixed, seeded sample of tiles (the same tiles for values and counts)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"order": np.nan_to_num(res.order(), nan=0.0).astype(np.float32),               # [3, n_acc] total / upper / lower
+              "sums_per_step": res.sums.astype(np.float64) / passes,
+              "counts_per_step": res.counts.astype(np.float64) / passes}
+    if res.map_sums is not None:
+        n = res.map_counts.astype(np.int64)
+        ticks = np.where(n > 0, (np.abs(res.map_sums) // np.maximum(n, 1)) * np.sign(res.map_sums), 0)
+        om = (ticks.astype(np.float64) / 1e6).astype(np.float32).reshape(-1)
+        omc = (n.astype(np.float64) / passes).reshape(-1)
+        room = (max_bytes - sum(a.nbytes for a in arrays.values())) // (om.itemsize + omc.itemsize)
+        if om.size > room:
+            pick = np.sort(np.random.default_rng(0).choice(om.size, size=room, replace=False))
+            om, omc = om[pick], omc[pick]
+        arrays["ordermap"], arrays["ordermap_counts_per_step"] = om, omc
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -658,9 +691,14 @@ def main():
     ap.add_argument("--trig", choices=["squared", "acos"], default="squared",
                     help="squared: P2 from the squared cosine (library default); acos: the reference's literal acos -> cos "
                          "round trip (GORDER_FLAG_TRIG_ACOS_COS)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true")
-    ap.add_argument("--no-scaling-reference", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements: cpu_baseline, end_to_end, scaling_reference (N = 1); "
+                         "allreduce_ms, lib_allreduce, sharded end_to_end (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's results (per step) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full without the end-to-end blocks")
+    ap.add_argument("--no-scaling-reference", action="store_true", help="--full without the scaling reference")
     args = ap.parse_args()
 
     import torch
@@ -802,7 +840,7 @@ def main():
     kernel_names = eng.kernel_names()      # what the timed region really launched (gorder_hip_kernel_time_names)
     res = eng.finish()
     allreduce_ms = None
-    if world > 1:                  # the collective alone, after the timed region (what a step pays for it)
+    if world > 1 and args.full:    # the collective alone, after the timed region (what a step pays for it)
         torch.cuda.synchronize()
         dist.barrier()
         t1 = time.perf_counter()
@@ -901,7 +939,9 @@ def main():
                             "rccl_version": nccl_version, "collective_issued_by": "library (gorder_hip_allreduce)" if comm is not None
                             else "torch.distributed", "kernel_ms_per_step_per_rank": per_rank_ms, "device_per_rank": per_rank_dev,
                             "rehearsal_on_one_gpu": rehearsal}
-    if world == 1:
+    if rank == 0 and args.dump_outputs:
+        out["outputs"] = dump_outputs(res, max(1, res.n_frames // total), args.dump_outputs)
+    if world == 1 and args.full:
         # release the headline workload's frames before the secondary measurements
         del d_xyz, d_box
         eng.close()
@@ -932,7 +972,7 @@ def main():
             free_b, _ = torch.cuda.mem_get_info(device)
             if free_b > 150 * (1 << 30):
                 out["scaling_reference"] = scaling_reference(device)
-    if world > 1:
+    if world > 1 and args.full:
         # The headline above is final.  The extra blocks below run collectives; a rank that fails alone would leave the
         # others waiting, so a watchdog prints the line as it stands and ends every rank if they do not come back.
         wd = Watchdog(float(os.environ.get("GORDER_BENCH_EXTRAS_TIMEOUT", "600")), rank, lambda: dict(out) if rank == 0 else {})

@@ -183,6 +183,8 @@ if __name__ == "__main__":
             shutil.copy(src, os.path.join(HERE, "expected", f))
     # one small trajectory file as it is, for the reader's own tests (1 frame, 16 769 beads, 62 KB)
     shutil.copy(os.path.join(REF, "split", "cg3.xtc"), os.path.join(HERE, "cg3.xtc"))
+    # the same system's TRR file (1 frame, full precision), for the TRR reader's test
+    shutil.copy(os.path.join(REF, "split", "cg3.trr"), os.path.join(HERE, "cg3.trr"))
     # two more of the reference's trajectory files, as data for the decoders (device against host, bit for bit): one
     # all-atom frame with its water (long runs of small offsets) and a small multi-frame system
     shutil.copy(os.path.join(REF, "split", "pcpepg4.xtc"), os.path.join(HERE, "pcpepg4.xtc"))

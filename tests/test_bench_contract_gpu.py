@@ -1,10 +1,11 @@
-"""The line `python bench.py` prints at N = 1 carries what the driver and the reviewer read: the contract's keys, the
-roofline and cpu_baseline objects, the end-to-end blocks with both decode routes."""
+"""The line `python bench.py` prints at N = 1 carries what the driver and the reviewer read: the contract's keys and the
+roofline object; with --full also the cpu_baseline object and the end-to-end blocks with both decode routes."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -13,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_single_gpu_line(built):
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--frames", "2000",
-                          "--no-scaling-reference"], capture_output=True, text=True, timeout=900,
+                          "--full", "--no-scaling-reference"], capture_output=True, text=True, timeout=900,
                          env=dict(os.environ, GORDER_BENCH_LARGE_GB="0.5"))      # (the default run writes 8 GB)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -51,6 +52,30 @@ def test_single_gpu_line(built):
     s = e["solvated"]
     assert s["device_decode"]["decoded_on"] == "device" and s["device_decode"]["frames_decoded_by_host_after_all"] == 0
     assert s["device_decode"]["pcie_GBps"] > 0 and s["atoms_analysed"] * 4 == s["atoms_in_file"]
+
+
+def test_plain_line_and_dumped_outputs(built, tmp_path):
+    """A plain run carries the headline only (the secondary blocks are --full's), `--steps` is the number of timed steps,
+    and --dump-outputs writes the timed path's per-step results: the same for two runs whose warm-up differs."""
+    lines, dumps = [], []
+    for k, warmup in enumerate(("2", "7")):
+        dumps.append(tmp_path / f"run{k}")
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", warmup, "--frames", "512",
+                              "--dump-outputs", str(dumps[-1])], capture_output=True, text=True, timeout=900)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines.append(json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0]))
+    for d in lines:
+        assert d["steps"] == 4 and d["ms_per_step"] > 0 and d["unit"] == "frames/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f32" and abs(d["value"] - 4 * 512 / (d["ms_per_step"] * 4 / 1e3)) < 1e-6 * d["value"]
+        assert not {"cpu_baseline", "end_to_end", "scaling_reference"} & set(d)
+        assert d["outputs"] == ["counts_per_step", "order", "sums_per_step"]
+    for name in lines[0]["outputs"]:
+        a, b = (np.load(p / f"{name}.npy") for p in dumps)
+        assert a.dtype in (np.float32, np.float64) and a.shape == (3, 64) and np.isfinite(a).all()
+        np.testing.assert_array_equal(a, b)
+    counts = np.load(dumps[0] / "counts_per_step.npy")
+    assert (counts[0] == 512 * 256).all()                    # every C-H bond type of every lipid in every frame of the step
+    assert (counts[1:] == 0).all() and (np.load(dumps[0] / "order.npy")[1:] == 0).all()   # no leaflets: empty rows hold 0
 
 
 @pytest.mark.parametrize("workload,dominant,others", [

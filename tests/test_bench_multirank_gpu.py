@@ -41,7 +41,7 @@ def test_two_ranks_on_one_gpu_weak(built, workload, frames):
 def test_two_ranks_strong_scaling_default(built):
     """`--gpus N` with N > 1 runs the north_star experiment: STRONG scaling of one CG-1M trajectory cut into contiguous
     frame shards, every step = reset + shard + one all-reduce (here 301 frames instead of 10 000: 151 + 150)."""
-    out = launch(["--frames", "301"], 29534)
+    out = launch(["--frames", "301", "--full"], 29534)
     assert out["n_gpus"] == 2 and out["scaling"] == "strong"
     assert "1M-bead" in out["config"]["workload"] and out["config"]["frames_per_step"] == 301
     assert out["config"]["frames_per_step_per_gpu"] in (150, 151)

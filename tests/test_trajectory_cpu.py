@@ -106,12 +106,9 @@ def test_trr(tmp_path, double):
 
 
 def test_trr_of_the_reference_when_present(cg):
-    """tests/files/split/cg3.trr (t = 355 000 ps) holds the same frame as the XTC data, in full precision
-    written from it: the lipid beads equal the fixture frame of that time.  Needs /root/reference."""
-    path = "/root/reference/tests/files/split/cg3.trr"
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present")
-    xyz, box, t = xtc.read_trajectory([path])
+    """tests/golden/cg3.trr is the reference's tests/files/split/cg3.trr (t = 355 000 ps): it holds the same frame as
+    the XTC data, in full precision written from it: the lipid beads equal the fixture frame of that time."""
+    xyz, box, t = xtc.read_trajectory([os.path.join(GOLDEN, "cg3.trr")])
     k = int(np.flatnonzero(cg.times == t[0])[0])
     np.testing.assert_array_equal(xyz[0, : cg.xyz.shape[1]], cg.xyz[k])
     np.testing.assert_array_equal(box[0], cg.boxes[k])

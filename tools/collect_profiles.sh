@@ -2,12 +2,14 @@
 # usage (on the GPU box): tools/collect_profiles.sh <tag>   -> gpurun_out/<tag>/...  (copy what is to be judged into profiles/)
 # headline under rocprofv3 (kernel trace + stats), the default bench line, every workload, PMC passes, kernel splits
 TAG=${1:-r4z}
+# the full bench line (every secondary block): $BENCH_OUT, default bench_runs/<tag> in the repository
+BENCH_OUT=${BENCH_OUT:-$(cd "$(dirname "$0")/.." && pwd)/bench_runs/$TAG}
 set -x
 mkdir -p gpurun_out/$TAG
 cd /tmp; export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/$TAG/kt_head -- python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-end-to-end --no-scaling-reference > $GRAFT_REPO_ROOT/gpurun_out/$TAG/bench_headline_under_rocprof.json 2> $GRAFT_REPO_ROOT/gpurun_out/$TAG/kt_head.err
 cd $GRAFT_REPO_ROOT
-python3 bench.py --steps 20 --warmup 5 > gpurun_out/$TAG/bench_aa256.json 2> gpurun_out/$TAG/bench_aa256.err
+mkdir -p "$BENCH_OUT" && python3 bench.py --full --steps 20 --warmup 5 > "$BENCH_OUT/bench_aa256.json" 2> "$BENCH_OUT/bench_aa256.err"
 tools/bench_all.sh gpurun_out/$TAG/bench_all.jsonl > gpurun_out/$TAG/bench_all.txt 2>&1
 tools/pmc.sh ${TAG}_pmc_aa aa256 10000 k_bonds_tiled > gpurun_out/$TAG/pmc_aa.txt 2>&1
 python3 tools/pmc_summary.py gpurun_out/${TAG}_pmc_aa k_bonds_tiled aa256 10000 > gpurun_out/$TAG/pmc_aa256_k_bonds_tiled.json
