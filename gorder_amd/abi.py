@@ -35,8 +35,9 @@ ERR_BOX_RANGE = 103
 ERR_LEAFLETS_NOT_PRIMED = 104
 ERR_OVERFLOW = 105
 ERR_TRAJECTORY_FORMAT = 106
+ERR_CLUSTERING = 107         # spherical clustering: a head-centre distance is not finite
 
-LEAFLETS_NONE, LEAFLETS_GLOBAL, LEAFLETS_LOCAL, LEAFLETS_INDIVIDUAL, LEAFLETS_MANUAL = range(5)
+LEAFLETS_NONE, LEAFLETS_GLOBAL, LEAFLETS_LOCAL, LEAFLETS_INDIVIDUAL, LEAFLETS_MANUAL, LEAFLETS_SPHERICAL = range(6)
 FLAG_TRIG_ACOS_COS = 1
 FLAG_UA_FAST_NORMALISE = 2      # united atoms: tolerance-bounded hydrogen construction (include/gorder_hip.h)
 UA_CH1_SAT, UA_CH2, UA_CH3, UA_CH1_UNSAT = 1, 2, 3, 4
@@ -157,7 +158,7 @@ class Leaflets:
     frequency: int = 1      # 0 = once; REAL frequency (input frequency * step)
     flip: bool = False
     radius: float = 0.0
-    membrane: Optional[np.ndarray] = None
+    membrane: Optional[np.ndarray] = None     # Global / Local: group "Membrane"; Spherical: group "ClusterHeads"
 
 
 @dataclass
@@ -312,6 +313,7 @@ _EXPORTS = [
     "gorder_hip_plan_tables", "gorder_hip_selftest_arithmetic", "gorder_hip_selftest_trig", "gorder_hip_run_trajectory",
     "gorder_hip_comm_unique_id", "gorder_hip_comm_create", "gorder_hip_comm_destroy", "gorder_hip_allreduce",
     "gorder_hip_reset", "gorder_hip_xtc_decode", "gorder_hip_release_staging", "gorder_hip_speculation_stats", "gorder_hip_local_decide_stats",
+    "gorder_hip_spherical_stats",
 ]
 
 _lib = None
@@ -382,6 +384,7 @@ def load_library() -> C.CDLL:
     lib.gorder_hip_plan.argtypes = [vp, C.POINTER(CPlan)]
     lib.gorder_hip_speculation_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.gorder_hip_local_decide_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.gorder_hip_spherical_stats.argtypes = [vp, C.POINTER(C.c_float)]
     lib.gorder_hip_plan_tables.argtypes = [C.POINTER(CTables), C.POINTER(CPlan), C.POINTER(i32)]
     lib.gorder_hip_selftest_arithmetic.argtypes = [i32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.gorder_hip_selftest_trig.argtypes = [i32, i32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -730,6 +733,15 @@ class HipEngine:
         out = (C.c_uint64 * 4)()
         self._check(self.lib.gorder_hip_local_decide_stats(self._h, out))
         return {"submits": int(out[0]), "paused": int(out[1]), "open_frames": int(out[2]), "frames": int(out[3])}
+
+    def spherical_stats(self) -> dict:
+        """Spherical clustering (gorder_hip_spherical_stats), most recent assignment frame: centre of the head group, the
+        fitted two-component mixture, final average log-likelihood, EM iterations, group atoms labelled outer."""
+        out = (C.c_float * 12)()
+        self._check(self.lib.gorder_hip_spherical_stats(self._h, out))
+        v = np.array(out[:], dtype=np.float32)
+        return {"centre": v[0:3].copy(), "weight_a": v[3], "mean_a": v[4], "var_a": v[5], "mean_b": v[6], "var_b": v[7],
+                "avg_log_likelihood": v[8], "iterations": int(v[9]), "n_outer": int(v[10])}
 
     def plan(self) -> dict:
         p = CPlan()

@@ -11,6 +11,7 @@
 //   SystemLeafletClassification::run   leaflets.rs:171-205           -> k_leaflets_global
 //   common_identify_leaflet            leaflets.rs:711-732              (same kernel)
 //   IndividualClassification           leaflets.rs:777-801           -> k_leaflets_individual
+//   SystemSphericalClusterClassification spherical_clustering.rs:42-277, leaflets.rs:1296-1366 -> k_leaflets_spherical
 //   LocalClassification + local centres leaflets.rs:661-675, pbc.rs:273-318 -> k_local_{build,rowprefix,decide,flags_rows,flags_todo} (k_local_{bin,scan,scatter,flags}: very large membranes, no box)
 //   should_assign / get_assigned       leaflets.rs:435-441, 1437-1472   (host: assignment-row table)
 //   SystemTopology::add / reduce       topology/mod.rs:236-272          (integer sums: order-free)
@@ -139,6 +140,10 @@ struct gorder_hip_handle {
     uint8_t *d_aflags = nullptr;
     size_t aflags_rows = 0;
     float *d_adist = nullptr;
+    // spherical clustering: distances of the group atoms past the register-resident ones, sph_slab assignment frames a launch;
+    // the statistics of the most recent assignment frame (gorder_hip_spherical_stats)
+    float *d_sph_spill = nullptr, *d_sph_stats = nullptr;
+    uint32_t sph_spill = 0, sph_slab = 1u << 20, sph_threads = 1024;
     // Local leaflets scratch (sized for local_slab assignment frames)
     uint32_t *d_lcell_of = nullptr, *d_lcell_count = nullptr, *d_lcell_fill = nullptr;
     float *d_ltrig = nullptr;
@@ -289,7 +294,8 @@ int check_device_error(gorder_hip_handle *h) {
     const uint32_t code = (uint32_t)(key & 15u), detail = (uint32_t)(key >> 4) & 3u, mol = (uint32_t)(key >> 6) & 0x1ffffu;
     const uint32_t sample = (uint32_t)(key >> 23) & 1u, slot = (uint32_t)(key >> 24) & 0x3fffu;
     const uint32_t stage = (uint32_t)(key >> 38) & 3u, frame = (uint32_t)(key >> 40) & 0x7fffffu;
-    const int status = code == 8u ? (int)GORDER_ERR_BOX_RANGE : (code == 9u ? (int)GORDER_ERR_TRAJECTORY_FORMAT : (int)code);
+    const int status = code == 8u ? (int)GORDER_ERR_BOX_RANGE : (code == 9u ? (int)GORDER_ERR_TRAJECTORY_FORMAT :
+                       (code == 10u ? (int)GORDER_ERR_CLUSTERING : (int)code));
     h->err_frame = frame;
     char where[96];
     snprintf(where, sizeof(where), "frame %u of a batch", frame);
@@ -310,6 +316,8 @@ int check_device_error(gorder_hip_handle *h) {
         if (mol < h->host_heads.size()) h->err_index = h->host_heads[mol];                // leaflets.rs:661-675: the head's index
     } else if (status == GORDER_ERR_DYNAMIC_NORMAL) {
         h->err_index = detail;                                                             // NotEnoughPoints(n)
+    } else if (status == GORDER_ERR_CLUSTERING) {
+        h->err_index = h->err_frame;                                                       // the frame whose distances are not finite
     }
     char buf[200];
     snprintf(buf, sizeof(buf), "device raised %s (payload %llu) in %s", gorder_hip_strerror(status),
@@ -801,6 +809,7 @@ const char *gorder_hip_strerror(int status) {
         case GORDER_ERR_LEAFLETS_NOT_PRIMED: return "leaflet assignment missing for the first frame";
         case GORDER_ERR_OVERFLOW: return "order accumulator overflowed";
         case GORDER_ERR_TRAJECTORY_FORMAT: return "corrupt or truncated trajectory frame";
+        case GORDER_ERR_CLUSTERING: return "spherical clustering: a head-centre distance is not finite";
         default: return "unknown status";
     }
 }
@@ -1107,7 +1116,8 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
 
     const gorder_leaflets_t &lf = t->leaflets;
     if (lf.method != GORDER_LEAFLETS_NONE) {
-        if (lf.normal_dim > 2) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.normal_dim");
+        if (lf.method > GORDER_LEAFLETS_SPHERICAL) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.method");
+        if (lf.method != GORDER_LEAFLETS_SPHERICAL && lf.normal_dim > 2) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.normal_dim");
         std::vector<uint32_t> heads, mb(1, 0), ma;
         for (uint32_t m = 0; m < t->n_molecule_types; m++) {
             const gorder_moltype_t &mt = t->molecule_types[m];
@@ -1148,6 +1158,34 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
             if ((st = upload(h, &h->d_membrane, mem)) != GORDER_OK) return st;
             h->membrane_is_frame = lf.n_membrane == t->n_atoms && !env_flag("GORDER_HIP_LEAFLETS_GENERIC");
             for (uint32_t i = 0; i < lf.n_membrane && h->membrane_is_frame; i++) h->membrane_is_frame = mem[i] == i;
+        }
+        if (lf.method == GORDER_LEAFLETS_SPHERICAL) {
+            // leaflets.membrane is the group "ClusterHeads"; fewer than two atoms: NotEnoughAtomsToCluster (leaflets.rs:106-115)
+            if (!lf.membrane || lf.n_membrane < 2)
+                return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.n_membrane: spherical clustering needs at least two group atoms");
+            std::vector<uint32_t> grp(lf.membrane, lf.membrane + lf.n_membrane);
+            std::vector<int32_t> slot_of(t->n_atoms, -1);       // atom -> slot in the group
+            for (uint32_t i = 0; i < lf.n_membrane; i++) {
+                if (grp[i] >= t->n_atoms) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.membrane: index out of range");
+                if (slot_of[grp[i]] < 0) slot_of[grp[i]] = (int32_t)i;
+            }
+            // each molecule's head is its own atom of the group (get_reference_head, leaflets.rs:1340-1345).  The kernel needs
+            // no molecule -> slot table on the device: it recomputes the head's distance and responsibility from the atom.
+            for (uint32_t hd : heads)
+                if (slot_of[hd] < 0)
+                    return fail(h, GORDER_ERR_INVALID_ARGUMENT, "molecule_types[].heads: a head is not a member of leaflets.membrane");
+            if ((st = upload(h, &h->d_membrane, grp)) != GORDER_OK) return st;
+            // small groups: 256 threads a frame (16 atoms a thread, cheap barriers); larger ones 1024, and past
+            // 16 x 1024 atoms a scratch row per frame of a launch — at most 64 MiB, whatever the batch
+            h->sph_threads = lf.n_membrane <= 256u * (uint32_t)kSphKeep ? 256u : 1024u;
+            const uint32_t resident = h->sph_threads * (uint32_t)kSphKeep;
+            h->sph_spill = lf.n_membrane > resident ? lf.n_membrane - resident : 0u;
+            if (h->sph_spill) {
+                h->sph_slab = (uint32_t)std::min<size_t>(std::max<size_t>(((size_t)64 << 20) / (h->sph_spill * sizeof(float)), 1), 4096);
+                HIP_TRY(h, hipMalloc((void **)&h->d_sph_spill, (size_t)h->sph_slab * h->sph_spill * sizeof(float)));
+            }
+            HIP_TRY(h, hipMalloc((void **)&h->d_sph_stats, 12 * sizeof(float)));
+            HIP_TRY(h, hipMemset(h->d_sph_stats, 0, 12 * sizeof(float)));
         }
         // one read for global leaflets + order parameters: the tables of k_bonds_tiled<..., MOM> and k_spec_fixup
         if (lf.method == GORDER_LEAFLETS_GLOBAL && p.spec_ok && !env_flag("GORDER_HIP_NO_SPECULATE")) {
@@ -1241,6 +1279,7 @@ void gorder_hip_destroy(gorder_hip_handle *h) {
     (void)hipFree(h->d_rep);
     (void)hipFree(h->d_heads); (void)hipFree(h->d_membrane); (void)hipFree(h->d_methyl_begin);
     (void)hipFree(h->d_methyl_atoms); (void)hipFree(h->d_aflags); (void)hipFree(h->d_adist);
+    (void)hipFree(h->d_sph_spill); (void)hipFree(h->d_sph_stats);
     (void)hipFree(h->d_arow); (void)hipFree(h->d_aframes);
     (void)hipFree(h->d_lcell_of); (void)hipFree(h->d_lcell_count); (void)hipFree(h->d_lcell_fill);
     (void)hipFree(h->d_ltrig);
@@ -1372,8 +1411,27 @@ static int run_leaflets(gorder_hip_handle *h, const float *d_xyz, const float *d
                                h->stream, lb);
             done += ny;
         }
-    }
-    else if (lf.method == GORDER_LEAFLETS_LOCAL) {
+    } else if (lf.method == GORDER_LEAFLETS_SPHERICAL) {
+        // a workgroup per assignment frame; a group too large for the registers goes in slabs of frames (scratch rows)
+        TIMING_MARK(h, "k_leaflets_spherical");
+        SphArgs sa{};
+        sa.xyz = d_xyz; sa.box9 = d_box; sa.n_atoms = h->plan.n_atoms;
+        sa.aflags = h->d_aflags; sa.n_mol_total = h->plan.n_mol_total; sa.heads = h->d_heads;
+        sa.group = h->d_membrane; sa.n_group = lf.n_membrane;
+        sa.flip = lf.flip ? 1 : 0; sa.pbc = h->tables.handle_pbc ? 1 : 0;
+        sa.spill = h->d_sph_spill; sa.n_spill = h->sph_spill; sa.err = h->d_err;
+        for (size_t done = 0; done < aframes.size(); done += h->sph_slab) {
+            const uint32_t ns = (uint32_t)std::min<size_t>(aframes.size() - done, h->sph_slab);
+            const bool last = done + ns == aframes.size();
+            sa.aframes = h->d_aframes + done;
+            sa.row0 = row0 + (uint32_t)done;
+            sa.n_assign = ns;
+            sa.adist = last ? h->d_adist : nullptr;
+            sa.stats = last ? h->d_sph_stats : nullptr;
+            if (h->sph_threads == 256u) hipLaunchKernelGGL(k_leaflets_spherical<256>, dim3(ns), dim3(256), 0, h->stream, sa);
+            else hipLaunchKernelGGL(k_leaflets_spherical<1024>, dim3(ns), dim3(1024), 0, h->stream, sa);
+        }
+    } else if (lf.method == GORDER_LEAFLETS_LOCAL) {
         const size_t ncell = (size_t)kLocalMaxCells1D * kLocalMaxCells1D;
         LocalArgs lo{};
         lo.xyz = d_xyz; lo.box9 = d_box; lo.n_atoms = h->plan.n_atoms;
@@ -1850,6 +1908,15 @@ int gorder_hip_leaflet_distances(gorder_hip_handle *h, float *dist) {
     const int st = gorder_hip_synchronize(h);
     if (st != GORDER_OK) return st;
     HIP_TRY(h, hipMemcpy(dist, h->d_adist, sizeof(float) * h->plan.n_mol_total, hipMemcpyDeviceToHost));
+    return GORDER_OK;
+}
+
+int gorder_hip_spherical_stats(gorder_hip_handle *h, float out[12]) {
+    if (!h || !out || h->tables.leaflets.method != GORDER_LEAFLETS_SPHERICAL || !h->d_sph_stats) return GORDER_ERR_INVALID_ARGUMENT;
+    if (!h->have_assignment) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_spherical_stats: no assignment frame yet");
+    const int st = gorder_hip_synchronize(h);
+    if (st != GORDER_OK) return st;
+    HIP_TRY(h, hipMemcpy(out, h->d_sph_stats, 12 * sizeof(float), hipMemcpyDeviceToHost));
     return GORDER_OK;
 }
 

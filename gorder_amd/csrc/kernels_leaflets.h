@@ -2376,4 +2376,302 @@ __global__ __launch_bounds__(256) void k_local_flags_todo(LocalArgs a) {
     }
 }
 
+// ---- spherical clustering (GORDER_LEAFLETS_SPHERICAL): inner / outer leaflet of a vesicle ---------------------------
+// SystemSphericalClusterClassification::cluster (spherical_clustering.rs:42-76) and the assignment of the molecules
+// (leaflets.rs:1296-1366): per assignment frame the centre of geometry of the group "ClusterHeads", every group atom's
+// distance to it, a two-component 1-D Gaussian mixture fitted to the distances by EM (spherical_clustering.rs:118-242),
+// the component with the larger mean distance = upper (= outer) leaflet (:244-277).
+// One workgroup per assignment frame, everything of a frame on chip: a thread keeps kSphKeep distances in registers
+// (group atom i = thread + k * THREADS), the distances of a larger group's remaining atoms live in a scratch row.  All
+// sums are made of per-thread partials in a fixed order (block_sum_n), so a frame's flags and statistics depend on the
+// frame alone — not on the batch, the submit or the shard that carried it.  Nothing is kept per group atom but its
+// distance: a responsibility is a pure function of the distance and five parameters and is recomputed where it is used
+// (same instruction sequence, same bits), and a molecule's side is recomputed from its own head atom in the same way.
+constexpr int kSphKeep = 16;
+constexpr int kSphMaxIter = 50;          // GMM_MAX_ITERATIONS, spherical_clustering.rs:23
+constexpr float kSphTolerance = 1e-4f;   // GMM_TOLERANCE, spherical_clustering.rs:26
+
+struct SphArgs {
+    const float *xyz;
+    const float *box9;
+    uint32_t n_atoms;
+    const uint32_t *aframes;   // [n_assign] frame in the batch of each assignment frame of this launch
+    uint32_t row0;             // first output row
+    uint32_t n_assign;
+    uint8_t *aflags;           // [rows][n_mol_total]
+    float *adist;              // [n_mol_total] head-centre distance, written by the launch's last frame (or null)
+    float *stats;              // [12] gorder_hip_spherical_stats, written by the launch's last frame (or null)
+    uint32_t n_mol_total;
+    const uint32_t *heads;     // [n_mol_total] the molecule's own atom of the group
+    const uint32_t *group;     // [n_group] atoms of "ClusterHeads"
+    uint32_t n_group;
+    int flip, pbc;
+    float *spill;              // [frames of the launch][n_spill] distances of the group atoms past kSphKeep * THREADS
+    uint32_t n_spill;
+    uint32_t *err;
+};
+
+struct SphParams { float w, mean_a, var_a, mean_b, var_b; };   // GmmParams, spherical_clustering.rs:80-97
+
+// N sums for the price (barriers) of one, every thread gets the same totals; scratch holds N x 16 doubles
+template <int N>
+__device__ __forceinline__ void block_sum_n(double (&v)[N], double *scratch) {
+    const uint32_t wave = threadIdx.x >> 6, n_waves = (blockDim.x + 63u) >> 6;
+#pragma unroll
+    for (int q = 0; q < N; q++) {
+        v[q] = wave_sum(v[q]);
+        if ((threadIdx.x & 63u) == 0) scratch[16 * q + wave] = v[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < N; q++) {
+        double r = 0.0;
+        for (uint32_t w = 0; w < n_waves; w++) r += scratch[16 * q + w];
+        v[q] = r;
+    }
+    __syncthreads();
+}
+
+// PBC3D::distance / NoPBC::distance over XYZ (pbc.rs:354-356, 164-166)
+__device__ __forceinline__ float sph_distance(const float *p, const float (&c)[3], const float (&box)[3], int pbc, int &bad) {
+    float v[3];
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+        const float dx = p[d] - c[d];
+        v[d] = pbc ? gm_min_image(dx, box[d], bad) : dx;
+    }
+    return __builtin_sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+}
+
+// log_gaussian, spherical_clustering.rs:99-104 ((2 pi).ln() is a constant there as well)
+__device__ __forceinline__ float sph_log_gaussian(float x, float mean, float log_var, float var) {
+    const float diff = x - mean;
+    return -0.5f * ((1.8378770664093453f + log_var) + diff * diff / var);
+}
+// E-step of one observation (spherical_clustering.rs:184-192): its log-likelihood and the responsibility of component A.
+// logf / expf are the library's full-precision functions (the stopping test reads the fourth decimal of a mean of logs).
+struct SphEStep { float log_wa, log_wb, log_va, log_vb; };
+__device__ __forceinline__ SphEStep sph_estep_setup(const SphParams &p) {
+    return {logf(p.w), logf(1.0f - p.w), logf(p.var_a), logf(p.var_b)};
+}
+__device__ __forceinline__ float sph_responsibility(float x, const SphParams &p, const SphEStep &e, float &log_px) {
+    const float ja = e.log_wa + sph_log_gaussian(x, p.mean_a, e.log_va, p.var_a);
+    const float jb = e.log_wb + sph_log_gaussian(x, p.mean_b, e.log_vb, p.var_b);
+    const float m = fmaxf(ja, jb);
+    log_px = m + logf(expf(ja - m) + expf(jb - m));            // log_sum_exp, :106-111
+    return expf(ja - log_px);
+}
+
+template <uint32_t THREADS>
+__global__ __launch_bounds__(THREADS) void k_leaflets_spherical(SphArgs a) {
+    __shared__ double scratch[6 * 16];
+    __shared__ uint32_t hist[2][256];
+    __shared__ uint32_t s_pref[2], s_rank[2];
+    const uint32_t bi = blockIdx.x, tid = threadIdx.x, n = a.n_group;
+    const uint32_t f = a.aframes[bi];
+    const float *x = a.xyz + (size_t)f * a.n_atoms * 3u;
+    float *spill = a.spill + (size_t)bi * a.n_spill;
+    uint8_t *row = a.aflags + (size_t)(a.row0 + bi) * a.n_mol_total;
+    const bool last = bi + 1u == a.n_assign;
+    float box[3] = {1.0f, 1.0f, 1.0f};
+    if (a.pbc) { const float *b = a.box9 + 9 * (size_t)f; box[0] = b[0]; box[1] = b[4]; box[2] = b[8]; }
+    int bad = 0;
+
+    // ---- 1. centre of geometry of the group: refined Bai-Breen with a box (the project's group centre, k_geom_shapes /
+    // gorder_oracle_center), the plain mean without (pbc.rs:100-102)
+    float est[3] = {0.0f, 0.0f, 0.0f};
+    if (a.pbc) {
+        double cs[6] = {0, 0, 0, 0, 0, 0};
+        float inv[3];
+#pragma unroll
+        for (int d = 0; d < 3; d++) inv[d] = 1.0f / box[d];
+        for (uint32_t i = tid; i < n; i += THREADS) {
+            const float *p = x + 3u * (size_t)a.group[i];
+#pragma unroll
+            for (int d = 0; d < 3; d++) {
+                float sn, c;
+                fast_sincos_rev(gm_wrap(p[d], box[d], bad) * inv[d], &sn, &c);
+                cs[d] += (double)c;
+                cs[3 + d] += (double)sn;
+            }
+        }
+        block_sum_n<6>(cs, scratch);
+#pragma unroll
+        for (int d = 0; d < 3; d++) est[d] = (atan2f(-(float)cs[3 + d], -(float)cs[d]) + 3.1415927f) / (6.2831855f / box[d]);
+    }
+    float centre[3];
+    {
+        double acc[3] = {0, 0, 0};
+        for (uint32_t i = tid; i < n; i += THREADS) {
+            const float *p = x + 3u * (size_t)a.group[i];
+#pragma unroll
+            for (int d = 0; d < 3; d++) acc[d] += (double)(a.pbc ? gm_nearest_image(p[d], est[d], box[d], bad) : p[d]);
+        }
+        block_sum_n<3>(acc, scratch);
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            const float c = (float)(acc[d] / (double)n);
+            centre[d] = a.pbc ? gm_wrap(c, box[d], bad) : c;
+        }
+    }
+
+    // ---- 2. distances: kSphKeep a thread in registers, the rest of a large group in the frame's scratch row
+    float keep[kSphKeep];
+    double chk[2] = {0.0, 0.0};            // [0] sum of d - d (0 unless a distance is not finite), [1] sum of d
+#pragma unroll
+    for (int k = 0; k < kSphKeep; k++) {
+        const uint32_t i = tid + (uint32_t)k * THREADS;
+        keep[k] = 0.0f;
+        if (i < n) {
+            const float dd = sph_distance(x + 3u * (size_t)a.group[i], centre, box, a.pbc, bad);
+            keep[k] = dd;
+            chk[0] += (double)(dd - dd);
+            chk[1] += (double)dd;
+        }
+    }
+    for (uint32_t i = tid + (uint32_t)kSphKeep * THREADS; i < n; i += THREADS) {
+        const float dd = sph_distance(x + 3u * (size_t)a.group[i], centre, box, a.pbc, bad);
+        spill[i - (uint32_t)kSphKeep * THREADS] = dd;     // (read back by this thread only)
+        chk[0] += (double)(dd - dd);
+        chk[1] += (double)dd;
+    }
+    // fn(distance) for every group atom of this thread, always in the same order
+    auto for_each = [&](auto &&fn) {
+#pragma unroll
+        for (int k = 0; k < kSphKeep; k++)
+            if (tid + (uint32_t)k * THREADS < n) fn(keep[k]);
+        for (uint32_t i = tid + (uint32_t)kSphKeep * THREADS; i < n; i += THREADS) fn(spill[i - (uint32_t)kSphKeep * THREADS]);
+    };
+    block_sum_n<2>(chk, scratch);
+    if (bad) raise_box_range(a.err, f);
+    if (chk[0] != 0.0) {
+        // a distance that is not finite: the reference panics in the sort of initialize_params (:120)
+        if (tid == 0) raise_error(a.err, GORDER_ERR_CLUSTERING, f, kStageSystem);
+        for (uint32_t m = tid; m < a.n_mol_total; m += THREADS) row[m] = 0;
+        return;                                                        // (uniform over the workgroup)
+    }
+
+    // ---- 3. initial guess (initialize_params, :118-139): sorted[n / 4] and sorted[3 n / 4] by a radix select on the bit
+    // patterns (distances are >= +0: their bits order like their values), both ranks in the same four passes
+    uint32_t pref[2] = {0u, 0u}, rank[2] = {n / 4u, (3u * n) / 4u};
+    for (int pass = 0; pass < 4; pass++) {
+        const int shift = 24 - 8 * pass;
+        const uint32_t himask = pass ? 0xffffffffu << (shift + 8) : 0u;
+        for (uint32_t i = tid; i < 512u; i += THREADS) (&hist[0][0])[i] = 0u;
+        __syncthreads();
+        for_each([&](float dd) {
+            const uint32_t bits = __float_as_uint(dd), b = (bits >> shift) & 255u;
+            if ((bits & himask) == pref[0]) atomicAdd(&hist[0][b], 1u);      // (integer counts in LDS: order-free)
+            if ((bits & himask) == pref[1]) atomicAdd(&hist[1][b], 1u);
+        });
+        __syncthreads();
+        const uint32_t wave = tid >> 6, lane = tid & 63u;
+        if (wave < 2u) {                     // wave w finds the bin that holds rank[w]: four bins a lane, a scan over the lanes
+            const uint32_t c0 = hist[wave][4u * lane], c1 = hist[wave][4u * lane + 1u], c2 = hist[wave][4u * lane + 2u],
+                           c3 = hist[wave][4u * lane + 3u];
+            const uint32_t s = (c0 + c1) + (c2 + c3);
+            uint32_t incl = s;
+            for (uint32_t off = 1; off < 64u; off <<= 1) {
+                const uint32_t t = __shfl_up(incl, off, 64);
+                if (lane >= off) incl += t;
+            }
+            const uint32_t excl = incl - s, k = wave ? rank[1] : rank[0];
+            if (k >= excl && k < incl) {
+                uint32_t r = k - excl, b = 0u;
+                if (r >= c0) { r -= c0; b = 1u; if (r >= c1) { r -= c1; b = 2u; if (r >= c2) { r -= c2; b = 3u; } } }
+                s_pref[wave] = (wave ? pref[1] : pref[0]) | ((4u * lane + b) << shift);
+                s_rank[wave] = r;
+            }
+        }
+        __syncthreads();
+        pref[0] = s_pref[0]; pref[1] = s_pref[1];
+        rank[0] = s_rank[0]; rank[1] = s_rank[1];
+    }
+    const float n_f = (float)n;
+    SphParams p;
+    p.w = 0.5f;
+    p.mean_a = __uint_as_float(pref[0]);
+    p.mean_b = __uint_as_float(pref[1]);
+    {   // global mean and SAMPLE variance (divisor n - 1: the `statistical` crate's variance, an assumed semantic)
+        const float gmean = (float)chk[1] / n_f;
+        double sq[1] = {0.0};
+        for_each([&](float dd) { const float df = dd - gmean; sq[0] += (double)(df * df); });
+        block_sum_n<1>(sq, scratch);
+        float gvar = (float)sq[0] / (n_f - 1.0f);
+        if (!(fabsf(gvar) <= 3.40282347e+38f) || gvar <= 0.0f) gvar = 1.0f;
+        p.var_a = p.var_b = fmaxf(gvar, 1e-6f);
+    }
+
+    // ---- 4. EM (fit_gmm_1d_two_components, :152-242)
+    SphParams pe = p;                       // the parameters of the last E-step: the responsibilities the labels come from
+    float prev_ll = -__builtin_inff();
+    uint32_t iters = 0;
+    for (int it = 0; it < kSphMaxIter; it++) {
+        pe = p;
+        const SphEStep es = sph_estep_setup(pe);
+        double s4[4] = {0, 0, 0, 0};        // log-likelihood, sum r, sum r x, sum (1 - r) x
+        for_each([&](float dd) {
+            float lpx;
+            const float r = sph_responsibility(dd, pe, es, lpx);
+            s4[0] += (double)lpx;
+            s4[1] += (double)r;
+            s4[2] += (double)(r * dd);
+            s4[3] += (double)((1.0f - r) * dd);
+        });
+        block_sum_n<4>(s4, scratch);
+        iters++;
+        const float avg_ll = (float)s4[0] / n_f;
+        const bool done = fabsf(avg_ll - prev_ll) < kSphTolerance;
+        prev_ll = avg_ll;
+        if (done) break;                    // (every thread holds the same sums)
+        float sum_a = (float)s4[1], sum_b = n_f - sum_a;
+        sum_a = fmaxf(sum_a, 1e-6f);
+        sum_b = fmaxf(sum_b, 1e-6f);
+        p.w = fminf(fmaxf(sum_a / n_f, 1e-4f), 1.0f - 1e-4f);
+        p.mean_a = (float)s4[2] / sum_a;
+        p.mean_b = (float)s4[3] / sum_b;
+        double s2[2] = {0, 0};
+        for_each([&](float dd) {
+            float lpx;
+            const float r = sph_responsibility(dd, pe, es, lpx);
+            const float da = dd - p.mean_a, db = dd - p.mean_b;
+            s2[0] += (double)(r * da * da);
+            s2[1] += (double)((1.0f - r) * db * db);
+        });
+        block_sum_n<2>(s2, scratch);
+        p.var_a = fmaxf((float)s2[0] / sum_a, 1e-6f);
+        p.var_b = fmaxf((float)s2[1] / sum_b, 1e-6f);
+    }
+
+    // ---- 5. clusters (Clusters::from_responsibilities, :244-277): r < 0.5 -> cluster 1, else cluster 2; the cluster with
+    // the larger mean distance is the upper (outer) one.  An empty cluster has the mean 0 / 0 = NaN, the comparison is
+    // false and cluster 2 becomes the upper one, as in the reference.
+    const SphEStep es = sph_estep_setup(pe);
+    double cl[3] = {0, 0, 0};               // members of cluster 1, its sum of distances, cluster 2's sum of distances
+    for_each([&](float dd) {
+        float lpx;
+        const bool c1 = sph_responsibility(dd, pe, es, lpx) < 0.5f;
+        cl[0] += c1 ? 1.0 : 0.0;
+        cl[1] += c1 ? (double)dd : 0.0;
+        cl[2] += c1 ? 0.0 : (double)dd;
+    });
+    block_sum_n<3>(cl, scratch);
+    const float n1 = (float)cl[0], n2 = n_f - n1;
+    const float av1 = (float)cl[1] / n1, av2 = (float)cl[2] / n2;
+    const bool upper_is_1 = av1 > av2;
+    for (uint32_t m = tid; m < a.n_mol_total; m += THREADS) {
+        const float dd = sph_distance(x + 3u * (size_t)a.heads[m], centre, box, a.pbc, bad);
+        float lpx;
+        const bool c1 = sph_responsibility(dd, pe, es, lpx) < 0.5f;
+        row[m] = (uint8_t)((c1 == upper_is_1 ? 0 : 1) ^ (a.flip ? 1 : 0));
+        if (last && a.adist) a.adist[m] = dd;
+    }
+    if (last && a.stats && tid == 0) {
+        float *o = a.stats;
+        o[0] = centre[0]; o[1] = centre[1]; o[2] = centre[2];
+        o[3] = p.w; o[4] = p.mean_a; o[5] = p.var_a; o[6] = p.mean_b; o[7] = p.var_b;
+        o[8] = prev_ll; o[9] = (float)iters; o[10] = upper_is_1 ? n1 : n2; o[11] = 0.0f;
+    }
+}
+
 }  // namespace

@@ -235,3 +235,72 @@ def ua_membrane(n_lipids: int = 256, box=(9.0, 9.0, 8.0), seed: int = 11, leafle
     t = Tables(n_atoms=n_atoms, molecule_types=[mt], handle_pbc=handle_pbc, normal=normal, leaflets=lf,
                ordermap=ordermap or OrderMap(), timewise=timewise)
     return System(f"ua{n_lipids}", t, base, box, jitter=0.01)
+
+
+# ---- Martini vesicle: the lipids of cg_membrane on two concentric shells ------------------------------
+def cg_vesicle(n_lipids: int = 3000, inner_radius: float = 6.0, outer_radius: float = 10.0, box=None, centre=None,
+               seed: int = 5, leaflets: Optional[int] = None, sigma: float = 0.25, frequency: int = 1, flip: bool = False,
+               handle_pbc: bool = True, ordermap: Optional[OrderMap] = None, timewise: bool = False,
+               normal=(0.0, 0.0, 1.0), heads_only: bool = False):
+    """CG vesicle for spherical-clustering leaflets: n_lipids Martini lipids (12 beads, 11 bonds: the tables of cg_membrane)
+    placed radially on two shells, shared between them by area.  The PO4 heads sit at the shell radii with a radial
+    spread `sigma`, the tails point to the mid-surface; the lipids are shuffled, so the atom index says nothing about the
+    side.  `centre` defaults to the middle of the box; a centre near a corner makes the vesicle straddle the periodic
+    faces (the base frame is wrapped).  heads_only: two beads a lipid (PO4, GL1) and their one bond — large head groups.
+    leaflets defaults to LEAFLETS_SPHERICAL (the group is every PO4 bead).
+    -> (System, sides [n_lipids] uint8: 0 = outer = upper, 1 = inner = lower); System.unwrapped is the base frame before
+    wrapping (frames_unwrapped(n, seed) jitters it like frames(): the same vesicle for handle_pbc = False)."""
+    from .abi import LEAFLETS_SPHERICAL
+    if leaflets is None:
+        leaflets = LEAFLETS_SPHERICAL
+    rng = np.random.default_rng(seed)
+    if box is None:
+        box = (2.0 * outer_radius + 6.0,) * 3
+    box = np.asarray(box, dtype=np.float32)
+    centre = np.asarray(box, dtype=np.float64) / 2 if centre is None else np.asarray(centre, dtype=np.float64)
+    n_out = int(round(n_lipids * outer_radius ** 2 / (inner_radius ** 2 + outer_radius ** 2)))
+    sides = np.ones(n_lipids, dtype=np.uint8)
+    sides[:n_out] = 0
+    sides = sides[rng.permutation(n_lipids)]
+    outer = sides == 0
+    u = _unit_vectors(rng, n_lipids)
+    # a tangent per lipid for the sideways offsets of the beads
+    t = np.cross(u, _unit_vectors(rng, n_lipids))
+    t /= np.linalg.norm(t, axis=1, keepdims=True)
+    r_head = np.where(outer, outer_radius, inner_radius) + rng.normal(0.0, sigma, n_lipids)
+    inward = np.where(outer, -1.0, 1.0)            # direction of the tails along the radius
+    beads = np.array([1, 2]) if heads_only else np.arange(12)
+    bpl = len(beads)
+    base = np.zeros((n_lipids, bpl, 3), dtype=np.float64)
+    for q, b in enumerate(beads):
+        r = r_head + inward * _CG_DEPTH[b] * 0.47 * 0.75
+        if b != 1:                                  # (the head keeps its radius exactly: the spread is `sigma`)
+            r = r + rng.normal(0, 0.05, n_lipids)
+        base[:, q] = centre + r[:, None] * u + (_CG_SIDE[b] + rng.normal(0, 0.05, n_lipids) * (b != 1))[:, None] * t
+    unwrapped = base.reshape(n_lipids * bpl, 3).astype(np.float32)
+    ids = np.arange(n_lipids)
+    tb = np.array([(0, 1)], dtype=np.uint32) if heads_only else _CG_BONDS
+    bonds = (tb[:, None, :] + (ids * bpl)[None, :, None]).astype(np.uint32)
+    head_rel = 0 if heads_only else 1
+    heads = (ids * bpl + head_rel).astype(np.uint32)
+    mt = MolType(n_molecules=n_lipids, bonds=bonds, heads=heads if leaflets else None, name="LIP0")
+    lf = Leaflets(method=leaflets, frequency=frequency, flip=flip,
+                  membrane=heads.copy() if leaflets == LEAFLETS_SPHERICAL else None)
+    tables = Tables(n_atoms=n_lipids * bpl, molecule_types=[mt], handle_pbc=handle_pbc, normal=normal, leaflets=lf,
+                    ordermap=ordermap or OrderMap(), timewise=timewise)
+    system = VesicleSystem(f"vesicle{n_lipids}", tables, np.mod(unwrapped, box).astype(np.float32), box, jitter=0.03)
+    system.unwrapped = unwrapped
+    return system, sides
+
+
+class VesicleSystem(System):
+    """A System that also keeps its base frame before wrapping."""
+    unwrapped: Optional[np.ndarray] = None
+
+    def frames_unwrapped(self, n_frames: int, seed: int = 0, first: int = 0) -> np.ndarray:
+        """frames() without the wrap into the box (the same jitter): the whole vesicle, for handle_pbc = False."""
+        out = np.empty((n_frames, self.n_atoms, 3), dtype=np.float32)
+        for k in range(n_frames):
+            rng = np.random.default_rng([seed, first + k])
+            out[k] = self.unwrapped + rng.normal(0.0, self.jitter, size=self.unwrapped.shape).astype(np.float32)
+        return out

@@ -63,9 +63,12 @@ typedef enum {
                                              earlier assignment is known: call gorder_hip_prime_leaflets */
     GORDER_ERR_OVERFLOW = 105,        /* a batch was refused because frames x molecules would reach 2^63 / 1e6: an i64
                                          order sum could then overflow (the reference panics, order.rs:44-60) */
-    GORDER_ERR_TRAJECTORY_FORMAT = 106 /* a corrupt or truncated trajectory frame, met by gorder_hip_xtc_decode on the device or
+    GORDER_ERR_TRAJECTORY_FORMAT = 106,/* a corrupt or truncated trajectory frame, met by gorder_hip_xtc_decode on the device or
                                          by the host reader inside gorder_hip_run_trajectory (the reference: a read error
                                          of the trajectory iterator, common.rs:248) */
+    GORDER_ERR_CLUSTERING = 107       /* GORDER_LEAFLETS_SPHERICAL: a head-centre distance of an assignment frame is not finite
+                                         (the reference panics in the sort of spherical_clustering.rs:120);
+                                         gorder_hip_last_error_index = that frame */
 } gorder_status_t;
 
 /* ---- leaflets -------------------------------------------------------------------------------- */
@@ -74,8 +77,16 @@ typedef enum {
     GORDER_LEAFLETS_GLOBAL = 1,      /* leaflets.rs:171-205 + :711-732 */
     GORDER_LEAFLETS_LOCAL = 2,       /* leaflets.rs:661-675 + pbc.rs:273-318 + :711-732 */
     GORDER_LEAFLETS_INDIVIDUAL = 3,  /* leaflets.rs:777-801 */
-    GORDER_LEAFLETS_MANUAL = 4       /* host supplies flags per assignment frame (leaflets.rs:820-860);
+    GORDER_LEAFLETS_MANUAL = 4,      /* host supplies flags per assignment frame (leaflets.rs:820-860);
                                         Leaflet encoding Upper=0, Lower=1 (lib.rs:416-422) */
+    GORDER_LEAFLETS_SPHERICAL = 5    /* LeafletClassification::spherical_clustering (spherical_clustering.rs:42-277, leaflets.rs:
+                                        1296-1366), for vesicles: per assignment frame the centre of geometry of the group
+                                        "ClusterHeads", every group atom's distance to it, a two-component 1-D Gaussian mixture
+                                        fitted to the distances by EM; the component farther out is the upper leaflet.
+                                        `membrane` / `n_membrane` carry the group (every atom the heads query selects, ascending —
+                                        the order matters only for reproducibility; at least 2, leaflets.rs:106-115), each
+                                        molecule's `heads[k]` is its own atom of that group; normal_dim and radius are unused,
+                                        frequency and flip as for the other methods */
 } gorder_leaflet_method_t;
 
 typedef struct {
@@ -85,8 +96,9 @@ typedef struct {
                                frequency = input frequency * step (leaflets.rs:157-163) */
     uint32_t flip;          /* leaflets.rs:68-73 */
     float radius;           /* Local: cylinder radius in nm (leaflets.rs:389-418) */
-    uint32_t n_membrane;    /* Global/Local: size of group "Membrane" */
-    const uint32_t *membrane; /* atom indices (into the submitted coordinate frame) */
+    uint32_t n_membrane;    /* Global/Local: size of group "Membrane"; Spherical: size of group "ClusterHeads" (>= 2) */
+    const uint32_t *membrane; /* atom indices (into the submitted coordinate frame); Spherical: the atoms of "ClusterHeads",
+                                 among them every molecule's heads[k] */
 } gorder_leaflets_t;
 
 /* ---- ordermaps (src/analysis/ordermap.rs:40-113, input/ordermap.rs:34-50) --------------------- */
@@ -349,8 +361,14 @@ int gorder_hip_timewise(gorder_hip_handle *h, int64_t *tw_sums, uint64_t *tw_cou
 
 /* Leaflet flags of the most recent assignment frame, [n_molecules_total] (Upper=0, Lower=1). */
 int gorder_hip_leaflets(gorder_hip_handle *h, uint8_t *flags, uint64_t *assignment_frame);
-/* Signed distances (nm) behind those flags, [n_molecules_total] (leaflets.rs:725, 796). */
+/* Signed distances (nm) behind those flags, [n_molecules_total] (leaflets.rs:725, 796).  GORDER_LEAFLETS_SPHERICAL: each
+ * molecule's head-centre distance (nm, non-negative) in the last assignment frame. */
 int gorder_hip_leaflet_distances(gorder_hip_handle *h, float *distances);
+/* GORDER_LEAFLETS_SPHERICAL, the most recent assignment frame: out[0..2] centre of the group (x, y, z); out[3..7] the fitted
+ * mixture — weight_a, mean_a, var_a, mean_b, var_b (GmmParams, spherical_clustering.rs:80-97); out[8] final average
+ * log-likelihood; out[9] EM iterations run (E-steps, at most 50); out[10] group atoms labelled outer (upper, before `flip`);
+ * out[11] reserved, 0.  GORDER_ERR_INVALID_ARGUMENT for other methods or before any assignment.  Waits for the stream. */
+int gorder_hip_spherical_stats(gorder_hip_handle *h, float out[12]);
 
 /* Manual membrane normals (MembraneNormal::Manual, ManualMembraneNormal::get_normal, normal.rs:266-300): the host
  * resolves the normals file and hands over, before a submit call, one vector per frame of that batch and per
@@ -413,7 +431,7 @@ const char *gorder_hip_strerror(int status);
 
 /* Device time of the submits since the last call with reset != 0 (ms, HIP events on the stream the handle launches on) and
  * their number.  The first call switches the timing on; submits before it are not timed.  A submit is timed as a chain of
- * segments, one per kernel group it queues — the leaflet kernels ("k_leaflets_global_contig"; "k_local_build",
+ * segments, one per kernel group it queues — the leaflet kernels ("k_leaflets_global_contig"; "k_leaflets_spherical"; "k_local_build",
  * "k_local_rowprefix", "k_local_flags_rows", "k_local_flags_todo" per 256-frame slab; ...), "k_dyn_cov + k_dyn_eigen",
  * "k_geom_shapes", the order kernels ("k_bonds_tiled", "k_ua_extras", "k_bonds_tiled_maps", ...), "k_map_accumulate",
  * "k_bonds_direct", "k_batch_end" —; *ms is the sum over all segments, i.e. the WHOLE step on the device. */
