@@ -310,7 +310,7 @@ _EXPORTS = [
     "gorder_hip_normals", "gorder_hip_export_maps", "gorder_hip_set_normals",
     "gorder_hip_accumulators_device", "gorder_hip_bind_accumulators", "gorder_hip_last_error_index", "gorder_hip_last_error_frame", "gorder_hip_kernel_time_names",
     "gorder_hip_last_error_message", "gorder_hip_strerror", "gorder_hip_kernel_time", "gorder_hip_kernel_time_group", "gorder_hip_plan",
-    "gorder_hip_plan_tables", "gorder_hip_selftest_arithmetic", "gorder_hip_selftest_trig", "gorder_hip_run_trajectory",
+    "gorder_hip_plan_tables", "gorder_hip_selftest_arithmetic", "gorder_hip_selftest_trig", "gorder_hip_selftest_wave_ops", "gorder_hip_run_trajectory",
     "gorder_hip_comm_unique_id", "gorder_hip_comm_create", "gorder_hip_comm_destroy", "gorder_hip_allreduce",
     "gorder_hip_reset", "gorder_hip_xtc_decode", "gorder_hip_release_staging", "gorder_hip_speculation_stats", "gorder_hip_local_decide_stats",
     "gorder_hip_spherical_stats",
@@ -388,6 +388,7 @@ def load_library() -> C.CDLL:
     lib.gorder_hip_plan_tables.argtypes = [C.POINTER(CTables), C.POINTER(CPlan), C.POINTER(i32)]
     lib.gorder_hip_selftest_arithmetic.argtypes = [i32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.gorder_hip_selftest_trig.argtypes = [i32, i32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.gorder_hip_selftest_wave_ops.argtypes = [i32, u32, vp, vp, vp, i32, vp, vp, vp, vp]
     lib.gorder_hip_run_trajectory.argtypes = [vp, C.POINTER(CTrajectory), C.POINTER(CTrajectoryStats)]
     lib.gorder_hip_comm_unique_id.argtypes = [vp]
     lib.gorder_hip_comm_create.argtypes = [vp, vp, i32, i32, C.POINTER(vp)]
@@ -410,6 +411,30 @@ def selftest_trig(fn: str, first_bits: int, stride: int, n: int, device: int = 0
     if st != 0:
         raise GorderHipError(st, "gorder_hip_selftest_trig")
     return out
+
+
+WAVE_OPS_ROWS = (10, 16, 9, 9)     # GORDER_WAVE_OPS_F64_ROWS, _F32_ROWS, _U32_ROWS, _FINFO_WORDS
+
+
+def selftest_wave_ops(f64, f32, u32, finfo_empty: bool = False, device: int = 0):
+    """What every lane of ONE workgroup of len(f64) threads holds behind each wave / block reduction of csrc/wave_ops.h
+    (gorder_hip_selftest_wave_ops): (f64 [10][n], f32 [16][n], u32 [9][n], finfo [9]); the rows: include/gorder_hip.h."""
+    lib = load_library()
+    f64 = np.ascontiguousarray(f64, dtype=np.float64)
+    f32 = np.ascontiguousarray(f32, dtype=np.float32)
+    u32 = np.ascontiguousarray(u32, dtype=np.uint32)
+    n = len(f64)
+    if len(f32) != n or len(u32) != n:
+        raise ValueError("one value of each type per thread")
+    o64 = np.empty((WAVE_OPS_ROWS[0], n), dtype=np.float64)
+    o32 = np.empty((WAVE_OPS_ROWS[1], n), dtype=np.float32)
+    ou = np.empty((WAVE_OPS_ROWS[2], n), dtype=np.uint32)
+    fi = np.empty(WAVE_OPS_ROWS[3], dtype=np.uint32)
+    st = lib.gorder_hip_selftest_wave_ops(device, n, f64.ctypes.data, f32.ctypes.data, u32.ctypes.data, int(finfo_empty),
+                                          o64.ctypes.data, o32.ctypes.data, ou.ctypes.data, fi.ctypes.data)
+    if st != 0:
+        raise GorderHipError(st, lib.gorder_hip_strerror(st).decode())
+    return o64, o32, ou, fi
 
 
 def selftest_arithmetic(n: int = 1 << 26, seed: int = 1, device: int = 0):

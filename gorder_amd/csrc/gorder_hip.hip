@@ -907,6 +907,84 @@ int gorder_hip_selftest_trig(int device, int fn, uint32_t first_bits, uint32_t s
     return st;
 }
 
+namespace {
+// every primitive of wave_ops.h on one value per thread; row r of an output = what every lane holds behind primitive r
+// (the order of the rows: gorder_hip.h)
+__global__ __launch_bounds__(1024) void k_selftest_wave_ops(const double *in_f64, const float *in_f32, const uint32_t *in_u32,
+                                                            int finfo_empty, double *out_f64, float *out_f32, uint32_t *out_u32,
+                                                            uint4 *out_finfo) {
+    __shared__ double scratch[32];
+    __shared__ float fscratch[32], l_lo[16], l_hi[16];
+    __shared__ uint32_t l_flags[16];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, n = blockDim.x;
+    const double d = in_f64[tid];
+    const float x = in_f32[tid];
+    const uint32_t u = in_u32[tid];
+    if (tid < 16u) { l_lo[tid] = 3.0e38f; l_hi[tid] = -3.0e38f; l_flags[tid] = 0u; }   // (the waves that are not here)
+    __syncthreads();
+    double s = d, q = 3.0 * d, bs[2] = {d, 3.0 * d};
+    float lo4 = x, hi4 = x, lo2 = x, hi2 = x, lo3 = x, hi3 = x, blo = x, bhi = x;
+    uint32_t or3 = u;
+    wave_sum2_minmax_bfly(s, q, lo4, hi4);
+    wave_minmax_bfly(lo2, hi2);
+    wave_minmax_or_bfly(lo3, hi3, or3);
+    block_sum_n<2>(bs, scratch);
+    block_minmax(blo, bhi, fscratch);
+    const double o64[GORDER_WAVE_OPS_F64_ROWS] = {row_sum(d), rows_to_wave(row_sum(d)), wave_sum_rows(d), wave_scan_rows(d, lane),
+                                                  wave_sum_bfly(d), bs[0], bs[1], lane_value(d, 47), s, q};
+    const float o32[GORDER_WAVE_OPS_F32_ROWS] = {row_sum(x), rows_to_wave(row_sum(x)), wave_sum_rows(x), wave_min_rows(x),
+                                                 wave_max_rows(x), lo2, hi2, blo, bhi, dpp_or_self<0x111>(x),
+                                                 dpp_or_zero<0x143, 0xc>(x), lane_value(x, 47), lo4, hi4, lo3, hi3};
+    const uint32_t ou[GORDER_WAVE_OPS_U32_ROWS] = {row_sum(u), rows_to_wave(row_sum(u)), wave_sum_rows(u), wave_scan_rows(u, lane),
+                                                   wave_scan_shfl(u, lane), or3, wave_max_bfly(u),
+                                                   (uint32_t)wave_sum_rows((int)u), lane_value(u, 47)};
+    for (int r = 0; r < GORDER_WAVE_OPS_F64_ROWS; r++) out_f64[r * n + tid] = o64[r];
+    for (int r = 0; r < GORDER_WAVE_OPS_F32_ROWS; r++) out_f32[r * n + tid] = o32[r];
+    for (int r = 0; r < GORDER_WAVE_OPS_U32_ROWS; r++) out_u32[r * n + tid] = ou[r];
+    // the finfo record twice: every flag kept, and bit 0 only; word 8 = the flags thread 0 leaves the fold with
+    const float zlo = finfo_empty ? 3.0e38f : x, zhi = finfo_empty ? -3.0e38f : x;
+    uint32_t fl = u;
+    block_finfo_record(zlo, zhi, fl, ~0u, l_lo, l_hi, l_flags, out_finfo);
+    if (tid == 0u) out_finfo[2].x = fl;
+    __syncthreads();
+    fl = u;
+    block_finfo_record(zlo, zhi, fl, 1u, l_lo, l_hi, l_flags, out_finfo + 1);
+}
+}  // namespace
+
+int gorder_hip_selftest_wave_ops(int device, uint32_t block, const double *f64, const float *f32, const uint32_t *u32,
+                                 int finfo_empty, double *out_f64, float *out_f32, uint32_t *out_u32, uint32_t *out_finfo) {
+    if (!f64 || !f32 || !u32 || !out_f64 || !out_f32 || !out_u32 || !out_finfo || block < 64u || block > 1024u || (block & 63u))
+        return GORDER_ERR_INVALID_ARGUMENT;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return GORDER_ERR_NO_DEVICE;
+    if (device < 0 || device >= count || hipSetDevice(device) != hipSuccess) return GORDER_ERR_INVALID_ARGUMENT;
+    // one allocation: the inputs, then the outputs, the widest type first (everything stays aligned)
+    const size_t n = block, b_fi = 0, b_i64 = 48, b_o64 = b_i64 + 8 * n, b_i32 = b_o64 + 8 * n * GORDER_WAVE_OPS_F64_ROWS,
+                 b_iu = b_i32 + 4 * n, b_o32 = b_iu + 4 * n, b_ou = b_o32 + 4 * n * GORDER_WAVE_OPS_F32_ROWS,
+                 bytes = b_ou + 4 * n * GORDER_WAVE_OPS_U32_ROWS;
+    char *d = nullptr;
+    if (hipMalloc((void **)&d, bytes) != hipSuccess) return GORDER_ERR_DEVICE;
+    int st = GORDER_OK;
+    if (hipMemset(d, 0, bytes) != hipSuccess || hipMemcpy(d + b_i64, f64, 8 * n, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d + b_i32, f32, 4 * n, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d + b_iu, u32, 4 * n, hipMemcpyHostToDevice) != hipSuccess)
+        st = GORDER_ERR_DEVICE;
+    if (st == GORDER_OK) {
+        hipLaunchKernelGGL(k_selftest_wave_ops, dim3(1), dim3(block), 0, 0, (const double *)(d + b_i64), (const float *)(d + b_i32),
+                           (const uint32_t *)(d + b_iu), finfo_empty, (double *)(d + b_o64), (float *)(d + b_o32),
+                           (uint32_t *)(d + b_ou), (uint4 *)(d + b_fi));
+        if (hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(out_f64, d + b_o64, 8 * n * GORDER_WAVE_OPS_F64_ROWS, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(out_f32, d + b_o32, 4 * n * GORDER_WAVE_OPS_F32_ROWS, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(out_u32, d + b_ou, 4 * n * GORDER_WAVE_OPS_U32_ROWS, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(out_finfo, d + b_fi, 4 * GORDER_WAVE_OPS_FINFO_WORDS, hipMemcpyDeviceToHost) != hipSuccess)
+            st = GORDER_ERR_DEVICE;
+    }
+    (void)hipFree(d);
+    return st;
+}
+
 int gorder_hip_plan_tables(const gorder_tables_t *tables, gorder_hip_plan_t *out, int *selfcheck) {
     if (!tables || !out) return GORDER_ERR_INVALID_ARGUMENT;
     Plan p;

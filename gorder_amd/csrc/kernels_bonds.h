@@ -335,17 +335,8 @@ struct TiledStage {
 // normal coordinate of the atoms this tile OWNS (FrameArgs::own) out of the window that is in LDS anyway — relative to the
 // middle of the box, with its square and the extrema; a NaN coordinate poisons the sums — and leaves them for
 // k_spec_resolve: mom[frame][tile].  Five instructions an atom, no sine or cosine.
-// a wave reduction by DPP alone: four shifts inside the rows of 16, then the rows' results passed on (row_bcast:15 into
-// rows 1 and 3, row_bcast:31 into the upper half): the total ends up in lane 63.  Sums take 0 where the control names no
-// lane (bound_ctrl: the shift folds into the add), extrema their own value.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float mom_dpp0(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, true));
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float mom_dpp_self(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
-}
+// The wave reduction is the row order of wave_ops.h (the total ends up in lane 63), the sums by its dpp_or_zero, the
+// extrema by the hardware's own DPP forms:
 // v_min_f32 / v_max_f32 as the hardware has them: `fminf` makes the compiler canonicalise both operands first (a v_max x, x, x
 // each — over a hundred extra instructions in the moments), and a NaN does not matter here: the finiteness of the staged
 // floats is checked on its own.  The DPP forms write only the lanes whose source lane exists (the others keep their value);
@@ -381,7 +372,7 @@ __device__ __forceinline__ void tiled_moments(const FrameArgs &a, const Tile &t,
         }
     }
 #define GORDER_MOM_STEP(CTRL, MASK, CTRL_TEXT)                                                  \
-    s += mom_dpp0<CTRL, MASK>(s); q += mom_dpp0<CTRL, MASK>(q);                                 \
+    s += dpp_or_zero<CTRL, MASK>(s); q += dpp_or_zero<CTRL, MASK>(q);                               \
     GORDER_MOM_MINMAX_DPP(CTRL_TEXT);
     GORDER_MOM_STEP(0x111, 0xf, "row_shr:1 row_mask:0xf bank_mask:0xf")
     GORDER_MOM_STEP(0x112, 0xf, "row_shr:2 row_mask:0xf bank_mask:0xf")

@@ -3,6 +3,8 @@
 // leaflets, normals); device code for gfx950 only.
 #pragma once
 
+#include "wave_ops.h"
+
 namespace {
 
 constexpr int kFramesPerStage = 4;   // G: frames staged in LDS per barrier pair (= waves per block)

@@ -1001,20 +1001,6 @@ __device__ __noinline__ UaBonds ua_carbon_slow(uint32_t kind, UaCarbon c, UaCons
     return ua_carbon(kind, c, e, pl);
 }
 
-// sums of an int over the DPP rows of a wave (16 lanes each; row shifts: every lane of the wave must be here): lane 15 of
-// a row gets the row's sum
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ int ua_dpp_add(int v) { return v + __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, true); }
-__device__ __forceinline__ int ua_row_sum(int v) {
-    v = ua_dpp_add<0x111>(v); v = ua_dpp_add<0x112>(v); v = ua_dpp_add<0x114>(v); v = ua_dpp_add<0x118>(v);
-    return v;
-}
-// ... and on over the rows (row broadcasts): lane 63 gets the wave's sum
-__device__ __forceinline__ int ua_rows_to_wave(int v) {
-    v = ua_dpp_add<0x142, 0xa>(v); v = ua_dpp_add<0x143, 0xc>(v);
-    return v;
-}
-
 // MODE 0: order parameters only; 1: + staged ordermap samples, nothing else (no geometry selection, timewise rows or
 // per-molecule normals — the common ordermap run, and a much smaller kernel); 2: every extra; 3: per-frame rows, nothing else
 // FAST: GORDER_FLAG_UA_FAST_NORMALISE (ua_carbon_fast; inv_box holds 1 / box edge per frame).  PREFETCH: the next frame's
@@ -1248,8 +1234,8 @@ __device__ __forceinline__ void ua_extras_body(FrameArgs a_in, ExtraArgs e, cons
 #pragma unroll
             for (int k = 0; k < 3; k++) {
                 if (k >= nh_wave) break;                            // (uniform)
-                int s_all = ua_row_sum(tw_s[k]), s_low = ua_row_sum(tw_sl[k]), n = ua_row_sum(tw_n[k]);
-                if (wave_one_slot) { s_all = ua_rows_to_wave(s_all); s_low = ua_rows_to_wave(s_low); n = ua_rows_to_wave(n); }
+                int s_all = row_sum(tw_s[k]), s_low = row_sum(tw_sl[k]), n = row_sum(tw_n[k]);
+                if (wave_one_slot) { s_all = rows_to_wave(s_all); s_low = rows_to_wave(s_low); n = rows_to_wave(n); }
                 const uint32_t n_all = (uint32_t)n & 0xffffu, n_low = (uint32_t)n >> 16;
                 const bool sender = wave_one_slot ? (tid & 63u) == 63u : (tid & 15u) == 15u;
                 // (a wave that ends inside the tile: its last rows are idle, the wave's slot is that of its first lane)
@@ -1368,11 +1354,7 @@ __global__ __launch_bounds__(1024) void k_map_accumulate(const unsigned long lon
                 uint32_t carry = 0;
                 for (uint32_t i0 = 1; i0 <= nr; i0 += 64u) {
                     const uint32_t i = i0 + threadIdx.x, v = i <= nr ? l_pref[i] : 0u;
-                    uint32_t incl = v;
-                    for (uint32_t off = 1; off < 64u; off <<= 1) {
-                        const uint32_t u = __shfl_up(incl, off, 64);
-                        if (threadIdx.x >= off) incl += u;
-                    }
+                    const uint32_t incl = wave_scan_shfl(v, threadIdx.x);
                     if (i <= nr) l_pref[i] = carry + incl;
                     carry += __shfl(incl, 63, 64);
                 }

@@ -42,37 +42,6 @@ __device__ __forceinline__ void fast_sincos_rev(float u, float *sn, float *cs) {
     *cs = __builtin_amdgcn_cosf(u);
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// deterministic block reduction: butterfly inside each wave, then every thread adds the <= 16 wave
-// totals in the same order (2 barriers)
-__device__ __forceinline__ double block_sum(double v, double *scratch) {
-    v = wave_sum(v);
-    const uint32_t wave = threadIdx.x >> 6, n_waves = (blockDim.x + 63u) >> 6;
-    if ((threadIdx.x & 63u) == 0) scratch[wave] = v;
-    __syncthreads();
-    double r = 0.0;
-    for (uint32_t w = 0; w < n_waves; w++) r += scratch[w];
-    __syncthreads();
-    return r;
-}
-
-// two sums for the price (barriers) of one; scratch holds 2 x 16 doubles
-__device__ __forceinline__ void block_sum2(double &v0, double &v1, double *scratch) {
-    v0 = wave_sum(v0);
-    v1 = wave_sum(v1);
-    const uint32_t wave = threadIdx.x >> 6, n_waves = (blockDim.x + 63u) >> 6;
-    if ((threadIdx.x & 63u) == 0) { scratch[wave] = v0; scratch[16 + wave] = v1; }
-    __syncthreads();
-    double r0 = 0.0, r1 = 0.0;
-    for (uint32_t w = 0; w < n_waves; w++) { r0 += scratch[w]; r1 += scratch[16 + w]; }
-    __syncthreads();
-    v0 = r0; v1 = r1;
-}
-
 // ---- per-frame shapes of the geometry selection: GeometrySelection::init_reference (geometry.rs:192-210)
 // + construct_shape (geometry.rs:328-357, 422-451, 507-514).  One block per frame; a group reference needs
 // the centre of geometry of the group (refined Bai-Breen, like the global membrane centre).
@@ -289,18 +258,6 @@ __global__ __launch_bounds__(1024) void k_leaflets_global(LeafletArgs a) {
 // half box around it — any membrane thinner than half the box), then sum MI(z - est) = sum u + n (z_ref - est)
 // and the refinement needs no second look at the data; otherwise the frame is read again.  256-thread blocks,
 // nothing kept per atom: several frames per CU overlap their load and reduction phases.
-__device__ __forceinline__ void block_minmax(float &lo, float &hi, float *scratch /* 2 x 16 */) {
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, off, 64));
-        hi = fmaxf(hi, __shfl_xor(hi, off, 64));
-    }
-    const uint32_t wave = threadIdx.x >> 6, n_waves = (blockDim.x + 63u) >> 6;
-    if ((threadIdx.x & 63u) == 0) { scratch[wave] = lo; scratch[16 + wave] = hi; }
-    __syncthreads();
-    for (uint32_t w = 0; w < n_waves; w++) { lo = fminf(lo, scratch[w]); hi = fmaxf(hi, scratch[16 + w]); }
-    __syncthreads();
-}
-
 __device__ __forceinline__ void leaflets_global_contig_frame(const LeafletArgs &a, uint32_t bi) {
     __shared__ double scratch[32];
     __shared__ float fscratch[32];
@@ -401,10 +358,10 @@ __device__ __forceinline__ void leaflets_global_contig_frame(const LeafletArgs &
         chunk(__builtin_nontemporal_load(src + c), c, r);
         r = r == 0 ? 2u : r - 1u;
     }
-    double tc = (double)sc, ts = (double)ss;
-    block_sum2(tc, ts, scratch);
-    double tu = (double)su, nf = (double)nonfinite;
-    block_sum2(tu, nf, scratch);
+    double cs2[2] = {(double)sc, (double)ss}, un[2] = {(double)su, (double)nonfinite};
+    block_sum_n<2>(cs2, scratch);
+    block_sum_n<2>(un, scratch);
+    const double tc = cs2[0], ts = cs2[1], tu = un[0], nf = un[1];
     block_minmax(ulo, uhi, fscratch);
     float center;
     if (!pbc) {
@@ -516,10 +473,7 @@ __global__ __launch_bounds__(256) void k_spec_check(SpecArgs a) {
                 S += (double)m.x; Q += (double)m.y;
                 mn = fminf(mn, m.z); mx = fmaxf(mx, m.w);
             }
-            for (int off = 32; off >= 1; off >>= 1) {
-                S += __shfl_xor(S, off, 64); Q += __shfl_xor(Q, off, 64);
-                mn = fminf(mn, __shfl_xor(mn, off, 64)); mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-            }
+            wave_sum2_minmax_bfly(S, Q, mn, mx);
             if (threadIdx.x == 0u) {
                 const double n = (double)a.n_membrane, c = S / n;
                 bool ok = (S - S == 0.0) && (Q - Q == 0.0) && mn <= mx;             // finite sums, at least one atom
@@ -798,14 +752,6 @@ __device__ __forceinline__ void local_grid(const LocalArgs &a, const float *box,
     local_grid(a, box, nca, ncb, da, db, ka, kb);
 }
 
-// ordered-integer image of a float (monotonic for every non-NaN value): atomicMin / atomicMax on floats of either sign
-__device__ __forceinline__ uint32_t local_float_key(float v) {
-    const uint32_t b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float local_key_float(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 // finfo[s] as the kernels keep it while it is being made: (key of the minimum, key of the maximum, 1 if a coordinate is
 // not finite, -); set to (max key, 0, 0, 0) by whoever writes grid[s]
 __device__ __forceinline__ void local_finfo_init(const LocalArgs &a, uint32_t s) {
@@ -952,30 +898,6 @@ __global__ __launch_bounds__(256) void k_local_scatter(LocalArgs a) {
     }
 }
 
-template <int CTRL>
-__device__ __forceinline__ float row_add(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-template <int CTRL>
-__device__ __forceinline__ float row_shifted(float v) {      // out-of-row lanes keep their own value
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-template <int CTRL>
-__device__ __forceinline__ double row_add_f64(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, true);
-    return v + __hiloint2double(hi, lo);
-}
-template <int CTRL>
-__device__ __forceinline__ uint32_t row_add_u32(uint32_t v) {
-    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
-}
-// the value one lane holds, for every lane (lane index known at compile time: v_readlane, no LDS)
-__device__ __forceinline__ float lane_value(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-__device__ __forceinline__ double lane_value(double v, int l) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
 // Per row of cells: running sums along the row (the halo cells continue it), so that k_local_flags_rows takes the
 // cells of a row that lie wholly inside a head's cylinder — always one span of consecutive cells — as the difference
 // of two entries:  rowpre[ra (ncs + 1) + j] = sums over the cells 0 .. j-1 of row ra (cos and sin of the normal angle
@@ -1048,10 +970,7 @@ __device__ __forceinline__ void local_row_prefix(const uint32_t *__restrict__ cs
         const double z1 = vz[0], z2 = z1 + vz[1], z3 = z2 + vz[2], tz = z3 + vz[3];
         float ic = tc, is = ts, iq = tq;
         double iz = tz;
-        ic = row_add<0x111>(ic); is = row_add<0x111>(is); iz = row_add_f64<0x111>(iz); iq = row_add<0x111>(iq);
-        ic = row_add<0x112>(ic); is = row_add<0x112>(is); iz = row_add_f64<0x112>(iz); iq = row_add<0x112>(iq);
-        ic = row_add<0x114>(ic); is = row_add<0x114>(is); iz = row_add_f64<0x114>(iz); iq = row_add<0x114>(iq);
-        ic = row_add<0x118>(ic); is = row_add<0x118>(is); iz = row_add_f64<0x118>(iz); iq = row_add<0x118>(iq);
+        row_sums(ic, is, iz, iq);
         float bc = 0.0f, bs = 0.0f, bq = 0.0f;
         double bz = 0.0;
 #pragma unroll
@@ -1101,11 +1020,7 @@ __device__ __forceinline__ void local_row_prefix(const uint32_t *__restrict__ cs
 }
 // the frame's extrema of the normal coordinate and its "a coordinate is not finite" flag, from one wave
 __device__ __forceinline__ void local_finfo_merge(const LocalArgs &a, uint32_t s, float zlo, float zhi, uint32_t nf) {
-    for (int off = 32; off >= 1; off >>= 1) {
-        zlo = fminf(zlo, __shfl_xor(zlo, off, 64));
-        zhi = fmaxf(zhi, __shfl_xor(zhi, off, 64));
-        nf |= (uint32_t)__shfl_xor((int)nf, off, 64);
-    }
+    wave_minmax_or_bfly(zlo, zhi, nf);
     if ((threadIdx.x & 63u) == 0u) {
         uint32_t *fi = reinterpret_cast<uint32_t *>(a.finfo + s);
         if (zlo <= zhi) {
@@ -1253,12 +1168,7 @@ __global__ __launch_bounds__(1024) void k_local_build(LocalArgs a) {
             cnt[k] = c0 + k < ncell ? l_start[c0 + k] : 0u;
             sum += cnt[k];
         }
-        uint32_t incl = sum;
-#pragma unroll
-        for (uint32_t off = 1; off < 64u; off <<= 1) {
-            const uint32_t v = __shfl_up(incl, off, 64);
-            if ((tid & 63u) >= off) incl += v;
-        }
+        const uint32_t incl = wave_scan_shfl(sum, tid & 63u);
         if ((tid & 63u) == 63u) l_wave[tid >> 6] = incl;
         __syncthreads();
         uint32_t run = incl - sum;
@@ -1316,18 +1226,7 @@ __global__ __launch_bounds__(1024) void k_local_build(LocalArgs a) {
     if (a.finfo) {
         __shared__ float l_zlo[16], l_zhi[16];
         __shared__ uint32_t l_nf[16];
-        for (int off = 32; off >= 1; off >>= 1) {
-            zlo = fminf(zlo, __shfl_xor(zlo, off, 64));
-            zhi = fmaxf(zhi, __shfl_xor(zhi, off, 64));
-            nf |= (uint32_t)__shfl_xor((int)nf, off, 64);
-        }
-        if ((tid & 63u) == 0u) { l_zlo[tid >> 6] = zlo; l_zhi[tid >> 6] = zhi; l_nf[tid >> 6] = nf; }
-        __syncthreads();
-        if (tid == 0) {
-            for (uint32_t w = 1; w < 16u; w++) { zlo = fminf(zlo, l_zlo[w]); zhi = fmaxf(zhi, l_zhi[w]); nf |= l_nf[w]; }
-            reinterpret_cast<uint4 *>(a.finfo)[s] = zlo <= zhi ? make_uint4(local_float_key(zlo), local_float_key(zhi), nf, 2u)
-                                                                : make_uint4(0xffffffffu, 0u, nf, 2u);
-        }
+        block_finfo_record(zlo, zhi, nf, ~0u, l_zlo, l_zhi, l_nf, reinterpret_cast<uint4 *>(a.finfo) + s);
     }
     // (The rows' prefix sums stay a kernel of their own, k_local_rowprefix: done here behind pass 2 — a wave per row, six
     // rows per wave, the records still in this XCD's L2 — they took 190 us per 256 frames against 100 for the kernel,
@@ -1348,66 +1247,6 @@ __host__ __device__ inline float local_radius_threshold(float r) {
         thr = p;
     }
     return thr;
-}
-
-// Sum over the 64 lanes by DPP row shifts (cheaper than six ds_bpermute round trips per sum).
-// Within a row of 16 lanes a Hillis-Steele scan leaves the row total in its last lane; row_bcast:15 and
-// row_bcast:31 carry the totals on, lane 63 ends with the wave total.  Fixed order => deterministic.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_add_f64(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xf, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xf, true);
-    return v + __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double wave_total(double v) {
-    v = dpp_add_f64<0x111, 0xf>(v);   // row_shr:1
-    v = dpp_add_f64<0x112, 0xf>(v);   // row_shr:2
-    v = dpp_add_f64<0x114, 0xf>(v);   // row_shr:4
-    v = dpp_add_f64<0x118, 0xf>(v);   // row_shr:8
-    v = dpp_add_f64<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-    v = dpp_add_f64<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63), hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
-    return __hiloint2double(hi, lo);
-}
-
-
-// The same row-shift reductions for values whose last digits do not reach the result (the circular sums only make the
-// ESTIMATE, the member count is an integer): one DPP-modified add / min / max per step instead of three for an f64.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_add_f32(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, true));
-}
-__device__ __forceinline__ float wave_total_f32(float v) {
-    v = dpp_add_f32<0x111, 0xf>(v); v = dpp_add_f32<0x112, 0xf>(v); v = dpp_add_f32<0x114, 0xf>(v); v = dpp_add_f32<0x118, 0xf>(v);
-    v = dpp_add_f32<0x142, 0xa>(v); v = dpp_add_f32<0x143, 0xc>(v);
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_add_u32(uint32_t v) {
-    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, true);
-}
-__device__ __forceinline__ uint32_t wave_total_u32(uint32_t v) {
-    v = dpp_add_u32<0x111, 0xf>(v); v = dpp_add_u32<0x112, 0xf>(v); v = dpp_add_u32<0x114, 0xf>(v); v = dpp_add_u32<0x118, 0xf>(v);
-    v = dpp_add_u32<0x142, 0xa>(v); v = dpp_add_u32<0x143, 0xc>(v);
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-// minimum / maximum over the wave: lanes without a source keep their own value (bound_ctrl off, old = the value itself)
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_keep_f32(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
-}
-__device__ __forceinline__ float wave_min_f32(float v) {
-    v = fminf(v, dpp_keep_f32<0x111, 0xf>(v)); v = fminf(v, dpp_keep_f32<0x112, 0xf>(v));
-    v = fminf(v, dpp_keep_f32<0x114, 0xf>(v)); v = fminf(v, dpp_keep_f32<0x118, 0xf>(v));
-    v = fminf(v, dpp_keep_f32<0x142, 0xa>(v)); v = fminf(v, dpp_keep_f32<0x143, 0xc>(v));
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-__device__ __forceinline__ float wave_max_f32(float v) {
-    v = fmaxf(v, dpp_keep_f32<0x111, 0xf>(v)); v = fmaxf(v, dpp_keep_f32<0x112, 0xf>(v));
-    v = fmaxf(v, dpp_keep_f32<0x114, 0xf>(v)); v = fmaxf(v, dpp_keep_f32<0x118, 0xf>(v));
-    v = fmaxf(v, dpp_keep_f32<0x142, 0xa>(v)); v = fmaxf(v, dpp_keep_f32<0x143, 0xc>(v));
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
 // block = 256 threads = 4 waves = 4 heads; grid = (ceil(n_mol / 4), n_slab).  A head's candidates are
@@ -1592,19 +1431,19 @@ __device__ __noinline__ void local_flags_head(const LocalArgs &a, uint32_t s, ui
             }
         }
     }
-    const double tcnt = (double)wave_total_u32(cnt);
+    const double tcnt = (double)wave_sum_rows(cnt);
     if (tcnt == 0.0 || __any(nf != 0u)) {
         if (lane == 0) raise_error(a.err, GORDER_ERR_INVALID_LOCAL_MEMBRANE_CENTER, f, kStageTypes, a.mol_slot0 ? a.mol_slot0[m] : 0u, 0, m);
         return;
     }
     float center;
     if (!pbc) {
-        center = (float)(wave_total((double)sp) / tcnt);
+        center = (float)(wave_sum_rows((double)sp) / tcnt);
     } else {
-        const float tc = wave_total_f32(sc), ts = wave_total_f32(ss);        // the estimate only anchors the image choice
+        const float tc = wave_sum_rows(sc), ts = wave_sum_rows(ss);        // the estimate only anchors the image choice
         const float est = (atan2f(-ts, -tc) + 3.1415927f) / (6.2831855f / Ln);
-        ulo = wave_min_f32(ulo);
-        uhi = wave_max_f32(uhi);
+        ulo = wave_min_rows(ulo);
+        uhi = wave_max_rows(uhi);
         const float shift = gm_min_image(hn_pos - est, Ln, bad), half = Ln / 2.0f, margin = 1e-4f * Ln;
         const bool one_pass = ulo + shift > -half + margin && uhi + shift < half - margin;   // wave-uniform
         // pass 2 (only for a membrane thicker than half the box): refine with the mean minimum-image displacement
@@ -1623,8 +1462,8 @@ __device__ __noinline__ void local_flags_head(const LocalArgs &a, uint32_t s, ui
                 }
             }
         }
-        if (one_pass) center = gm_wrap((est + shift) + (float)(wave_total((double)su) / tcnt), Ln, bad);
-        else center = gm_wrap(est + (float)(wave_total((double)ref) / tcnt), Ln, bad);
+        if (one_pass) center = gm_wrap((est + shift) + (float)(wave_sum_rows((double)su) / tcnt), Ln, bad);
+        else center = gm_wrap(est + (float)(wave_sum_rows((double)ref) / tcnt), Ln, bad);
     }
     if (lane == 0) {
         if (center != center) {
@@ -1833,14 +1672,8 @@ __device__ __forceinline__ void local_rows_group(const LocalArgs &a, uint32_t s,
     // A wave whose four heads are all decided skips the lists, the ring loop and the centre; any other wave does everything
     // as before (and finds the same sides).
     if (try_prune) {
-        c_n = row_add_u32<0x111>(c_n); r_n = row_add_u32<0x111>(r_n); c_z = row_add<0x111>(c_z); r_z = row_add<0x111>(r_z); r_q = row_add<0x111>(r_q);
-        c_n = row_add_u32<0x112>(c_n); r_n = row_add_u32<0x112>(r_n); c_z = row_add<0x112>(c_z); r_z = row_add<0x112>(r_z); r_q = row_add<0x112>(r_q);
-        c_n = row_add_u32<0x114>(c_n); r_n = row_add_u32<0x114>(r_n); c_z = row_add<0x114>(c_z); r_z = row_add<0x114>(r_z); r_q = row_add<0x114>(r_q);
-        c_n = row_add_u32<0x118>(c_n); r_n = row_add_u32<0x118>(r_n); c_z = row_add<0x118>(c_z); r_z = row_add<0x118>(r_z); r_q = row_add<0x118>(r_q);
-        c_c = row_add<0x111>(c_c); c_s = row_add<0x111>(c_s);
-        c_c = row_add<0x112>(c_c); c_s = row_add<0x112>(c_s);
-        c_c = row_add<0x114>(c_c); c_s = row_add<0x114>(c_s);
-        c_c = row_add<0x118>(c_c); c_s = row_add<0x118>(c_s);
+        row_sums(c_n, r_n, c_z, r_z, r_q);
+        row_sums(c_c, c_s);
         const float hm = hn_pos - z_mid, fn = (float)c_n, fr = (float)r_n, fi = (float)(c_n - r_n);
         const float T = c_z - fn * hm, A = r_z - fr * hm;
         const float B = __builtin_fmaxf((r_q - 2.0f * hm * r_z) + fr * hm * hm, 0.0f) * 1.02f + 1e-3f * fr;
@@ -1879,10 +1712,8 @@ __device__ __forceinline__ void local_rows_group(const LocalArgs &a, uint32_t s,
     {
         const uint32_t n_a = run_q1[0] - run_q0[0], n_b = run_q1[1] - run_q0[1];
         const uint32_t p_a = (n_a + 7u) >> 3, p_b = (n_b + 7u) >> 3, mine = p_a + p_b;
-        uint32_t incl = mine;
-        incl = row_add_u32<0x111>(incl); incl = row_add_u32<0x112>(incl); incl = row_add_u32<0x114>(incl); incl = row_add_u32<0x118>(incl);
-        const uint32_t t0 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 15), t1 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 31);
-        const uint32_t t2 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 47), t3 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        const uint32_t incl = row_sum(mine);
+        const uint32_t t0 = lane_value(incl, 15), t1 = lane_value(incl, 31), t2 = lane_value(incl, 47), t3 = lane_value(incl, 63);
         n_ring = row == 0u ? t0 : (row == 1u ? t1 : (row == 2u ? t2 : t3));
         // (a piece = the BYTE offsets of its first record and of the end of its run: the loop below adds a lane's share)
         constexpr uint32_t kRec = (uint32_t)sizeof(LocalRec);
@@ -1942,11 +1773,8 @@ __device__ __forceinline__ void local_rows_group(const LocalArgs &a, uint32_t s,
     redo |= t_min < 0.0f;
     // ---- per row: totals in lane 15 of the row (row shifts only), then the centre as in the general passes
     double tu = (double)su + inner_z;
-    tu = row_add_f64<0x111>(tu); tu = row_add_f64<0x112>(tu); tu = row_add_f64<0x114>(tu); tu = row_add_f64<0x118>(tu);
-    sc = row_add<0x111>(sc); ss = row_add<0x111>(ss); cnt = row_add_u32<0x111>(cnt); n_inner = row_add_u32<0x111>(n_inner);
-    sc = row_add<0x112>(sc); ss = row_add<0x112>(ss); cnt = row_add_u32<0x112>(cnt); n_inner = row_add_u32<0x112>(n_inner);
-    sc = row_add<0x114>(sc); ss = row_add<0x114>(ss); cnt = row_add_u32<0x114>(cnt); n_inner = row_add_u32<0x114>(n_inner);
-    sc = row_add<0x118>(sc); ss = row_add<0x118>(ss); cnt = row_add_u32<0x118>(cnt); n_inner = row_add_u32<0x118>(n_inner);
+    tu = row_sum(tu);
+    row_sums(sc, ss, cnt, n_inner);
     const uint64_t redo_mask = __ballot(redo);
     const bool row_redo = ((redo_mask >> (16u * row)) & 0xffffull) != 0ull;
     bool general = fail || row_redo;
@@ -2053,19 +1881,6 @@ __device__ __attribute__((noinline)) LocalWrapped local_wrap_far(float xa, float
     w.b = gm_wrap(xb, Lb, w.bad);
     return w;
 }
-__device__ __forceinline__ uint32_t wave_scan_u32(uint32_t v, uint32_t lane) {         // inclusive, over the 64 lanes
-    v = row_add_u32<0x111>(v); v = row_add_u32<0x112>(v); v = row_add_u32<0x114>(v); v = row_add_u32<0x118>(v);
-    const uint32_t t0 = (uint32_t)__builtin_amdgcn_readlane((int)v, 15), t1 = (uint32_t)__builtin_amdgcn_readlane((int)v, 31),
-                   t2 = (uint32_t)__builtin_amdgcn_readlane((int)v, 47);
-    const uint32_t r = lane >> 4;
-    return v + (r > 0u ? t0 : 0u) + (r > 1u ? t1 : 0u) + (r > 2u ? t2 : 0u);
-}
-__device__ __forceinline__ double wave_scan_f64(double v, uint32_t lane) {             // (exact: the values are integers below 2^53)
-    v = row_add_f64<0x111>(v); v = row_add_f64<0x112>(v); v = row_add_f64<0x114>(v); v = row_add_f64<0x118>(v);
-    const double t0 = lane_value(v, 15), t1 = lane_value(v, 31), t2 = lane_value(v, 47);
-    const uint32_t r = lane >> 4;
-    return v + (r > 0u ? t0 : 0.0) + (r > 1u ? t1 : 0.0) + (r > 2u ? t2 : 0.0);
-}
 __global__ __launch_bounds__(1024) void k_local_sums(LocalArgs a) {
     extern __shared__ unsigned long long l_sums[];
     __shared__ float l_zlo[16], l_zhi[16];
@@ -2148,8 +1963,8 @@ __global__ __launch_bounds__(1024) void k_local_sums(LocalArgs a) {
             const uint32_t n = (uint32_t)(vb >> 42), ci = (uint32_t)(vb >> 21) & 0x1fffffu, si = (uint32_t)vb & 0x1fffffu;
             const double zi = (double)(uint32_t)(va >> 32), qi = (double)(uint32_t)va;
             flag |= n > 4095u ? 2u : 0u;
-            const uint32_t i_n = wave_scan_u32(n, lane), i_c = wave_scan_u32(ci, lane), i_s = wave_scan_u32(si, lane);
-            const double i_z = wave_scan_f64(zi, lane), i_q = wave_scan_f64(qi, lane);
+            const uint32_t i_n = wave_scan_rows(n, lane), i_c = wave_scan_rows(ci, lane), i_s = wave_scan_rows(si, lane);
+            const double i_z = wave_scan_rows(zi, lane), i_q = wave_scan_rows(qi, lane);
             if (j <= ncs) {
                 const uint32_t e_n = c_n + (i_n - n);
                 const double e_z = c_z + (i_z - zi), e_q = c_q + (i_q - qi);
@@ -2162,27 +1977,16 @@ __global__ __launch_bounds__(1024) void k_local_sums(LocalArgs a) {
                 e.cs = local_edge_trig(e_c, e_s);
                 out[(size_t)ra * (ncs + 1u) + j] = e;
             }
-            c_n += (uint32_t)__builtin_amdgcn_readlane((int)i_n, 63);
-            c_c += (uint32_t)__builtin_amdgcn_readlane((int)i_c, 63);
-            c_s += (uint32_t)__builtin_amdgcn_readlane((int)i_s, 63);
+            c_n += lane_value(i_n, 63);
+            c_c += lane_value(i_c, 63);
+            c_s += lane_value(i_s, 63);
             c_z += lane_value(i_z, 63);
             c_q += lane_value(i_q, 63);
         }
     }
     // ---- the frame's record: extrema of the normal coordinate, and whether the frame is for this kernel at all
-    for (int off = 32; off >= 1; off >>= 1) {
-        zlo = fminf(zlo, __shfl_xor(zlo, off, 64));
-        zhi = fmaxf(zhi, __shfl_xor(zhi, off, 64));
-        flag |= (uint32_t)__shfl_xor((int)flag, off, 64);
-    }
-    if (lane == 0u) { l_zlo[wave] = zlo; l_zhi[wave] = zhi; l_flag[wave] = flag; }
-    __syncthreads();
-    if (tid == 0u) {
-        for (uint32_t w = 1; w < 16u; w++) { zlo = fminf(zlo, l_zlo[w]); zhi = fmaxf(zhi, l_zhi[w]); flag |= l_flag[w]; }
-        reinterpret_cast<uint4 *>(a.finfo)[s] = zlo <= zhi ? make_uint4(local_float_key(zlo), local_float_key(zhi), flag & 1u, 2u)
-                                                            : make_uint4(0xffffffffu, 0u, flag & 1u, 2u);
-        if (flag) { a.need[s] = 1u; a.need[a.n_slab] = 1u; }          // (k_local_build makes the frame's record again, and everything else)
-    }
+    block_finfo_record(zlo, zhi, flag, 1u, l_zlo, l_zhi, l_flag, reinterpret_cast<uint4 *>(a.finfo) + s);
+    if (tid == 0u && flag) { a.need[s] = 1u; a.need[a.n_slab] = 1u; }   // (k_local_build makes the frame's record again, and everything else)
 }
 
 // The bound of k_local_flags_rows ("a head its ring cannot change") on its own, a LANE per head, the frame's table of cell
@@ -2359,7 +2163,7 @@ __global__ __launch_bounds__(256) void k_local_flags_todo(LocalArgs a) {
     if (a.need && a.summary && blockIdx.x == 0u && threadIdx.x < 64u) {
         uint32_t c = 0;
         for (uint32_t s = threadIdx.x; s < a.n_slab; s += 64u) c += a.need[s] != 0u ? 1u : 0u;
-        c = wave_total_u32(c);
+        c = wave_sum_rows(c);
         if (threadIdx.x == 0u) {
             const uint32_t open = atomicAdd(&a.summary[0], c) + c, seen = atomicAdd(&a.summary[1], a.n_slab) + a.n_slab;
             if (a.summary_host) {
@@ -2412,25 +2216,6 @@ struct SphArgs {
 };
 
 struct SphParams { float w, mean_a, var_a, mean_b, var_b; };   // GmmParams, spherical_clustering.rs:80-97
-
-// N sums for the price (barriers) of one, every thread gets the same totals; scratch holds N x 16 doubles
-template <int N>
-__device__ __forceinline__ void block_sum_n(double (&v)[N], double *scratch) {
-    const uint32_t wave = threadIdx.x >> 6, n_waves = (blockDim.x + 63u) >> 6;
-#pragma unroll
-    for (int q = 0; q < N; q++) {
-        v[q] = wave_sum(v[q]);
-        if ((threadIdx.x & 63u) == 0) scratch[16 * q + wave] = v[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < N; q++) {
-        double r = 0.0;
-        for (uint32_t w = 0; w < n_waves; w++) r += scratch[16 * q + w];
-        v[q] = r;
-    }
-    __syncthreads();
-}
 
 // PBC3D::distance / NoPBC::distance over XYZ (pbc.rs:354-356, 164-166)
 __device__ __forceinline__ float sph_distance(const float *p, const float (&c)[3], const float (&box)[3], int pbc, int &bad) {
@@ -2570,11 +2355,7 @@ __global__ __launch_bounds__(THREADS) void k_leaflets_spherical(SphArgs a) {
             const uint32_t c0 = hist[wave][4u * lane], c1 = hist[wave][4u * lane + 1u], c2 = hist[wave][4u * lane + 2u],
                            c3 = hist[wave][4u * lane + 3u];
             const uint32_t s = (c0 + c1) + (c2 + c3);
-            uint32_t incl = s;
-            for (uint32_t off = 1; off < 64u; off <<= 1) {
-                const uint32_t t = __shfl_up(incl, off, 64);
-                if (lane >= off) incl += t;
-            }
+            const uint32_t incl = wave_scan_shfl(s, lane);
             const uint32_t excl = incl - s, k = wave ? rank[1] : rank[0];
             if (k >= excl && k < incl) {
                 uint32_t r = k - excl, b = 0u;

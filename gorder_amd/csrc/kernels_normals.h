@@ -129,14 +129,10 @@ __global__ __launch_bounds__(256) void k_dyn_cov(LocalArgs a, DynCov *__restrict
         }
     }
     // totals in lane 15 of the row (row shifts only)
-    auto row_total = [](double v) {
-        v = row_add_f64<0x111>(v); v = row_add_f64<0x112>(v); v = row_add_f64<0x114>(v);
-        return row_add_f64<0x118>(v);
-    };
-    cnt = row_add_u32<0x111>(cnt); cnt = row_add_u32<0x112>(cnt); cnt = row_add_u32<0x114>(cnt); cnt = row_add_u32<0x118>(cnt);
-    sx = row_total(sx); sy = row_total(sy); sz = row_total(sz);
-    sxx = row_total(sxx); sxy = row_total(sxy); sxz = row_total(sxz);
-    syy = row_total(syy); syz = row_total(syz); szz = row_total(szz);
+    cnt = row_sum(cnt);
+    sx = row_sum(sx); sy = row_sum(sy); sz = row_sum(sz);
+    sxx = row_sum(sxx); sxy = row_sum(sxy); sxz = row_sum(sxz);
+    syy = row_sum(syy); syz = row_sum(syz); szz = row_sum(szz);
     if (sub == 15u && mol_ok) {
         if (undefined) raise_error(a.err, GORDER_ERR_UNDEFINED_POSITION, f, kStageSystem, 0, 0, m);
         cov[(size_t)s * a.n_mol_total + m] = DynCov{undefined ? -1.0 : (double)cnt, sx, sy, sz, sxx, sxy, sxz, syy, syz, szz};

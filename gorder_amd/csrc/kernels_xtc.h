@@ -339,9 +339,7 @@ __global__ __launch_bounds__(64) void k_xtc_chunks(const uint8_t *__restrict__ b
     const uint32_t atom0 = ca.atom;
     // atoms of this chunk (a checkpoint lies within a group of the chunk's nominal start: never more than kXtcChunk + 8)
     uint32_t n_at = (live && !bad_frame && cb.atom >= ca.atom && cb.atom - ca.atom <= kXtcChunk + 16u) ? cb.atom - ca.atom : 0u;
-    uint32_t n_max = n_at;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) n_max = max(n_max, (uint32_t)__shfl_xor((int)n_max, off, 64));
+    const uint32_t n_max = wave_max_bfly(n_at);
     if (n_max == 0u) return;                     // (uniform; no workgroup barrier below this line)
 
     // Decoded atoms go through LDS: a lane writing its chunk's atom straight to memory is one 12-byte piece in each of

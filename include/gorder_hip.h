@@ -497,6 +497,25 @@ int gorder_hip_selftest_arithmetic(int device, uint64_t n, uint64_t seed, uint64
  * the HOST array `out`: to be compared with the host's libm (tests/test_parity_gpu.py does, over all of [-1, 1] and
  * [0, pi] in strides). */
 int gorder_hip_selftest_trig(int device, int fn, uint32_t first_bits, uint32_t stride, uint32_t n, float *out);
+/* Diagnostic: ONE workgroup of `block` threads (a multiple of 64, at most 1024) runs every wave and block reduction of the
+ * kernels (csrc/wave_ops.h) on one value per thread of the HOST arrays f64, f32, u32 [block] and returns what every lane
+ * holds afterwards: out_*[row * block + thread], to be compared bit for bit with the literal restatement of the two
+ * orders in tests/wave_ops_ref.py.  Rows (a "row sum" is defined in lane 15 of each 16 lanes, a "rows" total in lane 63):
+ *   out_f64: 0 row sum, 1 + rows to wave, 2 wave sum (rows), 3 wave scan (rows), 4 wave sum (butterfly), 5 block sum of x,
+ *            6 block sum of 3 x (the same call), 7 lane 47's value, 8 / 9 sums of x and 3 x by the four-quantity butterfly
+ *   out_f32: 0 row sum, 1 + rows to wave, 2 wave sum (rows), 3 / 4 wave min / max (rows), 5 / 6 min / max (butterfly),
+ *            7 / 8 block min / max, 9 row_shr:1 or own value, 10 row_bcast:31 into rows 2, 3 or zero, 11 lane 47's value,
+ *            12 / 13 min / max by the four-quantity butterfly, 14 / 15 by the three-quantity one
+ *   out_u32: 0 row sum, 1 + rows to wave, 2 wave sum (rows), 3 wave scan (rows), 4 wave scan (shuffles), 5 or
+ *            (butterfly), 6 max (butterfly), 7 wave sum (rows) as int, 8 lane 47's value
+ *   out_finfo [9]: a frame's record (key of min f32, key of max f32, or of u32, 2) with every flag kept, the same with
+ *            bit 0 only, and the flags thread 0 is left with; finfo_empty != 0: no thread has a value (min > max). */
+#define GORDER_WAVE_OPS_F64_ROWS 10
+#define GORDER_WAVE_OPS_F32_ROWS 16
+#define GORDER_WAVE_OPS_U32_ROWS 9
+#define GORDER_WAVE_OPS_FINFO_WORDS 9
+int gorder_hip_selftest_wave_ops(int device, uint32_t block, const double *f64, const float *f32, const uint32_t *u32,
+                                 int finfo_empty, double *out_f64, float *out_f32, uint32_t *out_u32, uint32_t *out_finfo);
 
 #ifdef __cplusplus
 }
