@@ -35,9 +35,11 @@ ERR_BOX_RANGE = 103
 ERR_LEAFLETS_NOT_PRIMED = 104
 ERR_OVERFLOW = 105
 ERR_TRAJECTORY_FORMAT = 106
-ERR_CLUSTERING = 107         # spherical clustering: a head-centre distance is not finite
+ERR_CLUSTERING = 107         # spherical / spectral clustering: a distance of an assignment frame is not finite
+ERR_CLUSTER_MATCH = 108      # spectral clustering: the clusters match neither leaflet of the previous assignment frame
 
 LEAFLETS_NONE, LEAFLETS_GLOBAL, LEAFLETS_LOCAL, LEAFLETS_INDIVIDUAL, LEAFLETS_MANUAL, LEAFLETS_SPHERICAL = range(6)
+LEAFLETS_CLUSTERING = 6      # spectral clustering (include/gorder_hip.h): membranes of any shape
 FLAG_TRIG_ACOS_COS = 1
 FLAG_UA_FAST_NORMALISE = 2      # united atoms: tolerance-bounded hydrogen construction (include/gorder_hip.h)
 UA_CH1_SAT, UA_CH2, UA_CH3, UA_CH1_UNSAT = 1, 2, 3, 4
@@ -158,7 +160,7 @@ class Leaflets:
     frequency: int = 1      # 0 = once; REAL frequency (input frequency * step)
     flip: bool = False
     radius: float = 0.0
-    membrane: Optional[np.ndarray] = None     # Global / Local: group "Membrane"; Spherical: group "ClusterHeads"
+    membrane: Optional[np.ndarray] = None     # Global / Local: group "Membrane"; Spherical / Clustering: group "ClusterHeads"
 
 
 @dataclass
@@ -313,7 +315,7 @@ _EXPORTS = [
     "gorder_hip_plan_tables", "gorder_hip_selftest_arithmetic", "gorder_hip_selftest_trig", "gorder_hip_selftest_wave_ops", "gorder_hip_run_trajectory",
     "gorder_hip_comm_unique_id", "gorder_hip_comm_create", "gorder_hip_comm_destroy", "gorder_hip_allreduce",
     "gorder_hip_reset", "gorder_hip_xtc_decode", "gorder_hip_release_staging", "gorder_hip_speculation_stats", "gorder_hip_local_decide_stats",
-    "gorder_hip_spherical_stats",
+    "gorder_hip_spherical_stats", "gorder_hip_clustering_stats",
 ]
 
 _lib = None
@@ -385,6 +387,7 @@ def load_library() -> C.CDLL:
     lib.gorder_hip_speculation_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.gorder_hip_local_decide_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.gorder_hip_spherical_stats.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.gorder_hip_clustering_stats.argtypes = [vp, C.POINTER(C.c_float)]
     lib.gorder_hip_plan_tables.argtypes = [C.POINTER(CTables), C.POINTER(CPlan), C.POINTER(i32)]
     lib.gorder_hip_selftest_arithmetic.argtypes = [i32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.gorder_hip_selftest_trig.argtypes = [i32, i32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -767,6 +770,16 @@ class HipEngine:
         v = np.array(out[:], dtype=np.float32)
         return {"centre": v[0:3].copy(), "weight_a": v[3], "mean_a": v[4], "var_a": v[5], "mean_b": v[6], "var_b": v[7],
                 "avg_log_likelihood": v[8], "iterations": int(v[9]), "n_outer": int(v[10])}
+
+    def clustering_stats(self) -> dict:
+        """Spectral clustering (gorder_hip_clustering_stats), most recent assignment frame: eigenvalues 2-4 of the normalised
+        Laplacian, Lanczos steps, 2-means rounds, populations of the two clusters before and after orientation, the overlaps
+        with the previous assignment frame's leaflets (NaN for frame 0)."""
+        out = (C.c_float * 12)()
+        self._check(self.lib.gorder_hip_clustering_stats(self._h, out))
+        v = np.array(out[:], dtype=np.float32)
+        return {"eigenvalues": v[0:3].copy(), "steps": int(v[3]), "rounds": int(v[4]), "n_cluster": (int(v[5]), int(v[6])),
+                "n_upper": int(v[7]), "n_lower": int(v[8]), "o_up": v[9], "o_lo": v[10]}
 
     def plan(self) -> dict:
         p = CPlan()

@@ -12,6 +12,7 @@
 //   common_identify_leaflet            leaflets.rs:711-732              (same kernel)
 //   IndividualClassification           leaflets.rs:777-801           -> k_leaflets_individual
 //   SystemSphericalClusterClassification spherical_clustering.rs:42-277, leaflets.rs:1296-1366 -> k_leaflets_spherical
+//   SystemClusterClassification (precise route) clustering.rs:478-800 -> k_cluster_{degrees,lanczos,embed,orient}
 //   LocalClassification + local centres leaflets.rs:661-675, pbc.rs:273-318 -> k_local_{build,rowprefix,decide,flags_rows,flags_todo} (k_local_{bin,scan,scatter,flags}: very large membranes, no box)
 //   should_assign / get_assigned       leaflets.rs:435-441, 1437-1472   (host: assignment-row table)
 //   SystemTopology::add / reduce       topology/mod.rs:236-272          (integer sums: order-free)
@@ -47,6 +48,7 @@ using gorder::Tile;
 #include "kernels_bonds.h"
 #include "kernels_extras.h"
 #include "kernels_leaflets.h"
+#include "kernels_cluster.h"
 #include "kernels_normals.h"
 #include "kernels_xtc.h"
 
@@ -144,6 +146,16 @@ struct gorder_hip_handle {
     // the statistics of the most recent assignment frame (gorder_hip_spherical_stats)
     float *d_sph_spill = nullptr, *d_sph_stats = nullptr;
     uint32_t sph_spill = 0, sph_slab = 1u << 20, sph_threads = 1024;
+    // spectral clustering: scratch for cl_slab assignment frames a launch (one allocation, carved in ClArgs), the group slot
+    // of every molecule's head, the oriented labels of the previous assignment frame (the carry) and the last frame's statistics
+    void *d_cl_scratch = nullptr;
+    uint32_t *d_cl_head_slot = nullptr;
+    uint8_t *d_cl_carry = nullptr, *d_cl_is0 = nullptr;
+    float *d_cl_stats = nullptr;
+    uint32_t cl_slab = 1, cl_m_max = 0;
+    bool cl_stored_w = false;              // GORDER_HIP_CLUSTER_STORED_W: S v reads W stored once a frame instead of recomputing it
+    bool cl_have_carry = false;
+    std::vector<uint8_t> cl_is0;           // per assignment frame of the call in flight: frame_index == 0
     // Local leaflets scratch (sized for local_slab assignment frames)
     uint32_t *d_lcell_of = nullptr, *d_lcell_count = nullptr, *d_lcell_fill = nullptr;
     float *d_ltrig = nullptr;
@@ -295,7 +307,7 @@ int check_device_error(gorder_hip_handle *h) {
     const uint32_t sample = (uint32_t)(key >> 23) & 1u, slot = (uint32_t)(key >> 24) & 0x3fffu;
     const uint32_t stage = (uint32_t)(key >> 38) & 3u, frame = (uint32_t)(key >> 40) & 0x7fffffu;
     const int status = code == 8u ? (int)GORDER_ERR_BOX_RANGE : (code == 9u ? (int)GORDER_ERR_TRAJECTORY_FORMAT :
-                       (code == 10u ? (int)GORDER_ERR_CLUSTERING : (int)code));
+                       (code == 10u ? (int)GORDER_ERR_CLUSTERING : (code == 11u ? (int)GORDER_ERR_CLUSTER_MATCH : (int)code)));
     h->err_frame = frame;
     char where[96];
     snprintf(where, sizeof(where), "frame %u of a batch", frame);
@@ -316,7 +328,7 @@ int check_device_error(gorder_hip_handle *h) {
         if (mol < h->host_heads.size()) h->err_index = h->host_heads[mol];                // leaflets.rs:661-675: the head's index
     } else if (status == GORDER_ERR_DYNAMIC_NORMAL) {
         h->err_index = detail;                                                             // NotEnoughPoints(n)
-    } else if (status == GORDER_ERR_CLUSTERING) {
+    } else if (status == GORDER_ERR_CLUSTERING || status == GORDER_ERR_CLUSTER_MATCH) {
         h->err_index = h->err_frame;                                                       // the frame whose distances are not finite
     }
     char buf[200];
@@ -809,7 +821,8 @@ const char *gorder_hip_strerror(int status) {
         case GORDER_ERR_LEAFLETS_NOT_PRIMED: return "leaflet assignment missing for the first frame";
         case GORDER_ERR_OVERFLOW: return "order accumulator overflowed";
         case GORDER_ERR_TRAJECTORY_FORMAT: return "corrupt or truncated trajectory frame";
-        case GORDER_ERR_CLUSTERING: return "spherical clustering: a head-centre distance is not finite";
+        case GORDER_ERR_CLUSTERING: return "clustering: a distance between head atoms or to their centre is not finite";
+        case GORDER_ERR_CLUSTER_MATCH: return "clustering: the clusters match neither leaflet of the previous assignment frame (80 % overlap)";
         default: return "unknown status";
     }
 }
@@ -1006,6 +1019,8 @@ int gorder_hip_plan_tables(const gorder_tables_t *tables, gorder_hip_plan_t *out
     return GORDER_OK;
 }
 
+static size_t cl_frame_bytes(uint32_t n, uint32_t m_max);
+
 int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
     if (!t || !out) return GORDER_ERR_INVALID_ARGUMENT;
     *out = nullptr;
@@ -1194,8 +1209,8 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
 
     const gorder_leaflets_t &lf = t->leaflets;
     if (lf.method != GORDER_LEAFLETS_NONE) {
-        if (lf.method > GORDER_LEAFLETS_SPHERICAL) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.method");
-        if (lf.method != GORDER_LEAFLETS_SPHERICAL && lf.normal_dim > 2) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.normal_dim");
+        if (lf.method > GORDER_LEAFLETS_CLUSTERING) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.method");
+        if (lf.method != GORDER_LEAFLETS_SPHERICAL && lf.method != GORDER_LEAFLETS_CLUSTERING && lf.normal_dim > 2) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.normal_dim");
         std::vector<uint32_t> heads, mb(1, 0), ma;
         for (uint32_t m = 0; m < t->n_molecule_types; m++) {
             const gorder_moltype_t &mt = t->molecule_types[m];
@@ -1264,6 +1279,40 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
             }
             HIP_TRY(h, hipMalloc((void **)&h->d_sph_stats, 12 * sizeof(float)));
             HIP_TRY(h, hipMemset(h->d_sph_stats, 0, 12 * sizeof(float)));
+        }
+        if (lf.method == GORDER_LEAFLETS_CLUSTERING) {
+            // leaflets.membrane is the group "ClusterHeads" (leaflets.rs:96-105: at least two atoms); the dense route holds
+            // n x (steps + 1) basis vectors a frame, hence the bound
+            if (!lf.membrane || lf.n_membrane < kClMinGroup)
+                return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.n_membrane: clustering needs at least two group atoms");
+            if (lf.n_membrane > kClMaxGroup)
+                return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.n_membrane: clustering takes at most 8192 group atoms");
+            std::vector<uint32_t> grp(lf.membrane, lf.membrane + lf.n_membrane);
+            std::vector<int32_t> slot_of(t->n_atoms, -1);
+            for (uint32_t i = 0; i < lf.n_membrane; i++) {
+                if (grp[i] >= t->n_atoms) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.membrane: index out of range");
+                if (i && grp[i] <= grp[i - 1]) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.membrane: clustering needs ascending, distinct atoms");
+                slot_of[grp[i]] = (int32_t)i;
+            }
+            std::vector<uint32_t> head_slot;
+            for (uint32_t hd : heads) {
+                if (slot_of[hd] < 0)
+                    return fail(h, GORDER_ERR_INVALID_ARGUMENT, "molecule_types[].heads: a head is not a member of leaflets.membrane");
+                head_slot.push_back((uint32_t)slot_of[hd]);
+            }
+            if ((st = upload(h, &h->d_membrane, grp)) != GORDER_OK) return st;
+            if ((st = upload(h, &h->d_cl_head_slot, head_slot)) != GORDER_OK) return st;
+            const uint32_t n = lf.n_membrane;
+            h->cl_m_max = std::min<uint32_t>(n - 1u, (uint32_t)kClMaxSteps);
+            // at most 512 MiB of scratch whatever the batch, at most 1024 frames a launch
+            h->cl_stored_w = env_flag("GORDER_HIP_CLUSTER_STORED_W");
+            const size_t per_frame = cl_frame_bytes(n, h->cl_m_max) + (h->cl_stored_w ? (size_t)n * n * 4 : 0);
+            h->cl_slab = (uint32_t)std::min<size_t>(std::max<size_t>(((size_t)512 << 20) / per_frame, 1), 1024);
+            HIP_TRY(h, hipMalloc(&h->d_cl_scratch, (size_t)h->cl_slab * per_frame));
+            HIP_TRY(h, hipMalloc((void **)&h->d_cl_carry, n));
+            HIP_TRY(h, hipMalloc((void **)&h->d_cl_is0, h->cl_slab));
+            HIP_TRY(h, hipMalloc((void **)&h->d_cl_stats, 12 * sizeof(float)));
+            HIP_TRY(h, hipMemset(h->d_cl_stats, 0, 12 * sizeof(float)));
         }
         // one read for global leaflets + order parameters: the tables of k_bonds_tiled<..., MOM> and k_spec_fixup
         if (lf.method == GORDER_LEAFLETS_GLOBAL && p.spec_ok && !env_flag("GORDER_HIP_NO_SPECULATE")) {
@@ -1358,6 +1407,8 @@ void gorder_hip_destroy(gorder_hip_handle *h) {
     (void)hipFree(h->d_heads); (void)hipFree(h->d_membrane); (void)hipFree(h->d_methyl_begin);
     (void)hipFree(h->d_methyl_atoms); (void)hipFree(h->d_aflags); (void)hipFree(h->d_adist);
     (void)hipFree(h->d_sph_spill); (void)hipFree(h->d_sph_stats);
+    (void)hipFree(h->d_cl_scratch); (void)hipFree(h->d_cl_head_slot); (void)hipFree(h->d_cl_carry); (void)hipFree(h->d_cl_is0);
+    (void)hipFree(h->d_cl_stats);
     (void)hipFree(h->d_arow); (void)hipFree(h->d_aframes);
     (void)hipFree(h->d_lcell_of); (void)hipFree(h->d_lcell_count); (void)hipFree(h->d_lcell_fill);
     (void)hipFree(h->d_ltrig);
@@ -1439,6 +1490,57 @@ static void spec_poll(gorder_hip_handle *h, bool wait) {
 }
 
 // ---- leaflet assignment rows for a batch (host part of leaflets.rs:435-441, 1437-1472) --------
+// spectral clustering: bytes of scratch one assignment frame takes (every array a multiple of 16 bytes), and the launch
+static size_t cl_round(size_t b) { return (b + 15u) & ~(size_t)15u; }
+static size_t cl_frame_bytes(uint32_t n, uint32_t m_max) {
+    return cl_round(3 * (size_t)n * 4) + 3 * cl_round((size_t)n * 4) + cl_round((size_t)(m_max + 1u) * n * 4) +
+           cl_round(kClSol * 8) + cl_round(n) + cl_round(kClMeta * 4) + 16;
+}
+static int run_clustering(gorder_hip_handle *h, const float *d_xyz, const float *d_box, size_t n_assign, uint32_t row0) {
+    const gorder_leaflets_t &lf = h->tables.leaflets;
+    const uint32_t n = lf.n_membrane, slab = h->cl_slab;
+    ClArgs ca{};
+    ca.xyz = d_xyz; ca.box9 = d_box; ca.n_atoms = h->plan.n_atoms; ca.group = h->d_membrane; ca.n = n;
+    ca.pbc = h->tables.handle_pbc ? 1 : 0; ca.m_max = h->cl_m_max; ca.err = h->d_err;
+    char *base = (char *)h->d_cl_scratch;
+    auto carve = [&](size_t per_frame) { char *at = base; base += per_frame * slab; return at; };
+    ca.sol = (double *)carve(cl_round(kClSol * 8));
+    ca.pos = (float *)carve(cl_round(3 * (size_t)n * 4));
+    ca.s = (float *)carve(cl_round((size_t)n * 4));
+    ca.q = (float *)carve(cl_round((size_t)n * 4));
+    ca.emb = (float *)carve(cl_round((size_t)n * 4));
+    ca.V = (float *)carve(cl_round((size_t)(h->cl_m_max + 1u) * n * 4));
+    ca.meta = (float *)carve(cl_round(kClMeta * 4));
+    ca.fail = (uint32_t *)carve(16);
+    ca.lab = (uint8_t *)carve(cl_round(n));
+    ca.W = h->cl_stored_w ? (float *)carve((size_t)n * n * 4) : nullptr;
+    // (the arrays are indexed [slot][..] with their exact sizes: the rounding only pads the ends)
+    ClOrientArgs oa{};
+    oa.n = n; oa.lab = ca.lab; oa.emb = ca.emb; oa.meta = ca.meta; oa.fail = ca.fail; oa.carry = h->d_cl_carry;
+    oa.aflags = h->d_aflags; oa.n_mol_total = h->plan.n_mol_total; oa.head_slot = h->d_cl_head_slot;
+    oa.flip = lf.flip ? 1 : 0; oa.err = h->d_err; oa.is_frame0 = h->d_cl_is0;
+    for (size_t done = 0; done < n_assign; done += slab) {
+        const uint32_t ns = (uint32_t)std::min<size_t>(n_assign - done, slab);
+        const bool last = done + ns == n_assign;
+        ca.aframes = h->d_aframes + done; ca.n_assign = ns;
+        oa.aframes = ca.aframes; oa.n_assign = ns; oa.row0 = row0 + (uint32_t)done;
+        oa.adist = last ? h->d_adist : nullptr;
+        oa.stats = last ? h->d_cl_stats : nullptr;
+        HIP_TRY(h, hipMemsetAsync(ca.fail, 0, (size_t)ns * sizeof(uint32_t), h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->d_cl_is0, h->cl_is0.data() + done, ns, hipMemcpyHostToDevice, h->stream));
+        TIMING_MARK(h, "k_cluster_degrees");
+        hipLaunchKernelGGL(k_cluster_degrees, dim3((n + 255u) / 256u, ns), dim3(256), 0, h->stream, ca);
+        TIMING_MARK(h, "k_cluster_lanczos");
+        hipLaunchKernelGGL(k_cluster_lanczos, dim3(ns), dim3(1024), 0, h->stream, ca);
+        TIMING_MARK(h, "k_cluster_embed");
+        hipLaunchKernelGGL(k_cluster_embed, dim3(ns), dim3(1024), 0, h->stream, ca);
+        TIMING_MARK(h, "k_cluster_orient");
+        hipLaunchKernelGGL(k_cluster_orient, dim3(1), dim3(1024), 0, h->stream, oa);
+    }
+    h->cl_have_carry = true;
+    return GORDER_OK;
+}
+
 static int run_leaflets(gorder_hip_handle *h, const float *d_xyz, const float *d_box,
                         const std::vector<uint32_t> &aframes, uint32_t row0, const uint8_t *skip = nullptr) {
     if (aframes.empty()) return GORDER_OK;
@@ -1509,6 +1611,8 @@ static int run_leaflets(gorder_hip_handle *h, const float *d_xyz, const float *d
             if (h->sph_threads == 256u) hipLaunchKernelGGL(k_leaflets_spherical<256>, dim3(ns), dim3(256), 0, h->stream, sa);
             else hipLaunchKernelGGL(k_leaflets_spherical<1024>, dim3(ns), dim3(1024), 0, h->stream, sa);
         }
+    } else if (lf.method == GORDER_LEAFLETS_CLUSTERING) {
+        if ((st = run_clustering(h, d_xyz, d_box, aframes.size(), row0)) != GORDER_OK) return st;
     } else if (lf.method == GORDER_LEAFLETS_LOCAL) {
         const size_t ncell = (size_t)kLocalMaxCells1D * kLocalMaxCells1D;
         LocalArgs lo{};
@@ -1637,6 +1741,13 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
         uint64_t last_assign_frame = h->assignment_frame;
         for (uint32_t f = 0; f < n_frames; f++) {
             if (lf.method != GORDER_LEAFLETS_MANUAL && should_assign(lf.frequency, frame_index[f])) {
+                if (lf.method == GORDER_LEAFLETS_CLUSTERING) {
+                    // a later assignment frame is matched against the clusters the handle holds
+                    if (aframes.empty()) h->cl_is0.clear();
+                    if (aframes.empty() && frame_index[f] != 0 && !h->cl_have_carry)
+                        return fail(h, GORDER_ERR_LEAFLETS_NOT_PRIMED, "clustering: no clusters of an earlier assignment frame to match against");
+                    h->cl_is0.push_back(frame_index[f] == 0 ? 1 : 0);
+                }
                 aframes.push_back(f);
                 cur = (uint32_t)aframes.size();
                 have = true;
@@ -1853,6 +1964,11 @@ int gorder_hip_prime_leaflets(gorder_hip_handle *h, const float *d_xyz, const fl
         h->aflags_rows = 2;
     }
     std::vector<uint32_t> aframes(1, 0);
+    if (lf.method == GORDER_LEAFLETS_CLUSTERING) {
+        if (frame_index != 0 && !h->cl_have_carry)
+            return fail(h, GORDER_ERR_LEAFLETS_NOT_PRIMED, "clustering: prime frame 0 before a later assignment frame");
+        h->cl_is0.assign(1, frame_index == 0 ? 1 : 0);
+    }
     const int st = run_leaflets(h, d_xyz, d_box, aframes, 0);
     (void)timing_mark(h, nullptr);      // (the priming frame's kernels are a chain of their own: nothing stays open until the next submit)
     if (st != GORDER_OK) return st;
@@ -1998,6 +2114,15 @@ int gorder_hip_spherical_stats(gorder_hip_handle *h, float out[12]) {
     return GORDER_OK;
 }
 
+int gorder_hip_clustering_stats(gorder_hip_handle *h, float out[12]) {
+    if (!h || !out || h->tables.leaflets.method != GORDER_LEAFLETS_CLUSTERING || !h->d_cl_stats) return GORDER_ERR_INVALID_ARGUMENT;
+    if (!h->have_assignment) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_clustering_stats: no assignment frame yet");
+    const int st = gorder_hip_synchronize(h);
+    if (st != GORDER_OK) return st;
+    HIP_TRY(h, hipMemcpy(out, h->d_cl_stats, 12 * sizeof(float), hipMemcpyDeviceToHost));
+    return GORDER_OK;
+}
+
 int gorder_hip_accumulators_device(gorder_hip_handle *h, void **d_ptr, uint64_t *n_u64) {
     if (!h || !d_ptr || !n_u64) return GORDER_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
@@ -2063,6 +2188,7 @@ int gorder_hip_reset(gorder_hip_handle *h) {
     h->batch_log.clear();
     h->n_frames = 0;
     h->have_assignment = false;
+    h->cl_have_carry = false;
     h->assignment_frame = 0;
     h->manual_frames = 0;
     h->err_index = 0;

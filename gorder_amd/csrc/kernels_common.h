@@ -51,7 +51,7 @@ struct FrameArgs {
 //   [23]    0 = leaflet assignment of the type, 1 = order sample
 //   [22:6]  global molecule id (clamped to 2^17 - 1)   [5:4] detail (which atom of the sample / cloud size)
 //   [3:0]   code: gorder_status_t 1..7, 8 = GORDER_ERR_BOX_RANGE, 9 = GORDER_ERR_TRAJECTORY_FORMAT (k_xtc_scan),
-//           10 = GORDER_ERR_CLUSTERING (k_leaflets_spherical)
+//           10 = GORDER_ERR_CLUSTERING (k_leaflets_spherical, k_cluster_degrees), 11 = GORDER_ERR_CLUSTER_MATCH (k_cluster_orient)
 // The payload of gorder_hip_last_error_index (an atom index) is resolved on the host from (slot, molecule, detail).
 constexpr unsigned long long kErrNone = ~0ull;
 enum ErrStage : uint32_t { kStageBox = 0, kStageSystem = 1, kStageTypes = 2, kStageEnd = 3 };
@@ -64,7 +64,7 @@ __device__ __forceinline__ void raise_error(uint32_t *err, uint32_t code, uint32
         ((unsigned long long)min(slot, 0x3fffu) << 24) | ((unsigned long long)(sample & 1u) << 23) |
         ((unsigned long long)min(mol, 0x1ffffu) << 6) | ((unsigned long long)(detail & 3u) << 4) |
         (unsigned long long)(code == GORDER_ERR_BOX_RANGE ? 8u : (code == GORDER_ERR_TRAJECTORY_FORMAT ? 9u :
-                             (code == GORDER_ERR_CLUSTERING ? 10u : (code & 15u))));
+                             (code == GORDER_ERR_CLUSTERING ? 10u : (code == GORDER_ERR_CLUSTER_MATCH ? 11u : (code & 15u)))));
     atomicMin(reinterpret_cast<unsigned long long *>(err), key);
 }
 // the library's own range error (a coordinate so far outside the box that the reference would spin): end of frame

@@ -18,7 +18,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .abi import (LEAFLETS_GLOBAL, LEAFLETS_INDIVIDUAL, LEAFLETS_LOCAL, LEAFLETS_NONE, LEAFLETS_SPHERICAL, Leaflets, MolType,
+from .abi import (LEAFLETS_CLUSTERING, LEAFLETS_GLOBAL, LEAFLETS_INDIVIDUAL, LEAFLETS_LOCAL, LEAFLETS_NONE, LEAFLETS_SPHERICAL, Leaflets, MolType,
                   OrderMap, Results, Tables)
 
 
@@ -208,7 +208,7 @@ def build_tables(structure: Structure, analysis: str, sel1: np.ndarray, sel2: Op
     "Master" group, common.rs:92-103); default = union of every selection involved.
     leaflets: {"method": ..., "membrane": mask, "heads": mask, "methyls": mask, "frequency": n, "flip": bool,
                "radius": r}.  LEAFLETS_SPHERICAL (spherical_clustering, for vesicles) takes {"method", "heads", "frequency",
-               "flip"}: the group "ClusterHeads" is `heads` restricted to the master atoms — heads of molecules that are not
+               "flip"}, and so does LEAFLETS_CLUSTERING (spectral clustering, membranes of any shape): the group "ClusterHeads" is `heads` restricted to the master atoms — heads of molecules that are not
                analysed stay in it —, and every analysed molecule has exactly one atom of it.
     Returns (Tables, [MolLabels], master index array)."""
     same = analysis == "cg"
@@ -239,7 +239,7 @@ def build_tables(structure: Structure, analysis: str, sel1: np.ndarray, sel2: Op
                 assert i >= 0 and j >= 0, "order atoms must be part of the master group"
                 bonds[b, k] = (min(i, j), max(i, j))
         heads = methyls = None
-        if lf.get("method", LEAFLETS_NONE) in (LEAFLETS_GLOBAL, LEAFLETS_LOCAL, LEAFLETS_INDIVIDUAL, LEAFLETS_SPHERICAL):
+        if lf.get("method", LEAFLETS_NONE) in (LEAFLETS_GLOBAL, LEAFLETS_LOCAL, LEAFLETS_INDIVIDUAL, LEAFLETS_SPHERICAL, LEAFLETS_CLUSTERING):
             heads = np.zeros(n_mol, dtype=np.uint32)
             for k, atoms in enumerate(mols):
                 hs = [a for a in atoms if lf["heads"][a]]
@@ -270,7 +270,7 @@ def build_tables(structure: Structure, analysis: str, sel1: np.ndarray, sel2: Op
         mem = None
         if lf["method"] in (LEAFLETS_GLOBAL, LEAFLETS_LOCAL):
             mem = remap[np.flatnonzero(lf["membrane"])].astype(np.uint32)
-        elif lf["method"] == LEAFLETS_SPHERICAL:
+        elif lf["method"] in (LEAFLETS_SPHERICAL, LEAFLETS_CLUSTERING):
             mem = _cluster_heads(lf, master, remap)
         leaf = Leaflets(method=lf["method"], normal_dim=lf.get("normal_dim", 2), frequency=lf.get("frequency", 1),
                         flip=lf.get("flip", False), radius=lf.get("radius", 0.0), membrane=mem)
@@ -283,9 +283,9 @@ def build_tables(structure: Structure, analysis: str, sel1: np.ndarray, sel2: Op
 
 
 def _cluster_heads(lf, master, remap):
-    """Group "ClusterHeads" of spherical clustering: every master atom the heads query selects, in ascending order."""
+    """Group "ClusterHeads" of spherical and spectral clustering: every master atom the heads query selects, in ascending order."""
     mem = remap[np.flatnonzero(lf["heads"] & np.asarray(master, dtype=bool))]
-    assert (mem >= 0).all() and len(mem) >= 2, "spherical clustering needs at least two head atoms (NotEnoughAtomsToCluster)"
+    assert (mem >= 0).all() and len(mem) >= 2, "clustering needs at least two head atoms (NotEnoughAtomsToCluster)"
     return mem.astype(np.uint32)
 
 
@@ -398,8 +398,8 @@ def build_tables_ua(structure: Structure, saturated: np.ndarray, unsaturated: np
         if not ua_atoms:
             continue
         heads = methyls = None
-        if lf.get("method", LEAFLETS_NONE) in (LEAFLETS_GLOBAL, LEAFLETS_LOCAL, LEAFLETS_INDIVIDUAL, LEAFLETS_SPHERICAL):
-            if lf["method"] == LEAFLETS_SPHERICAL:
+        if lf.get("method", LEAFLETS_NONE) in (LEAFLETS_GLOBAL, LEAFLETS_LOCAL, LEAFLETS_INDIVIDUAL, LEAFLETS_SPHERICAL, LEAFLETS_CLUSTERING):
+            if lf["method"] in (LEAFLETS_SPHERICAL, LEAFLETS_CLUSTERING):
                 for atoms in mols:
                     n_h = sum(1 for a in atoms if lf["heads"][a])
                     assert n_h == 1, f"molecule type {t['name']}: {n_h} head identifiers (need exactly 1)"
@@ -415,7 +415,7 @@ def build_tables_ua(structure: Structure, saturated: np.ndarray, unsaturated: np
         mem = None
         if lf["method"] in (LEAFLETS_GLOBAL, LEAFLETS_LOCAL):
             mem = remap[np.flatnonzero(lf["membrane"])].astype(np.uint32)
-        elif lf["method"] == LEAFLETS_SPHERICAL:
+        elif lf["method"] in (LEAFLETS_SPHERICAL, LEAFLETS_CLUSTERING):
             mem = _cluster_heads(lf, master, remap)
         leaf = Leaflets(method=lf["method"], normal_dim=lf.get("normal_dim", 2), frequency=lf.get("frequency", 1),
                         flip=lf.get("flip", False), radius=lf.get("radius", 0.0), membrane=mem)

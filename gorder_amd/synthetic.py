@@ -293,6 +293,58 @@ def cg_vesicle(n_lipids: int = 3000, inner_radius: float = 6.0, outer_radius: fl
     return system, sides
 
 
+# ---- buckled Martini bilayer: the lipids of cg_membrane on a sinusoid -----------------------------------
+def cg_buckled(n_lipids: int = 3000, box=(44.0, 22.0, 18.0), amplitude: float = 3.0, seed: int = 13,
+               leaflets: Optional[int] = None, frequency: int = 1, flip: bool = False, handle_pbc: bool = True,
+               ordermap: Optional[OrderMap] = None, timewise: bool = False, normal=(0.0, 0.0, 1.0),
+               half_thickness: float = 2.0):
+    """Periodic CG bilayer whose midplane is z0 + amplitude * sin(2 pi x / Lx), z0 = Lz / 2: with the amplitude above the
+    half thickness (head to midplane, 2 nm) no plane separates the leaflets, which is what spectral clustering is for.
+    The lipids (12 beads, 11 bonds: the tables of cg_membrane) stand along z on two grids, one per leaflet, and are
+    shuffled, so the atom index says nothing about the side.  leaflets defaults to LEAFLETS_CLUSTERING (the group is every
+    PO4 bead; LEAFLETS_GLOBAL / LEAFLETS_LOCAL get the whole system as their membrane).
+    -> (System, sides [n_lipids] uint8: 0 = upper, the leaflet above the midplane, 1 = lower)."""
+    from .abi import LEAFLETS_CLUSTERING, LEAFLETS_SPHERICAL
+    if leaflets is None:
+        leaflets = LEAFLETS_CLUSTERING
+    rng = np.random.default_rng(seed)
+    box = np.asarray(box, dtype=np.float32)
+    per_leaflet = (n_lipids + 1) // 2
+    nx = max(1, int(round(np.sqrt(per_leaflet * float(box[0]) / float(box[1])))))
+    ny = (per_leaflet + nx - 1) // nx
+    sides = (np.arange(n_lipids) % 2).astype(np.uint8)
+    g = np.arange(n_lipids) // 2
+    order = rng.permutation(n_lipids)
+    sides, g = sides[order], g[order]
+    if sides[0] == 1:          # lipid 0 is upper: with equal populations its cluster is the upper one (ab-initio tie rule)
+        sides = (1 - sides).astype(np.uint8)
+    ox = (g % nx + 0.5) * box[0] / nx + rng.normal(0, 0.08, n_lipids)
+    oy = (g // nx + 0.5) * box[1] / ny + rng.normal(0, 0.08, n_lipids)
+    mid = box[2] / 2 + amplitude * np.sin(2 * np.pi * ox / box[0])
+    sgn = np.where(sides == 0, 1.0, -1.0)
+    base = np.zeros((n_lipids, 12, 3), dtype=np.float64)
+    for b in range(12):
+        base[:, b, 0] = ox + _CG_SIDE[b] + rng.normal(0, 0.05, n_lipids)
+        base[:, b, 1] = oy + rng.normal(0, 0.05, n_lipids)
+        base[:, b, 2] = mid + sgn * (half_thickness - _CG_DEPTH[b] * 0.47 * 0.75) + rng.normal(0, 0.05, n_lipids)
+    n_atoms = n_lipids * 12
+    base = np.mod(base.reshape(n_atoms, 3), box).astype(np.float32)
+    ids = np.arange(n_lipids)
+    bonds = (_CG_BONDS[:, None, :] + (ids * 12)[None, :, None]).astype(np.uint32)
+    heads = (ids * 12 + 1).astype(np.uint32)
+    mt = MolType(n_molecules=n_lipids, bonds=bonds, heads=heads if leaflets else None, name="LIP0")
+    if leaflets in (LEAFLETS_CLUSTERING, LEAFLETS_SPHERICAL):
+        mem = heads.copy()
+    elif leaflets in (LEAFLETS_GLOBAL, LEAFLETS_LOCAL):
+        mem = np.arange(n_atoms, dtype=np.uint32)
+    else:
+        mem = None
+    lf = Leaflets(method=leaflets, normal_dim=2, frequency=frequency, flip=flip, radius=2.5, membrane=mem)
+    tables = Tables(n_atoms=n_atoms, molecule_types=[mt], handle_pbc=handle_pbc, normal=normal, leaflets=lf,
+                    ordermap=ordermap or OrderMap(), timewise=timewise)
+    return System(f"buckled{n_lipids}", tables, base, box, jitter=0.03), sides
+
+
 class VesicleSystem(System):
     """A System that also keeps its base frame before wrapping."""
     unwrapped: Optional[np.ndarray] = None

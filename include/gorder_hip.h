@@ -66,9 +66,13 @@ typedef enum {
     GORDER_ERR_TRAJECTORY_FORMAT = 106,/* a corrupt or truncated trajectory frame, met by gorder_hip_xtc_decode on the device or
                                          by the host reader inside gorder_hip_run_trajectory (the reference: a read error
                                          of the trajectory iterator, common.rs:248) */
-    GORDER_ERR_CLUSTERING = 107       /* GORDER_LEAFLETS_SPHERICAL: a head-centre distance of an assignment frame is not finite
+    GORDER_ERR_CLUSTERING = 107,      /* GORDER_LEAFLETS_SPHERICAL: a head-centre distance of an assignment frame is not finite
                                          (the reference panics in the sort of spherical_clustering.rs:120);
-                                         gorder_hip_last_error_index = that frame */
+                                         GORDER_LEAFLETS_CLUSTERING: a coordinate of a group atom or a distance between two
+                                         of them is not finite; gorder_hip_last_error_index = that frame */
+    GORDER_ERR_CLUSTER_MATCH = 108    /* GORDER_LEAFLETS_CLUSTERING: the clusters of an assignment frame overlap neither leaflet
+                                         of the previous assignment frame by 80 % (ClusterError::CouldNotMatchLeaflets(80),
+                                         clustering.rs:770-785); gorder_hip_last_error_index = that frame */
 } gorder_status_t;
 
 /* ---- leaflets -------------------------------------------------------------------------------- */
@@ -79,7 +83,7 @@ typedef enum {
     GORDER_LEAFLETS_INDIVIDUAL = 3,  /* leaflets.rs:777-801 */
     GORDER_LEAFLETS_MANUAL = 4,      /* host supplies flags per assignment frame (leaflets.rs:820-860);
                                         Leaflet encoding Upper=0, Lower=1 (lib.rs:416-422) */
-    GORDER_LEAFLETS_SPHERICAL = 5    /* LeafletClassification::spherical_clustering (spherical_clustering.rs:42-277, leaflets.rs:
+    GORDER_LEAFLETS_SPHERICAL = 5,   /* LeafletClassification::spherical_clustering (spherical_clustering.rs:42-277, leaflets.rs:
                                         1296-1366), for vesicles: per assignment frame the centre of geometry of the group
                                         "ClusterHeads", every group atom's distance to it, a two-component 1-D Gaussian mixture
                                         fitted to the distances by EM; the component farther out is the upper leaflet.
@@ -87,6 +91,24 @@ typedef enum {
                                         the order matters only for reproducibility; at least 2, leaflets.rs:106-115), each
                                         molecule's `heads[k]` is its own atom of that group; normal_dim and radius are unused,
                                         frequency and flip as for the other methods */
+    GORDER_LEAFLETS_CLUSTERING = 6   /* LeafletClassification::clustering (clustering.rs:478-800), spectral clustering for membranes
+                                        of any shape (buckled, tubes, wrapped around the box).  Per assignment frame, over the n
+                                        atoms of "ClusterHeads" in ascending order: W_ij = expf(-d_ij^2) (sigma = 1, 3-D minimum
+                                        image with handle_pbc, no cut-off), deg = W 1, L = I - D^-1/2 W D^-1/2; the eigenvectors
+                                        of L's 2nd and 3rd smallest eigenvalues, rows normalised; 2-means from rows 0 and 1
+                                        (100 rounds at most, ties to cluster 0); frame 0: the more populated cluster is upper
+                                        (tie: the one with the lowest atom), later frames: the cluster is what 80 % of it was in
+                                        the previous assignment frame, else GORDER_ERR_CLUSTER_MATCH.
+                                        "Skip the first" is exact here: L's eigenvector of eigenvalue 0 is D^1/2 1 in closed
+                                        form, the device deflates that vector and takes the next two (the reference takes
+                                        columns 1 and 2 of a full decomposition, an arbitrary basis where the cross-leaflet
+                                        weights underflow and eigenvalue 0 is double).  ONE definition runs for every frame:
+                                        the reference's sloppy route (cut-off, sigma 0.5, random Lanczos start, retries), its
+                                        switching rules and its thread-shared reference clusters are CPU cost heuristics whose
+                                        result is "the precise result, when they succeed", and are not reproduced.
+                                        `membrane` / `n_membrane` carry the group, ascending and distinct, 2 <= n_membrane <=
+                                        8192 (dense route: the scratch holds n x 301 floats a frame, 512 MiB at most);
+                                        each molecule's heads[k] is its own atom of the group; normal_dim and radius unused */
 } gorder_leaflet_method_t;
 
 typedef struct {
@@ -369,6 +391,17 @@ int gorder_hip_leaflet_distances(gorder_hip_handle *h, float *distances);
  * log-likelihood; out[9] EM iterations run (E-steps, at most 50); out[10] group atoms labelled outer (upper, before `flip`);
  * out[11] reserved, 0.  GORDER_ERR_INVALID_ARGUMENT for other methods or before any assignment.  Waits for the stream. */
 int gorder_hip_spherical_stats(gorder_hip_handle *h, float out[12]);
+/* GORDER_LEAFLETS_CLUSTERING, the most recent assignment frame: out[0..2] the eigenvalues 2, 3, 4 of L as the solver sees them
+ * (1 - Ritz value; NaN where the group is too small to have one); out[3] Lanczos steps used; out[4] 2-means rounds (label
+ * passes, the one that found no change included); out[5], out[6] atoms in 2-means cluster 0 and 1; out[7], out[8] atoms in the
+ * upper and the lower leaflet (before `flip`); out[9], out[10] o_up, o_lo: the share of cluster 0 that was upper / lower in the
+ * previous assignment frame (NaN for frame 0); out[11] reserved, 0.  gorder_hip_leaflet_distances gives each molecule's first
+ * embedding coordinate (v2 after row normalisation, sign: the group's first atom is not negative).
+ * gorder_hip_prime_leaflets: frame 0 gives the ab-initio orientation, a later frame is matched against the clusters the handle
+ * holds — a shard primes frame 0, then the last assignment frame before its range; a later assignment frame with nothing held
+ * is GORDER_ERR_LEAFLETS_NOT_PRIMED; gorder_hip_reset forgets the held clusters.
+ * GORDER_ERR_INVALID_ARGUMENT for other methods or before any assignment.  Waits for the stream. */
+int gorder_hip_clustering_stats(gorder_hip_handle *h, float out[12]);
 
 /* Manual membrane normals (MembraneNormal::Manual, ManualMembraneNormal::get_normal, normal.rs:266-300): the host
  * resolves the normals file and hands over, before a submit call, one vector per frame of that batch and per
@@ -431,7 +464,8 @@ const char *gorder_hip_strerror(int status);
 
 /* Device time of the submits since the last call with reset != 0 (ms, HIP events on the stream the handle launches on) and
  * their number.  The first call switches the timing on; submits before it are not timed.  A submit is timed as a chain of
- * segments, one per kernel group it queues — the leaflet kernels ("k_leaflets_global_contig"; "k_leaflets_spherical"; "k_local_build",
+ * segments, one per kernel group it queues — the leaflet kernels ("k_leaflets_global_contig"; "k_leaflets_spherical";
+ * "k_cluster_degrees", "k_cluster_lanczos", "k_cluster_embed", "k_cluster_orient" per slab of frames; "k_local_build",
  * "k_local_rowprefix", "k_local_flags_rows", "k_local_flags_todo" per 256-frame slab; ...), "k_dyn_cov + k_dyn_eigen",
  * "k_geom_shapes", the order kernels ("k_bonds_tiled", "k_ua_extras", "k_bonds_tiled_maps", ...), "k_map_accumulate",
  * "k_bonds_direct", "k_batch_end" —; *ms is the sum over all segments, i.e. the WHOLE step on the device. */
