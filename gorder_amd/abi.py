@@ -40,6 +40,7 @@ ERR_CLUSTER_MATCH = 108      # spectral clustering: the clusters match neither l
 
 LEAFLETS_NONE, LEAFLETS_GLOBAL, LEAFLETS_LOCAL, LEAFLETS_INDIVIDUAL, LEAFLETS_MANUAL, LEAFLETS_SPHERICAL = range(6)
 LEAFLETS_CLUSTERING = 6      # spectral clustering (include/gorder_hip.h): membranes of any shape
+COLLECT_LEAFLETS, COLLECT_NORMALS = 1, 2   # gorder_collect_t: what HipEngine.set_collect keeps of every frame
 FLAG_TRIG_ACOS_COS = 1
 FLAG_UA_FAST_NORMALISE = 2      # united atoms: tolerance-bounded hydrogen construction (include/gorder_hip.h)
 UA_CH1_SAT, UA_CH2, UA_CH3, UA_CH1_UNSAT = 1, 2, 3, 4
@@ -316,6 +317,7 @@ _EXPORTS = [
     "gorder_hip_comm_unique_id", "gorder_hip_comm_create", "gorder_hip_comm_destroy", "gorder_hip_allreduce",
     "gorder_hip_reset", "gorder_hip_xtc_decode", "gorder_hip_release_staging", "gorder_hip_speculation_stats", "gorder_hip_local_decide_stats",
     "gorder_hip_spherical_stats", "gorder_hip_clustering_stats",
+    "gorder_hip_set_collect", "gorder_hip_collected_counts", "gorder_hip_collected_leaflets", "gorder_hip_collected_normals",
 ]
 
 _lib = None
@@ -402,6 +404,10 @@ def load_library() -> C.CDLL:
     lib.gorder_hip_xtc_decode.argtypes = [vp, vp, u64, vp, u32, u32, vp, u32, vp, u32]
     lib.gorder_hip_release_staging.argtypes = [vp]
     lib.gorder_hip_release_staging.restype = None
+    lib.gorder_hip_set_collect.argtypes = [vp, u32]
+    lib.gorder_hip_collected_counts.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    lib.gorder_hip_collected_leaflets.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
+    lib.gorder_hip_collected_normals.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
     _lib = lib
     return lib
 
@@ -684,6 +690,42 @@ class HipEngine:
         fr = C.c_uint64()
         self._check(self.lib.gorder_hip_leaflets(self._h, flags.ctypes.data_as(C.c_void_p), C.byref(fr)))
         return flags, int(fr.value)
+
+    def set_collect(self, what: int):
+        """Keep every assignment frame's leaflet flags (COLLECT_LEAFLETS) and / or every analysed frame's dynamic membrane
+        normals (COLLECT_NORMALS) of the frames submitted from now on (gorder_hip_set_collect): before the first submit
+        or right after reset()."""
+        self._check(self.lib.gorder_hip_set_collect(self._h, what))
+
+    def collected_counts(self):
+        """(leaflet rows, normal rows) collected so far; does not wait."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.gorder_hip_collected_counts(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def collected_leaflets(self):
+        """Every assignment frame since set_collect / reset -> (flags [rows, n_molecules_total] u8, Upper = 0 / Lower = 1,
+        frames [rows] u64: the frames' global indices)."""
+        rows = self.collected_counts()[0]
+        flags = np.zeros((rows, self.tables.n_molecules_total), dtype=np.uint8)
+        frames = np.zeros(rows, dtype=np.uint64)
+        n = C.c_uint64()
+        self._check(self.lib.gorder_hip_collected_leaflets(self._h, flags.ctypes.data_as(C.c_void_p),
+                                                           frames.ctypes.data_as(C.c_void_p), rows, C.byref(n)))
+        assert n.value == rows
+        return flags, frames
+
+    def collected_normals(self):
+        """Every analysed frame since set_collect / reset -> (normals [rows, n_molecules_total, 3] f32, NaN where the
+        reference never computed the molecule's normal in that frame, frames [rows] u64)."""
+        rows = self.collected_counts()[1]
+        normals = np.zeros((rows, self.tables.n_molecules_total, 3), dtype=np.float32)
+        frames = np.zeros(rows, dtype=np.uint64)
+        n = C.c_uint64()
+        self._check(self.lib.gorder_hip_collected_normals(self._h, normals.ctypes.data_as(C.c_void_p),
+                                                          frames.ctypes.data_as(C.c_void_p), rows, C.byref(n)))
+        assert n.value == rows
+        return normals, frames
 
     def leaflet_distances(self) -> np.ndarray:
         d = np.zeros(self.tables.n_molecules_total, dtype=np.float32)

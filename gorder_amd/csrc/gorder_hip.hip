@@ -35,6 +35,7 @@
 #include "../../include/gorder_hip.h"
 #include "gm_math.h"
 #include "plan.h"
+#include "collect_store.h"
 
 #pragma clang fp contract(off)
 
@@ -51,6 +52,7 @@ using gorder::Tile;
 #include "kernels_cluster.h"
 #include "kernels_normals.h"
 #include "kernels_xtc.h"
+#include "kernels_collect.h"
 
 // ============================================================================================
 // host side
@@ -236,6 +238,16 @@ struct gorder_hip_handle {
     std::deque<BatchLog> batch_log;
     uint64_t n_submits = 0;
     const unsigned long long *decoder_key = nullptr;   // gorder_hip_run_trajectory: the slot's decoder record, for the next submit only
+    // collected history (gorder_hip_set_collect): per batch the rows are packed into a device staging block (k_collect_flags,
+    // k_collect_normals) and copied, stream-ordered, into the pinned chunks of the stores (collect_store.h)
+    uint32_t collect = 0;                       // gorder_collect_t bits
+    bool collect_locked = false;                // something was submitted or primed since create / reset
+    gorder::CollectStore collect_flags;         // rows of ceil(n_mol / 64) u64
+    gorder::CollectStore collect_normals;       // rows of n_mol x 3 f32
+    unsigned long long *d_collect_words = nullptr;
+    CollectVec3 *d_collect_vec = nullptr;
+    uint8_t *d_touched = nullptr;               // [n_frames][n_mol_total] of the batch (ExtraArgs::touched)
+    size_t collect_words_cap = 0, collect_vec_cap = 0, touched_cap = 0;
 };
 
 namespace {
@@ -748,6 +760,55 @@ int launch_orders(gorder_hip_handle *h, FrameArgs &a) {
     }
 #undef name
     return GORDER_OK;       // (the frames are counted by k_batch_end, which also closes the batch's timing chain)
+}
+
+// ---- collected history (gorder_hip_set_collect): staging block -> pinned chunks ----------------------------------------
+void *collect_host_alloc(size_t bytes) {
+    void *p = nullptr;
+    return hipHostMalloc(&p, bytes) == hipSuccess ? p : nullptr;
+}
+void collect_host_free(void *p) { (void)hipHostFree(p); }
+
+// reserve `n_rows` rows labelled `frames` and queue the copies that fill them from the staging block (a batch that crosses
+// a chunk boundary takes more than one copy); nothing waits
+int collect_copy_out(gorder_hip_handle *h, gorder::CollectStore &store, const void *d_block, const uint64_t *frames, size_t n_rows) {
+    std::vector<gorder::CollectPiece> pieces;
+    if (!store.reserve(frames, n_rows, pieces)) return fail(h, GORDER_ERR_DEVICE, "collect: no pinned host memory for the history");
+    const char *src = static_cast<const char *>(d_block);
+    for (const gorder::CollectPiece &pc : pieces) {
+        const size_t bytes = pc.rows * store.row_bytes();
+        HIP_TRY(h, hipMemcpyAsync(pc.host, src, bytes, hipMemcpyDeviceToHost, h->stream));
+        src += bytes;
+    }
+    return GORDER_OK;
+}
+
+// rows first_row .. of d_aflags are the sides of the assignment frames `frames`: pack and keep them
+int collect_flag_rows(gorder_hip_handle *h, size_t first_row, const std::vector<uint64_t> &frames) {
+    if (frames.empty()) return GORDER_OK;
+    const uint32_t n_mol = h->plan.n_mol_total, wpr = (uint32_t)gorder::collect_flag_words(n_mol);
+    const unsigned long long total = (unsigned long long)frames.size() * wpr;
+    if ((total + 3u) / 4u > 0x7fffffffull || frames.size() > 0xffffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "collect: batch too large");
+    int st;
+    if ((st = ensure(h, &h->d_collect_words, &h->collect_words_cap, (size_t)total)) != GORDER_OK) return st;
+    TIMING_MARK(h, "k_collect_flags");
+    hipLaunchKernelGGL(k_collect_flags, dim3((uint32_t)((total + 3u) / 4u)), dim3(256), 0, h->stream,
+                       h->d_aflags + first_row * (size_t)n_mol, n_mol, (uint32_t)frames.size(), wpr, h->d_collect_words);
+    HIP_TRY(h, hipGetLastError());
+    return collect_copy_out(h, h->collect_flags, h->d_collect_words, frames.data(), frames.size());
+}
+
+// the batch's d_dyn_normals [n_frames][n_mol_total] as rows of three floats a molecule
+int collect_normal_rows(gorder_hip_handle *h, const uint64_t *frame_index, uint32_t n_frames, const uint8_t *touched) {
+    const unsigned long long n = (unsigned long long)n_frames * h->plan.n_mol_total;
+    if ((n + 255u) / 256u > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "collect: batch too large");
+    int st;
+    if ((st = ensure(h, &h->d_collect_vec, &h->collect_vec_cap, (size_t)n)) != GORDER_OK) return st;
+    TIMING_MARK(h, "k_collect_normals");
+    hipLaunchKernelGGL(k_collect_normals, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, h->stream,
+                       (const float4 *)h->d_dyn_normals, touched, n, h->d_collect_vec);
+    HIP_TRY(h, hipGetLastError());
+    return collect_copy_out(h, h->collect_normals, h->d_collect_vec, frame_index, n_frames);
 }
 
 }  // namespace
@@ -1410,6 +1471,8 @@ void gorder_hip_destroy(gorder_hip_handle *h) {
     (void)hipFree(h->d_cl_scratch); (void)hipFree(h->d_cl_head_slot); (void)hipFree(h->d_cl_carry); (void)hipFree(h->d_cl_is0);
     (void)hipFree(h->d_cl_stats);
     (void)hipFree(h->d_arow); (void)hipFree(h->d_aframes);
+    (void)hipFree(h->d_collect_words); (void)hipFree(h->d_collect_vec); (void)hipFree(h->d_touched);
+    h->collect_flags.release(); h->collect_normals.release();     // (the stream was waited for above: no copy is in flight)
     (void)hipFree(h->d_lcell_of); (void)hipFree(h->d_lcell_count); (void)hipFree(h->d_lcell_fill);
     (void)hipFree(h->d_ltrig);
     for (int k = 0; k < 2; k++) {
@@ -1707,6 +1770,7 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
     if (((uintptr_t)d_xyz & 15u) != 0) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "d_xyz must be 16-byte aligned");
     if (n_frames == 0) return GORDER_OK;
     HIP_TRY(h, hipSetDevice(h->device));
+    h->collect_locked = true;
     const Plan &p = h->plan;
     const gorder_leaflets_t &lf = h->tables.leaflets;
     int st;
@@ -1722,6 +1786,7 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
     size_t n_new_rows = 0;
     bool spec = false;
     std::vector<uint32_t> spec_aframes;
+    std::vector<uint64_t> collect_frames;       // collected leaflets: the assignment frames of this batch = rows 1.. of d_aflags
     // argument errors come before the first kernel of the batch is queued (a batch that fails later leaves through
     // abort_batch below, so that a key its kernels raised is not committed under the next batch's ordinal)
     if (h->manual_frames) {
@@ -1794,6 +1859,8 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
             h->up_arow = arow;
             h->up_arow_at = h->d_arow;
         }
+        if (h->collect & GORDER_COLLECT_LEAFLETS)
+            for (uint32_t f : aframes) collect_frames.push_back(frame_index[f]);
         if (spec) spec_aframes = aframes;
         else if ((st = run_leaflets(h, d_xyz, d_box, aframes, 1)) != GORDER_OK) return abort_batch(st);
         h->have_assignment = true;
@@ -1844,6 +1911,14 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
         a.own_head_begin = h->d_own_head_begin; a.own_heads = h->d_own_heads; a.head_z = h->d_head_z;
         h->spec_now = true;
     }
+    h->extra.touched = nullptr;
+    if ((h->collect & GORDER_COLLECT_NORMALS) && h->extra.geom_kind && !p.tiles.empty() && p.ua_tiles.empty()) {
+        // bond systems fetch a molecule's normal after the geometry test (bond.rs:424-431): k_bonds_extras marks who did
+        const size_t nt = (size_t)n_frames * p.n_mol_total;
+        if ((st = ensure(h, &h->d_touched, &h->touched_cap, nt)) != GORDER_OK) return abort_batch(st);
+        if (hipMemsetAsync(h->d_touched, 0, nt, h->stream) != hipSuccess) return abort_batch(fail(h, GORDER_ERR_DEVICE, "collect: hipMemsetAsync"));
+        h->extra.touched = h->d_touched;
+    }
     st = launch_orders(h, a);
     h->spec_now = false;
     h->manual_active = false;
@@ -1885,6 +1960,10 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
         h->spec_ring_frames[ring_slot] = n_frames;
         h->spec_batches++;
     }
+    // the history a host asked for (rows 1.. of d_aflags hold every assignment frame's exact sides by now)
+    if ((st = collect_flag_rows(h, 1, collect_frames)) != GORDER_OK) return abort_batch(st);
+    if ((h->collect & GORDER_COLLECT_NORMALS) && p.n_mol_total &&
+        (st = collect_normal_rows(h, frame_index, n_frames, h->extra.touched)) != GORDER_OK) return abort_batch(st);
     if (n_new_rows) {   // newest assignment becomes the carry row of the next batch
         HIP_TRY(h, hipMemcpyAsync(h->d_aflags, h->d_aflags + n_new_rows * (size_t)p.n_mol_total, p.n_mol_total,
                                   hipMemcpyDeviceToDevice, h->stream));
@@ -1952,6 +2031,7 @@ int gorder_hip_prime_leaflets(gorder_hip_handle *h, const float *d_xyz, const fl
     if (lf.method == GORDER_LEAFLETS_NONE || lf.method == GORDER_LEAFLETS_MANUAL) return GORDER_ERR_INVALID_ARGUMENT;
     if (h->tables.handle_pbc && !d_box) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "box required when handle_pbc = 1");
     HIP_TRY(h, hipSetDevice(h->device));
+    h->collect_locked = true;     // (no row: the primed frame belongs to the shard that analyses it)
     if (h->tables.handle_pbc) {   // the priming frame goes through check_box like any analysed frame (common.rs:186-198)
         hipLaunchKernelGGL(k_check_box, dim3(1), dim3(256), 0, h->stream, d_box, 1u, h->d_err);
         HIP_TRY(h, hipGetLastError());
@@ -1992,6 +2072,12 @@ int gorder_hip_set_manual_leaflets(gorder_hip_handle *h, const uint8_t *flags, u
     HIP_TRY(h, hipMemcpy(h->d_aflags, tmp.data(), n, hipMemcpyHostToDevice));
     h->have_assignment = true;
     h->assignment_frame = frame_index;
+    h->collect_locked = true;
+    if (h->collect & GORDER_COLLECT_LEAFLETS) {     // the row the host handed over is an assignment frame's row like any other
+        const int st = collect_flag_rows(h, 0, std::vector<uint64_t>(1, frame_index));
+        (void)timing_mark(h, nullptr);
+        if (st != GORDER_OK) return st;
+    }
     return GORDER_OK;
 }
 
@@ -2097,6 +2183,70 @@ int gorder_hip_leaflets(gorder_hip_handle *h, uint8_t *flags, uint64_t *assignme
     return GORDER_OK;
 }
 
+// ---- collected history: every assignment frame's flags, every analysed frame's dynamic normals --------------------------
+int gorder_hip_set_collect(gorder_hip_handle *h, uint32_t what) {
+    if (!h) return GORDER_ERR_INVALID_ARGUMENT;
+    if (what & ~(uint32_t)(GORDER_COLLECT_LEAFLETS | GORDER_COLLECT_NORMALS)) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_collect: unknown bit");
+    if (h->collect_locked)
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_collect: only before the first submit or prime, or right after gorder_hip_reset");
+    if ((what & GORDER_COLLECT_LEAFLETS) && h->tables.leaflets.method == GORDER_LEAFLETS_NONE)
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_collect: no leaflet method to collect from");
+    if ((what & GORDER_COLLECT_NORMALS) && !h->dyn)
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_collect: normals are collected for dynamic membrane normals only");
+    if (what && !h->plan.n_mol_total) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_collect: no molecules");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const gorder::CollectAlloc pinned{collect_host_alloc, collect_host_free};
+    if ((what & GORDER_COLLECT_LEAFLETS) && !h->collect_flags.configured())
+        h->collect_flags.configure(gorder::collect_flag_words(h->plan.n_mol_total) * sizeof(uint64_t), pinned);
+    if ((what & GORDER_COLLECT_NORMALS) && !h->collect_normals.configured())
+        h->collect_normals.configure((size_t)h->plan.n_mol_total * 3u * sizeof(float), pinned);
+    h->collect_flags.clear();
+    h->collect_normals.clear();
+    h->collect = what;
+    return GORDER_OK;
+}
+
+int gorder_hip_collected_counts(gorder_hip_handle *h, uint64_t *n_leaflet_rows, uint64_t *n_normal_rows) {
+    if (!h) return GORDER_ERR_INVALID_ARGUMENT;
+    if (n_leaflet_rows) *n_leaflet_rows = (h->collect & GORDER_COLLECT_LEAFLETS) ? h->collect_flags.n_rows() : 0;
+    if (n_normal_rows) *n_normal_rows = (h->collect & GORDER_COLLECT_NORMALS) ? h->collect_normals.n_rows() : 0;
+    return GORDER_OK;
+}
+
+int gorder_hip_collected_leaflets(gorder_hip_handle *h, uint8_t *flags, uint64_t *frames, uint64_t capacity_rows, uint64_t *n_rows) {
+    if (!h || !n_rows) return GORDER_ERR_INVALID_ARGUMENT;
+    *n_rows = 0;
+    if (!(h->collect & GORDER_COLLECT_LEAFLETS)) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_collected_leaflets: leaflets are not being collected");
+    const gorder::CollectStore &store = h->collect_flags;
+    *n_rows = store.n_rows();
+    if ((flags || frames) && capacity_rows < store.n_rows()) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_collected_leaflets: capacity_rows is too small");
+    const int st = gorder_hip_synchronize(h);       // the copies into the chunks are behind the batches' kernels on the stream
+    if (st != GORDER_OK) return st;
+    const size_t n_mol = h->plan.n_mol_total;
+    if (flags)
+        store.for_each_row([&](uint64_t r, const void *row) {
+            gorder::collect_unpack_flags(static_cast<const uint64_t *>(row), n_mol, flags + r * n_mol);
+        });
+    if (frames && store.n_rows()) memcpy(frames, store.frames().data(), store.n_rows() * sizeof(uint64_t));
+    return GORDER_OK;
+}
+
+int gorder_hip_collected_normals(gorder_hip_handle *h, float *normals, uint64_t *frames, uint64_t capacity_rows, uint64_t *n_rows) {
+    if (!h || !n_rows) return GORDER_ERR_INVALID_ARGUMENT;
+    *n_rows = 0;
+    if (!(h->collect & GORDER_COLLECT_NORMALS)) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_collected_normals: normals are not being collected");
+    const gorder::CollectStore &store = h->collect_normals;
+    *n_rows = store.n_rows();
+    if ((normals || frames) && capacity_rows < store.n_rows()) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_collected_normals: capacity_rows is too small");
+    const int st = gorder_hip_synchronize(h);
+    if (st != GORDER_OK) return st;
+    const size_t row_floats = (size_t)h->plan.n_mol_total * 3u;
+    if (normals)
+        store.for_each_row([&](uint64_t r, const void *row) { memcpy(normals + r * row_floats, row, row_floats * sizeof(float)); });
+    if (frames && store.n_rows()) memcpy(frames, store.frames().data(), store.n_rows() * sizeof(uint64_t));
+    return GORDER_OK;
+}
+
 int gorder_hip_leaflet_distances(gorder_hip_handle *h, float *dist) {
     if (!h || !dist || !h->d_adist) return GORDER_ERR_INVALID_ARGUMENT;
     const int st = gorder_hip_synchronize(h);
@@ -2187,6 +2337,11 @@ int gorder_hip_reset(gorder_hip_handle *h) {
     HIP_TRY(h, hipMemsetAsync(h->d_err, 0xff, kErrWords * sizeof(uint32_t), h->stream));
     h->batch_log.clear();
     h->n_frames = 0;
+    // collected rows: gone (the chunks stay, copies still queued into them run before anything a later batch queues); the
+    // switch stays and may be set anew
+    h->collect_flags.clear();
+    h->collect_normals.clear();
+    h->collect_locked = false;
     h->have_assignment = false;
     h->cl_have_carry = false;
     h->assignment_frame = 0;

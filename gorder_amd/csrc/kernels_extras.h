@@ -47,6 +47,9 @@ struct ExtraArgs {
     // GORDER_FLAG_UA_FAST_NORMALISE: box edges and 1 / box edge per frame [n_frames][8] (k_inv_box: IEEE divisions, once per frame instead
     // of once per lane and frame), or null
     const float *inv_box;
+    // collected normals (gorder_hip_set_collect) of a bond system with a geometry selection: [n_frames][n_mol_total], 1 where a
+    // sample fetched the molecule's normal of that frame; null otherwise
+    uint8_t *touched;
 };
 
 // groan_rs Rectangular / Cylinder / Sphere ::inside (oracle: inside_shape), XOR invert (geometry.rs:181-189).
@@ -238,6 +241,7 @@ __global__ __launch_bounds__(kBlock) void k_bonds_extras(FrameArgs a_in, ExtraAr
                 float sch;
                 if (!MAPS_ONLY && e.dyn) {   // the molecule's own normal of this frame, fetched after the geometry test (bond.rs:429-431)
                     const float4 n = e.dyn[(size_t)f * a.n_mol_total + it.mol];
+                    if (e.touched) e.touched[(size_t)f * a.n_mol_total + it.mol] = 1;     // (racing lanes store the same byte)
                     if (n.w < 3.0f) raise_error(a.err, GORDER_ERR_DYNAMIC_NORMAL, f, kStageTypes, gslot, 1, it.mol, (uint32_t)n.w);
                     const float n2sq = (n.x * n.x + n.y * n.y) + n.z * n.z;
                     sch = gm_calc_sch<ACOS_COS>(vx, vy, vz, n.x, n.y, n.z, __builtin_sqrtf(n2sq), n2sq);

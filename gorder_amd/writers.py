@@ -239,3 +239,56 @@ def convergence_text(timewise, labels, analysis: str, leaflets: bool, header: Op
     for f in range(sums.shape[0]):
         out.append(f"{f * step + 1:<4d} " + " ".join(f"{_fixed(c[f]):>8s}" for c in cols) + " ")
     return "\n".join(out) + "\n"
+
+
+def _per_type_rows(labels, n_columns: int):
+    """(name, column slice) per molecule type: the molecules are stored molecule type major."""
+    at = 0
+    for ml in labels:
+        yield ml.name, slice(at, at + ml.n_molecules)
+        at += ml.n_molecules
+    if at != n_columns:
+        raise ValueError(f"the labels hold {at} molecules, the rows {n_columns}")
+
+
+def leaflets_export_text(flags, frames, labels, frequency: int, header: Optional[str] = None) -> str:
+    """The reference's leaflet assignment file (tests/golden/expected/aa_leaflets_every5.yaml) from what
+    HipEngine.collected_leaflets returns: per molecule type a sequence with one flow list per assignment frame, 1 = upper
+    and 0 = lower (this repo stores Upper = 0), each under a comment with the frame's number counted from 1.  `frequency`
+    is the real frequency of the classifier (0 = once): the frames must be its assignment frames."""
+    import numpy as np
+    flags, frames = np.asarray(flags), np.asarray(frames)
+    if flags.ndim != 2 or len(frames) != flags.shape[0]:
+        raise ValueError("flags [rows, molecules] and frames [rows]")
+    for f in frames:
+        if (int(f) != 0) if frequency == 0 else (int(f) % frequency != 0):
+            raise ValueError(f"frame {int(f)} is not an assignment frame of frequency {frequency}")
+    out = [header or "# Leaflet assignment file"]
+    for name, cols in _per_type_rows(labels, flags.shape[1]):
+        out.append(f"{name}:")
+        for row, f in zip(flags, frames):
+            out.append(f"# Frame index {int(f) + 1}")
+            out.append("  - [" + ",".join("0" if x else "1" for x in row[cols]) + "]")
+    return "\n".join(out) + "\n"
+
+
+def _component(x) -> str:
+    return f"{'NaN' if x != x else format(float(x), '.6f'):>9s}"
+
+
+def normals_export_text(normals, frames, labels, header: Optional[str] = None) -> str:
+    """The reference's membrane normals file (tests/golden/expected/ua_normals.yaml) from what
+    HipEngine.collected_normals returns: per molecule type one flow list of [x,y,z] per analysed frame, every component
+    9 wide with 6 decimals, a normal that was never computed as NaN (a YAML reader takes that as a string: read it back
+    with float())."""
+    import numpy as np
+    normals, frames = np.asarray(normals), np.asarray(frames)
+    if normals.ndim != 3 or normals.shape[2] != 3 or len(frames) != normals.shape[0]:
+        raise ValueError("normals [rows, molecules, 3] and frames [rows]")
+    out = [header or "# Membrane normals file"]
+    for name, cols in _per_type_rows(labels, normals.shape[1]):
+        out.append(f"{name}:")
+        for row, f in zip(normals, frames):
+            out.append(f"# Frame index {int(f) + 1}")
+            out.append("  - [" + ",".join("[" + ",".join(_component(c) for c in v) + "]" for v in row[cols]) + "]")
+    return "\n".join(out) + "\n"

@@ -383,6 +383,41 @@ int gorder_hip_timewise(gorder_hip_handle *h, int64_t *tw_sums, uint64_t *tw_cou
 
 /* Leaflet flags of the most recent assignment frame, [n_molecules_total] (Upper=0, Lower=1). */
 int gorder_hip_leaflets(gorder_hip_handle *h, uint8_t *flags, uint64_t *assignment_frame);
+/* ---- collected history ("Exporting internal data": LeafletClassification::..with_collect, AssignedLeaflets, NormalsStorage,
+ * DynamicMembraneNormal::store_normals normal.rs:210-227) --------------------------------------------------------------------
+ * gorder_hip_leaflets and gorder_hip_normals give the LAST frame only.  With collection switched on the handle keeps, for
+ * every batch however it was cut, one row of leaflet flags per assignment frame (should_assign, leaflets.rs:435-441) and one row
+ * of dynamic membrane normals per analysed frame: packed on the device (k_collect_flags: 1 bit a molecule; k_collect_normals:
+ * 12 bytes a molecule), copied behind the batch's kernels into pinned host memory the handle owns (chunks of 8 MiB or one batch,
+ * never moved, reused after gorder_hip_reset) — a submit stays asynchronous.  A handle that never calls gorder_hip_set_collect
+ * queues exactly what it queued before.
+ * gorder_hip_set_collect: accepted before the first submit / prime / set_manual_leaflets or right after gorder_hip_reset, else
+ *   GORDER_ERR_INVALID_ARGUMENT; GORDER_COLLECT_LEAFLETS needs leaflets.method != NONE (GORDER_LEAFLETS_MANUAL: the rows are
+ *   the flags the host handed over, each with its frame_index), GORDER_COLLECT_NORMALS needs dynamic_normal.enabled (static and
+ *   manual normals are not stored by the reference either, normal.rs:111-116).
+ * gorder_hip_prime_leaflets appends NO row: the primed frame belongs to the shard that analyses it, so the rows of the shards
+ *   concatenated by frames[] hold every assignment frame exactly once.
+ * gorder_hip_reset clears the rows and keeps the switch; gorder_hip_release_staging keeps the rows.
+ * A normal is {NaN, NaN, NaN} where the reference never computed it: AA / CG fetch a molecule's normal after the geometry test
+ *   (bond.rs:424-431), so a molecule none of whose bonds lay inside the selection in that frame is NaN; united atoms fetch it
+ *   for every molecule before the test (uaorder.rs:412-413): none is NaN.
+ * The two readers wait for the handle's stream (a device error of the run is returned as by gorder_hip_synchronize); *n_rows is
+ *   always set; GORDER_ERR_INVALID_ARGUMENT if that kind is not being collected or capacity_rows < *n_rows. */
+typedef enum { GORDER_COLLECT_LEAFLETS = 1u, GORDER_COLLECT_NORMALS = 2u } gorder_collect_t;
+/* Switch collection on (bit set of gorder_collect_t; 0 = off). */
+int gorder_hip_set_collect(gorder_hip_handle *h, uint32_t what);
+/* Rows collected so far: assignment frames, analysed frames. */
+int gorder_hip_collected_counts(gorder_hip_handle *h, uint64_t *n_leaflet_rows, uint64_t *n_normal_rows);
+/* flags  [n_rows][n_molecules_total]  Upper=0 / Lower=1, after `flip`, molecules in molecule-type-major order
+ * frames [n_rows]                     the assignment frames' global frame indices, ascending in submission order
+ * Either pointer may be NULL to skip it; *n_rows is always set. */
+int gorder_hip_collected_leaflets(gorder_hip_handle *h, uint8_t *flags, uint64_t *frames,
+                                  uint64_t capacity_rows, uint64_t *n_rows);
+/* normals [n_rows][n_molecules_total][3]  unit vectors
+ * frames  [n_rows]                        global frame indices */
+int gorder_hip_collected_normals(gorder_hip_handle *h, float *normals, uint64_t *frames,
+                                 uint64_t capacity_rows, uint64_t *n_rows);
+
 /* Signed distances (nm) behind those flags, [n_molecules_total] (leaflets.rs:725, 796).  GORDER_LEAFLETS_SPHERICAL: each
  * molecule's head-centre distance (nm, non-negative) in the last assignment frame. */
 int gorder_hip_leaflet_distances(gorder_hip_handle *h, float *distances);
@@ -468,7 +503,7 @@ const char *gorder_hip_strerror(int status);
  * "k_cluster_degrees", "k_cluster_lanczos", "k_cluster_embed", "k_cluster_orient" per slab of frames; "k_local_build",
  * "k_local_rowprefix", "k_local_flags_rows", "k_local_flags_todo" per 256-frame slab; ...), "k_dyn_cov + k_dyn_eigen",
  * "k_geom_shapes", the order kernels ("k_bonds_tiled", "k_ua_extras", "k_bonds_tiled_maps", ...), "k_map_accumulate",
- * "k_bonds_direct", "k_batch_end" —; *ms is the sum over all segments, i.e. the WHOLE step on the device. */
+ * "k_bonds_direct", with collection "k_collect_flags" and "k_collect_normals" (the copy to the host included), "k_batch_end" —; *ms is the sum over all segments, i.e. the WHOLE step on the device. */
 int gorder_hip_kernel_time(gorder_hip_handle *h, double *ms, uint64_t *launches, int reset);
 /* Group `index` of the same measurement (in order of first appearance since the last reset): its name, the device time
  * of its segments and their number.  GORDER_ERR_INVALID_ARGUMENT past the last group.  The times of all groups add up to
