@@ -28,6 +28,9 @@ ERR_ZERO_BOX = 3
 ERR_UNDEFINED_POSITION = 4
 ERR_INVALID_GLOBAL_MEMBRANE_CENTER = 5
 ERR_INVALID_LOCAL_MEMBRANE_CENTER = 6
+ERR_DYNAMIC_NORMAL = 7
+ERR_MANUAL_LEAFLET_FRAME = 8     # a frame has no row in the manual leaflet table (HipEngine.set_manual_leaflet_table)
+ERR_MANUAL_NORMAL_FRAME = 9      # a frame has no row in the manual normal table (HipEngine.set_manual_normal_table)
 ERR_INVALID_ARGUMENT = 100
 ERR_DEVICE = 101
 ERR_NO_DEVICE = 102
@@ -318,6 +321,7 @@ _EXPORTS = [
     "gorder_hip_reset", "gorder_hip_xtc_decode", "gorder_hip_release_staging", "gorder_hip_speculation_stats", "gorder_hip_local_decide_stats",
     "gorder_hip_spherical_stats", "gorder_hip_clustering_stats",
     "gorder_hip_set_collect", "gorder_hip_collected_counts", "gorder_hip_collected_leaflets", "gorder_hip_collected_normals",
+    "gorder_hip_set_manual_leaflet_table", "gorder_hip_set_manual_normal_table",
 ]
 
 _lib = None
@@ -408,6 +412,8 @@ def load_library() -> C.CDLL:
     lib.gorder_hip_collected_counts.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     lib.gorder_hip_collected_leaflets.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
     lib.gorder_hip_collected_normals.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
+    lib.gorder_hip_set_manual_leaflet_table.argtypes = [vp, vp, u64, u64]
+    lib.gorder_hip_set_manual_normal_table.argtypes = [vp, vp, u32, u64, u64]
     _lib = lib
     return lib
 
@@ -650,6 +656,26 @@ class HipEngine:
         flags = np.ascontiguousarray(flags, dtype=np.uint8)
         assert flags.size == self.tables.n_molecules_total
         self._check(self.lib.gorder_hip_set_manual_leaflets(self._h, flags.ctypes.data_as(C.c_void_p), frame_index))
+
+    def set_manual_leaflet_table(self, flags, first_row: int = 0):
+        """Manual leaflets of the whole trajectory (gorder_hip_set_manual_leaflet_table): flags [rows, n_molecules_total],
+        Upper = 0 / Lower = 1, row r = assignment index first_row + r (frame // frequency; 0 for frequency 0) — what
+        collected_leaflets() or manual.read_leaflets_file gives.  Copied to the device; zero rows (or None) remove the table."""
+        n_mol = self.tables.n_molecules_total
+        flags = np.zeros((0, n_mol), dtype=np.uint8) if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
+        assert flags.ndim == 2 and flags.shape[1] == n_mol
+        self._check(self.lib.gorder_hip_set_manual_leaflet_table(self._h, flags.ctypes.data_as(C.c_void_p) if len(flags) else None,
+                                                                 first_row, len(flags)))
+
+    def set_manual_normal_table(self, normals, step: int = 1, first_row: int = 0):
+        """Manual membrane normals of the whole trajectory (gorder_hip_set_manual_normal_table): normals
+        [rows, n_molecules_total, 3], row r = frame (first_row + r) * step — what collected_normals() or
+        manual.read_normals_file gives.  Copied to the device; zero rows (or None) remove the table."""
+        n_mol = self.tables.n_molecules_total
+        n = np.zeros((0, n_mol, 3), dtype=np.float32) if normals is None else np.ascontiguousarray(normals, dtype=np.float32)
+        assert n.ndim == 3 and n.shape[1:] == (n_mol, 3)
+        self._check(self.lib.gorder_hip_set_manual_normal_table(self._h, n.ctypes.data_as(C.c_void_p) if len(n) else None,
+                                                                step, first_row, len(n)))
 
     def synchronize(self):
         self._check(self.lib.gorder_hip_synchronize(self._h))

@@ -36,6 +36,7 @@
 #include "gm_math.h"
 #include "plan.h"
 #include "collect_store.h"
+#include "replay_rows.h"
 
 #pragma clang fp contract(off)
 
@@ -53,6 +54,7 @@ using gorder::Tile;
 #include "kernels_normals.h"
 #include "kernels_xtc.h"
 #include "kernels_collect.h"
+#include "kernels_replay.h"
 
 // ============================================================================================
 // host side
@@ -248,6 +250,17 @@ struct gorder_hip_handle {
     CollectVec3 *d_collect_vec = nullptr;
     uint8_t *d_touched = nullptr;               // [n_frames][n_mol_total] of the batch (ExtraArgs::touched)
     size_t collect_words_cap = 0, collect_vec_cap = 0, touched_cap = 0;
+    // whole-trajectory manual tables (gorder_hip_set_manual_leaflet_table / _normal_table; replay_rows.h): packed on the
+    // device, expanded per batch by k_replay_flags / k_replay_normals
+    unsigned long long *d_ltable = nullptr;     // [window rows][ceil(n_mol / 64)] u64, before `flip`
+    gorder::ReplayWindow ltable_win;
+    bool replay_have_carry = false;             // row 0 of d_aflags is the table's row replay_carry_index
+    uint64_t replay_carry_index = 0;
+    ReplayVec3 *d_ntable = nullptr;             // [window rows][n_mol] x 12 bytes
+    gorder::ReplayWindow ntable_win;
+    uint32_t ntable_step = 1;
+    uint32_t *d_nrow = nullptr;                 // per frame of the batch: its row of d_ntable
+    size_t nrow_cap = 0;
 };
 
 namespace {
@@ -811,6 +824,53 @@ int collect_normal_rows(gorder_hip_handle *h, const uint64_t *frame_index, uint3
     return collect_copy_out(h, h->collect_normals, h->d_collect_vec, frame_index, n_frames);
 }
 
+// ---- whole-trajectory manual tables: expand what a batch needs (kernels_replay.h) -----------------------------------------
+// a small list of 32-bit rows for this batch, behind everything queued so far
+int upload_rows(gorder_hip_handle *h, uint32_t **buf, size_t *cap, const std::vector<uint32_t> &rows) {
+    const int st = ensure(h, buf, cap, rows.size());
+    if (st != GORDER_OK) return st;
+    HIP_TRY(h, hipMemcpyAsync(*buf, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    return GORDER_OK;
+}
+
+// rows 1.. of d_aflags from the table rows rb.expand
+int replay_flag_rows(gorder_hip_handle *h, const gorder::ReplayLeafletBatch &rb) {
+    if (rb.expand.empty()) return GORDER_OK;
+    const uint32_t n_mol = h->plan.n_mol_total, wpr = (uint32_t)gorder::replay_flag_words(n_mol);
+    const unsigned long long total = (unsigned long long)rb.expand.size() * wpr;
+    if ((total + 3u) / 4u > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "manual leaflet table: batch too large");
+    int st;
+    const size_t cap_before = h->aframes_cap;
+    if ((st = ensure(h, &h->d_aframes, &h->aframes_cap, rb.expand.size())) != GORDER_OK) return st;
+    if (h->aframes_cap != cap_before) h->up_aframes_at = nullptr;
+    if (h->up_aframes_at != h->d_aframes || h->up_aframes != rb.expand) {      // (equal batches skip the upload, as run_leaflets)
+        HIP_TRY(h, hipMemcpyAsync(h->d_aframes, rb.expand.data(), rb.expand.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        h->up_aframes = rb.expand;
+        h->up_aframes_at = h->d_aframes;
+    }
+    TIMING_MARK(h, "k_replay_flags");
+    hipLaunchKernelGGL(k_replay_flags, dim3((uint32_t)((total + 3u) / 4u)), dim3(256), 0, h->stream, h->d_ltable, h->d_aframes,
+                       (uint32_t)rb.expand.size(), wpr, n_mol, h->tables.leaflets.flip ? 1u : 0u, h->d_aflags + n_mol);
+    HIP_TRY(h, hipGetLastError());
+    return GORDER_OK;
+}
+
+// d_dyn_normals [n_frames][n_mol_total] from the table rows row_of_frame
+int replay_normal_rows(gorder_hip_handle *h, const std::vector<uint32_t> &row_of_frame) {
+    const uint32_t n_mol = h->plan.n_mol_total;
+    const unsigned long long n = (unsigned long long)row_of_frame.size() * n_mol;
+    if ((n + 255u) / 256u > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "manual normal table: batch too large");
+    int st;
+    if ((st = ensure(h, &h->d_dyn_normals, &h->dyn_normals_cap, (size_t)n)) != GORDER_OK) return st;
+    if ((st = upload_rows(h, &h->d_nrow, &h->nrow_cap, row_of_frame)) != GORDER_OK) return st;
+    if (!n) return GORDER_OK;
+    TIMING_MARK(h, "k_replay_normals");
+    hipLaunchKernelGGL(k_replay_normals, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, h->stream, h->d_ntable, h->d_nrow, n_mol, n,
+                       h->d_dyn_normals);
+    HIP_TRY(h, hipGetLastError());
+    return GORDER_OK;
+}
+
 }  // namespace
 
 // ---- RCCL: SystemTopology::reduce across the GPUs of a node (topology/mod.rs:256-272) -----------------------------
@@ -875,6 +935,8 @@ const char *gorder_hip_strerror(int status) {
         case GORDER_ERR_INVALID_GLOBAL_MEMBRANE_CENTER: return "could not calculate global membrane center";
         case GORDER_ERR_INVALID_LOCAL_MEMBRANE_CENTER: return "could not calculate local membrane center";
         case GORDER_ERR_DYNAMIC_NORMAL: return "not enough points for dynamic local membrane normal calculation (need 3)";
+        case GORDER_ERR_MANUAL_LEAFLET_FRAME: return "manual leaflet assignment: no row for the frame";
+        case GORDER_ERR_MANUAL_NORMAL_FRAME: return "manual membrane normals: no row for the frame";
         case GORDER_ERR_INVALID_ARGUMENT: return "invalid argument";
         case GORDER_ERR_DEVICE: return "HIP runtime error";
         case GORDER_ERR_NO_DEVICE: return "no HIP device available (this library has no CPU fallback)";
@@ -1472,6 +1534,7 @@ void gorder_hip_destroy(gorder_hip_handle *h) {
     (void)hipFree(h->d_cl_stats);
     (void)hipFree(h->d_arow); (void)hipFree(h->d_aframes);
     (void)hipFree(h->d_collect_words); (void)hipFree(h->d_collect_vec); (void)hipFree(h->d_touched);
+    (void)hipFree(h->d_ltable); (void)hipFree(h->d_ntable); (void)hipFree(h->d_nrow);
     h->collect_flags.release(); h->collect_normals.release();     // (the stream was waited for above: no copy is in flight)
     (void)hipFree(h->d_lcell_of); (void)hipFree(h->d_lcell_count); (void)hipFree(h->d_lcell_fill);
     (void)hipFree(h->d_ltrig);
@@ -1793,6 +1856,28 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
         if (h->manual_frames != n_frames) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_normals: frame count differs from the batch");
         if (!p.direct.empty()) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "manual normals: a bond spans more than the LDS window");
     }
+    // whole-trajectory manual tables: every frame of the batch must have its row, or the batch is refused whole
+    const bool ltable = lf.method == GORDER_LEAFLETS_MANUAL && h->d_ltable;
+    gorder::ReplayLeafletBatch replay;
+    std::vector<uint32_t> normal_rows;
+    if (ltable) {
+        uint64_t bad = 0;
+        if (gorder::replay_plan_leaflets(lf.frequency, h->ltable_win, h->replay_have_carry, h->replay_carry_index, frame_index, n_frames,
+                                         replay, &bad) != gorder::kReplayOk) {
+            h->err_frame = bad;
+            return fail(h, GORDER_ERR_MANUAL_LEAFLET_FRAME, "manual leaflet table: no row for frame " + std::to_string(bad));
+        }
+    }
+    if (h->d_ntable) {
+        uint64_t bad = 0;
+        const gorder::ReplayStatus rs = gorder::replay_plan_normals(h->ntable_step, h->ntable_win, frame_index, n_frames, normal_rows, &bad);
+        if (rs != gorder::kReplayOk) {
+            h->err_frame = bad;
+            if (rs == gorder::kReplayBadStep)
+                return fail(h, GORDER_ERR_INVALID_ARGUMENT, "manual normal table: frame " + std::to_string(bad) + " is no multiple of the step");
+            return fail(h, GORDER_ERR_MANUAL_NORMAL_FRAME, "manual normal table: no row for frame " + std::to_string(bad));
+        }
+    }
     auto abort_batch = [&](int status) {
         hipLaunchKernelGGL(k_batch_abort, dim3(1), dim3(1), 0, h->stream, h->d_err);
         (void)hipGetLastError();
@@ -1804,7 +1889,10 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
         uint32_t cur = 0;
         bool have = h->have_assignment;
         uint64_t last_assign_frame = h->assignment_frame;
-        for (uint32_t f = 0; f < n_frames; f++) {
+        if (ltable) {
+            arow = replay.arow;
+            last_assign_frame = replay.carry_index * lf.frequency;       // the assignment frame of the newest row
+        } else for (uint32_t f = 0; f < n_frames; f++) {
             if (lf.method != GORDER_LEAFLETS_MANUAL && should_assign(lf.frequency, frame_index[f])) {
                 if (lf.method == GORDER_LEAFLETS_CLUSTERING) {
                     // a later assignment frame is matched against the clusters the handle holds
@@ -1827,7 +1915,7 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
         const bool tw_tiled = h->extra.tw && !(h->tables.flags & GORDER_FLAG_TRIG_ACOS_COS) && h->d_item_run &&
                               h->frames_per_stage == (int)kRecFrames && !env_flag("GORDER_HIP_TW_GATHER");
         spec = h->spec_enabled && lf.method == GORDER_LEAFLETS_GLOBAL && h->have_assignment && aframes.size() == n_frames &&
-               !h->extra.maps && (!h->extra.tw || tw_tiled) && !h->extra.geom_kind && !h->dyn && !h->manual_frames &&
+               !h->extra.maps && (!h->extra.tw || tw_tiled) && !h->extra.geom_kind && !h->dyn && !h->manual_frames && !h->d_ntable &&
                !h->use_gather && !p.tiles.empty();
         if (spec) {
             spec_poll(h, false);
@@ -1836,7 +1924,7 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
             spec = h->spec_enabled;
         }
         if (spec) std::fill(arow.begin(), arow.end(), 0u);
-        const size_t rows = aframes.size() + 1;            // (a speculative batch: row 0 and every frame's exact sides)
+        const size_t rows = (ltable ? replay.expand.size() : aframes.size()) + 1;   // (a speculative batch: row 0 and every frame's exact sides)
         if (rows > h->aflags_rows) {
             uint8_t *nb = nullptr;
             const size_t nrows = rows + rows / 4;
@@ -1862,10 +1950,11 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
         if (h->collect & GORDER_COLLECT_LEAFLETS)
             for (uint32_t f : aframes) collect_frames.push_back(frame_index[f]);
         if (spec) spec_aframes = aframes;
+        else if (ltable) { if ((st = replay_flag_rows(h, replay)) != GORDER_OK) return abort_batch(st); }
         else if ((st = run_leaflets(h, d_xyz, d_box, aframes, 1)) != GORDER_OK) return abort_batch(st);
         h->have_assignment = true;
         h->assignment_frame = last_assign_frame;
-        n_new_rows = spec ? 0 : aframes.size();
+        n_new_rows = spec ? 0 : (ltable ? replay.expand.size() : aframes.size());
     }
     // (check_box: k_batch_end, at the end of the batch)
     if (h->extra.tw && h->n_frames + n_frames > h->tw_cap) {   // grow the per-frame rows (timewise.rs:183-186)
@@ -1902,6 +1991,9 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
             return abort_batch(fail(h, GORDER_ERR_DEVICE, "manual normals: copy to the device failed"));
         h->manual_active = true;
         h->manual_frames = 0;
+    } else if (h->d_ntable) {   // ... or the rows of the table, unpacked behind whatever still reads the buffer
+        if ((st = replay_normal_rows(h, normal_rows)) != GORDER_OK) return abort_batch(st);
+        h->manual_active = true;
     }
     const uint32_t n_tiles_all = (uint32_t)p.tiles.size();
     if (spec) {
@@ -1962,12 +2054,24 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
     }
     // the history a host asked for (rows 1.. of d_aflags hold every assignment frame's exact sides by now)
     if ((st = collect_flag_rows(h, 1, collect_frames)) != GORDER_OK) return abort_batch(st);
-    if ((h->collect & GORDER_COLLECT_NORMALS) && p.n_mol_total &&
+    if (ltable && (h->collect & GORDER_COLLECT_LEAFLETS)) {
+        // a table: only the rows an assignment frame opened (a batch that starts inside an interval re-expands its row and
+        // appends nothing, as priming does), in runs of consecutive rows
+        for (size_t k = 0; k < replay.collect_rows.size();) {
+            size_t e = k + 1;
+            while (e < replay.collect_rows.size() && replay.collect_rows[e] == replay.collect_rows[e - 1] + 1u) e++;
+            const std::vector<uint64_t> run(replay.collect_frames.begin() + k, replay.collect_frames.begin() + e);
+            if ((st = collect_flag_rows(h, replay.collect_rows[k], run)) != GORDER_OK) return abort_batch(st);
+            k = e;
+        }
+    }
+    if ((h->collect & GORDER_COLLECT_NORMALS) && p.n_mol_total && !h->d_ntable &&
         (st = collect_normal_rows(h, frame_index, n_frames, h->extra.touched)) != GORDER_OK) return abort_batch(st);
     if (n_new_rows) {   // newest assignment becomes the carry row of the next batch
         HIP_TRY(h, hipMemcpyAsync(h->d_aflags, h->d_aflags + n_new_rows * (size_t)p.n_mol_total, p.n_mol_total,
                                   hipMemcpyDeviceToDevice, h->stream));
     }
+    if (ltable) { h->replay_have_carry = replay.have_carry; h->replay_carry_index = replay.carry_index; }
     // the batch's error key (if any) becomes the run's unless an earlier batch had one
     {
         gorder_hip_handle::BatchLog rec{h->n_submits, frame_index[0], n_frames > 1 ? frame_index[1] - frame_index[0] : 0, {}};
@@ -2060,6 +2164,7 @@ int gorder_hip_prime_leaflets(gorder_hip_handle *h, const float *d_xyz, const fl
 int gorder_hip_set_manual_leaflets(gorder_hip_handle *h, const uint8_t *flags, uint64_t frame_index) {
     if (!h || !flags) return GORDER_ERR_INVALID_ARGUMENT;
     if (h->tables.leaflets.method != GORDER_LEAFLETS_MANUAL) return GORDER_ERR_INVALID_ARGUMENT;
+    if (h->d_ltable) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_leaflets: a manual leaflet table is set");
     HIP_TRY(h, hipSetDevice(h->device));
     const uint32_t n = h->plan.n_mol_total;
     std::vector<uint8_t> tmp(n);
@@ -2126,6 +2231,7 @@ int gorder_hip_finish(gorder_hip_handle *h, int64_t *sums, uint64_t *counts, int
 
 int gorder_hip_set_normals(gorder_hip_handle *h, const float *normals, uint32_t n_frames) {
     if (!h || !normals || n_frames == 0) return GORDER_ERR_INVALID_ARGUMENT;
+    if (h->d_ntable) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_normals: a manual normal table is set");
     const size_t n = (size_t)n_frames * h->plan.n_mol_total;
     h->manual_normals.resize(4 * n);
     for (size_t i = 0; i < n; i++) {
@@ -2135,6 +2241,74 @@ int gorder_hip_set_normals(gorder_hip_handle *h, const float *normals, uint32_t 
         h->manual_normals[4 * i + 3] = 3.0f;     // "enough points": the sample kernels treat it like a computed normal
     }
     h->manual_frames = n_frames;
+    return GORDER_OK;
+}
+
+// ---- whole-trajectory manual tables ---------------------------------------------------------------------------------------
+// The only calls of the replay that wait: the new table is allocated and filled first (a failure leaves the old one in
+// place), then the stream is drained, since batches still queued may read the old table, and the old table is freed.
+int gorder_hip_set_manual_leaflet_table(gorder_hip_handle *h, const uint8_t *flags, uint64_t first_row, uint64_t n_rows) {
+    if (!h || (n_rows && !flags)) return GORDER_ERR_INVALID_ARGUMENT;
+    if (h->tables.leaflets.method != GORDER_LEAFLETS_MANUAL)
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_leaflet_table: leaflets.method is not GORDER_LEAFLETS_MANUAL");
+    const uint32_t n_mol = h->plan.n_mol_total;
+    if (n_rows && (!n_mol || !gorder::replay_window_ok(first_row, n_rows)))
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_leaflet_table: no molecules, or more than 2^32 - 1 rows");
+    HIP_TRY(h, hipSetDevice(h->device));
+    unsigned long long *nt = nullptr;
+    if (n_rows) {
+        const size_t wpr = gorder::replay_flag_words(n_mol);
+        std::vector<uint64_t> words((size_t)n_rows * wpr);
+        for (uint64_t r = 0; r < n_rows; r++) gorder::replay_pack_flags(flags + r * (size_t)n_mol, n_mol, words.data() + r * wpr);
+        if (hipMalloc((void **)&nt, words.size() * sizeof(uint64_t)) != hipSuccess) {
+            (void)hipGetLastError();         // (the handle stays usable: the error is reported here, not by the next launch)
+            return fail(h, GORDER_ERR_DEVICE, "gorder_hip_set_manual_leaflet_table: hipMalloc failed");
+        }
+        if (hipMemcpy(nt, words.data(), words.size() * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(nt);
+            return fail(h, GORDER_ERR_DEVICE, "gorder_hip_set_manual_leaflet_table: copy to the device failed");
+        }
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (h->d_ltable) (void)hipFree(h->d_ltable);
+    h->d_ltable = nt;
+    h->ltable_win.first_row = n_rows ? first_row : 0;
+    h->ltable_win.n_rows = n_rows;
+    // the row carried so far belongs to whatever supplied it: the next batch takes its first row from the new source
+    h->replay_have_carry = false;
+    h->have_assignment = false;
+    return GORDER_OK;
+}
+
+int gorder_hip_set_manual_normal_table(gorder_hip_handle *h, const float *normals, uint32_t step, uint64_t first_row, uint64_t n_rows) {
+    if (!h || (n_rows && !normals)) return GORDER_ERR_INVALID_ARGUMENT;
+    const uint32_t n_mol = h->plan.n_mol_total;
+    if (n_rows) {
+        if (step == 0) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_normal_table: step 0");
+        if (!n_mol || !gorder::replay_window_ok(first_row, n_rows))
+            return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_normal_table: no molecules, or more than 2^32 - 1 rows");
+        if (!h->plan.direct.empty()) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "manual normals: a bond spans more than the LDS window");
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    ReplayVec3 *nt = nullptr;
+    if (n_rows) {
+        const size_t bytes = (size_t)n_rows * n_mol * sizeof(ReplayVec3);
+        if (hipMalloc((void **)&nt, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, GORDER_ERR_DEVICE, "gorder_hip_set_manual_normal_table: hipMalloc failed");
+        }
+        if (hipMemcpy(nt, normals, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(nt);
+            return fail(h, GORDER_ERR_DEVICE, "gorder_hip_set_manual_normal_table: copy to the device failed");
+        }
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (h->d_ntable) (void)hipFree(h->d_ntable);
+    h->d_ntable = nt;
+    h->ntable_win.first_row = n_rows ? first_row : 0;
+    h->ntable_win.n_rows = n_rows;
+    h->ntable_step = n_rows ? step : 1;
+    h->manual_frames = 0;                    // normals handed over for "the next submit" give way to the table
     return GORDER_OK;
 }
 
@@ -2344,6 +2518,7 @@ int gorder_hip_reset(gorder_hip_handle *h) {
     h->collect_locked = false;
     h->have_assignment = false;
     h->cl_have_carry = false;
+    h->replay_have_carry = false;          // (the tables stay)
     h->assignment_frame = 0;
     h->manual_frames = 0;
     h->err_index = 0;

@@ -41,7 +41,7 @@ extern "C" {
 #endif
 
 /* ---- status codes ---------------------------------------------------------------------------
- * 1..7 mirror the AnalysisError variants the per-frame path can raise (src/errors.rs:121-141).
+ * 1..9 mirror the AnalysisError variants the per-frame path can raise (src/errors.rs:121-141).
  * >= 100 are errors of this library (no counterpart in the reference). */
 typedef enum {
     GORDER_OK = 0,
@@ -53,6 +53,9 @@ typedef enum {
     GORDER_ERR_INVALID_LOCAL_MEMBRANE_CENTER = 6,   /* ...::InvalidLocalMembraneCenter(idx)   errors.rs:143 */
     GORDER_ERR_DYNAMIC_NORMAL = 7,                  /* ...::DynamicNormalError(NotEnoughPoints(n)) errors.rs:155,
                                                        172-177; gorder_hip_last_error_index = n */
+    GORDER_ERR_MANUAL_LEAFLET_FRAME = 8,            /* ManualLeafletClassificationError::FrameNotFound: a frame of the batch has
+                                                       no row in the manual leaflet table; gorder_hip_last_error_frame */
+    GORDER_ERR_MANUAL_NORMAL_FRAME = 9,             /* ManualNormalError::FrameNotFound: the same for the manual normal table */
     GORDER_ERR_INVALID_ARGUMENT = 100,
     GORDER_ERR_DEVICE = 101,          /* a HIP runtime call failed; see gorder_hip_last_error_message */
     GORDER_ERR_NO_DEVICE = 102,       /* no gfx950 device visible: the product path has NO CPU fallback */
@@ -365,6 +368,37 @@ int gorder_hip_prime_leaflets(gorder_hip_handle *h, const float *d_xyz, const fl
  * that applies from `frame_index` on; molecules ordered molecule type major. */
 int gorder_hip_set_manual_leaflets(gorder_hip_handle *h, const uint8_t *flags, uint64_t frame_index);
 
+/* ---- whole-trajectory manual tables (`!FromFile` / `!FromMap` leaflets, leaflets.rs:815-858; manual membrane normals from a
+ * file, normal.rs:258-298) ---------------------------------------------------------------------------------------------------
+ * What gorder_hip_collected_leaflets / _normals of an earlier run (or FATSLiM, an NDX file, ...) gave, handed over ONCE for the
+ * whole trajectory: the tables are copied at the call (caller memory is not kept) and stay on the device in packed form — flags
+ * at one bit a molecule in u64 words, normals at 12 bytes a molecule.  A submit then only queues work, like every other method:
+ * k_replay_flags expands the rows a batch opens into the bytes the order kernels route by, k_replay_normals the batch's normals.
+ * gorder_hip_run_trajectory works with both (device-decoded XTC and shards included).
+ * The upload is the only call that waits for the stream.  A hipMalloc that fails is GORDER_ERR_DEVICE (the table set before stays).
+ * Row lookup, by the global frame_index of every submitted frame:
+ *   leaflets  assignment index = frame / leaflets.frequency (0 for frequency 0), leaflets.rs:835-839
+ *   normals   row = frame / step; a frame with frame % step != 0 is GORDER_ERR_INVALID_ARGUMENT (normal.rs:276-283 asserts)
+ * `first_row` lets a rank upload only its window: row r of the call is row first_row + r of the whole table.  A frame whose row
+ * is not in [first_row, first_row + n_rows) is GORDER_ERR_MANUAL_LEAFLET_FRAME / GORDER_ERR_MANUAL_NORMAL_FRAME: found on the
+ * host before the batch's first kernel is queued, the batch is refused whole (sums and frame count as before it) and
+ * gorder_hip_last_error_frame is the first frame without a row.  (A batch that continues the assignment interval the batch before
+ * ended in reads the row the handle carries and needs no row of the window.)
+ * n_rows = 0 removes the table.  Setting or removing the leaflet table forgets the carried assignment; gorder_hip_reset keeps
+ * both tables and forgets the carried row; gorder_hip_destroy frees them.  While a table is set the one-row / one-batch call
+ * of the same kind (gorder_hip_set_manual_leaflets / gorder_hip_set_normals) is GORDER_ERR_INVALID_ARGUMENT.
+ * gorder_hip_leaflets returns the most recent row.  GORDER_COLLECT_LEAFLETS: a row is collected for the frames with
+ * should_assign(frequency, frame) only — a batch that starts between two assignment frames re-expands its row and appends
+ * nothing, as priming does.  Manual normals are never collected (the reference does not store them either). */
+/* flags [n_rows][n_molecules_total], Upper=0 / Lower=1 before `flip`, molecule-type-major; needs GORDER_LEAFLETS_MANUAL. */
+int gorder_hip_set_manual_leaflet_table(gorder_hip_handle *h, const uint8_t *flags,
+                                        uint64_t first_row, uint64_t n_rows);
+/* normals [n_rows][n_molecules_total][3], any length (calc_sch normalises); row r belongs to frame (first_row + r) * step.
+ * Same precondition as gorder_hip_set_normals (no bond outside an LDS window); replaces the static / dynamic normal of every
+ * batch while it is set (the dynamic-normal kernels are not queued). */
+int gorder_hip_set_manual_normal_table(gorder_hip_handle *h, const float *normals, uint32_t step,
+                                       uint64_t first_row, uint64_t n_rows);
+
 int gorder_hip_synchronize(gorder_hip_handle *h);
 
 /* Synchronise and copy the accumulators out.  Leaves them intact (callers may keep submitting).
@@ -503,7 +537,8 @@ const char *gorder_hip_strerror(int status);
  * "k_cluster_degrees", "k_cluster_lanczos", "k_cluster_embed", "k_cluster_orient" per slab of frames; "k_local_build",
  * "k_local_rowprefix", "k_local_flags_rows", "k_local_flags_todo" per 256-frame slab; ...), "k_dyn_cov + k_dyn_eigen",
  * "k_geom_shapes", the order kernels ("k_bonds_tiled", "k_ua_extras", "k_bonds_tiled_maps", ...), "k_map_accumulate",
- * "k_bonds_direct", with collection "k_collect_flags" and "k_collect_normals" (the copy to the host included), "k_batch_end" —; *ms is the sum over all segments, i.e. the WHOLE step on the device. */
+ * "k_bonds_direct", with manual tables "k_replay_flags" and "k_replay_normals" (ahead of the order kernels), with collection
+ * "k_collect_flags" and "k_collect_normals" (the copy to the host included), "k_batch_end" —; *ms is the sum over all segments, i.e. the WHOLE step on the device. */
 int gorder_hip_kernel_time(gorder_hip_handle *h, double *ms, uint64_t *launches, int reset);
 /* Group `index` of the same measurement (in order of first appearance since the last reset): its name, the device time
  * of its segments and their number.  GORDER_ERR_INVALID_ARGUMENT past the last group.  The times of all groups add up to
