@@ -108,7 +108,8 @@ class CTrajectoryStats(C.Structure):
 
 
 class CXtcFrame(C.Structure):
-    """gorder_xtc_frame_t (include/gorder_xtc.h): one still-compressed frame for the device decoder."""
+    """gorder_xtc_frame_t (include/gorder_xtc.h): one still-compressed XTC frame, or the big-endian positions of a TRR
+    frame (kind 4: f32, 8: f64), for the device decoder."""
     _fields_ = [("offset", C.c_uint64), ("recip1", C.c_uint64), ("recip2", C.c_uint64), ("n_bytes", C.c_uint32),
                 ("kind", C.c_uint32), ("minint", C.c_int32 * 3), ("sizeint", C.c_uint32 * 3), ("smallidx", C.c_int32),
                 ("inv_precision", C.c_float), ("bitsize", C.c_uint32), ("bitsizeint", C.c_uint32)]
@@ -590,7 +591,8 @@ class HipEngine:
         """The reference's `read_trajectory` (common.rs:239-342) as one library call: read (and concatenate) the
         files, apply the time window / step, decode on `threads` host threads and analyse batch by batch with copies
         and kernels overlapped (gorder_hip_run_trajectory).  `device_decode`: the host threads only copy the compressed
-        XTC blocks, the device unpacks them (k_xtc_scan + k_xtc_chunks).  `shard` = (i, n): analyse only the i-th of n
+        XTC blocks, the device unpacks them (k_xtc_scan + k_xtc_chunks); of TRR files the positions of the analysed atoms
+        travel as they are in the file and k_trr_unpack makes the floats.  A GRO file in the run: host decoder.  `shard` = (i, n): analyse only the i-th of n
         contiguous shares of the selected frames (one rank of a multi-GPU run).  -> the pipeline's statistics."""
         arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
         grp = None if group is None else np.ascontiguousarray(group, dtype=np.uint32)
@@ -610,8 +612,9 @@ class HipEngine:
 
     def xtc_decode(self, d_blob: int, blob_bytes: int, d_frames: int, n_frames: int, n_atoms_file: int, d_slot_of: int,
                    n_stop: int, d_xyz: int, n_atoms_out: int):
-        """Decompress packed XTC frames on the device (gorder_hip_xtc_decode); all pointers are device addresses
-        (d_slot_of may be 0).  Asynchronous on the handle's stream."""
+        """Decompress packed XTC frames — and unpack packed TRR frames, also in one table — on the device
+        (gorder_hip_xtc_decode); all pointers are device addresses (d_slot_of may be 0).  The kernels are asynchronous on
+        the handle's stream; the call first reads the table's `kind` words back in that stream's order."""
         self._check(self.lib.gorder_hip_xtc_decode(self._h, d_blob, blob_bytes, d_frames, n_frames, n_atoms_file,
                                                    d_slot_of or None, n_stop, d_xyz, n_atoms_out))
 

@@ -53,6 +53,7 @@ using gorder::Tile;
 #include "kernels_cluster.h"
 #include "kernels_normals.h"
 #include "kernels_xtc.h"
+#include "kernels_trr.h"
 #include "kernels_collect.h"
 #include "kernels_replay.h"
 
@@ -2641,32 +2642,54 @@ int gorder_hip_kernel_time_group(gorder_hip_handle *h, uint32_t index, const cha
 size_t xtc_checkpoints(uint32_t n_frames, uint32_t n_stop) {
     return (size_t)n_frames * ((std::max(n_stop, 1u) + kXtcChunk - 1u) / kXtcChunk + 1u);
 }
+// `kinds`: what the table holds — kXtcTableXtc: frames for k_xtc_scan / k_xtc_chunks, kXtcTableTrr: frames for k_trr_unpack
+// (each kernel passes over the frames of the other kind); a kind the table does not hold queues nothing
+enum : uint32_t { kXtcTableXtc = 1u, kXtcTableTrr = 2u };
+uint32_t xtc_table_kinds(const gorder_xtc_frame_t *frames, uint32_t n_frames) {
+    uint32_t kinds = 0;
+    for (uint32_t k = 0; k < n_frames; k++) kinds |= (frames[k].kind & (kTrrKindF32 | kTrrKindF64)) ? kXtcTableTrr : kXtcTableXtc;
+    return kinds;
+}
 int xtc_decode_on(gorder_hip_handle *h, hipStream_t stream, const uint8_t *d_blob, uint64_t blob_bytes,
                   const gorder_xtc_frame_t *d_frames, uint32_t n_frames, uint32_t n_atoms_file, const int32_t *d_slot_of,
-                  uint32_t n_stop, float *d_xyz, uint32_t n_atoms_out, uint32_t *d_stat = nullptr, uint32_t *d_short = nullptr,
-                  uint32_t *d_err_key = nullptr, XtcCheckpoint *d_cp = nullptr) {
+                  uint32_t n_stop, float *d_xyz, uint32_t n_atoms_out, uint32_t kinds, uint32_t *d_stat = nullptr,
+                  uint32_t *d_short = nullptr, uint32_t *d_err_key = nullptr, XtcCheckpoint *d_cp = nullptr) {
     if (!h || !d_blob || !d_frames || !d_xyz || blob_bytes < 64 || (reinterpret_cast<uintptr_t>(d_blob) & 63u) != 0 || n_atoms_file == 0 || n_atoms_out == 0 ||
         n_stop > n_atoms_file || (!d_slot_of && n_atoms_out < n_stop))
         return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_xtc_decode: bad arguments");
     if (n_frames == 0) return GORDER_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    // two kernels (kernels_xtc.h): where the chunks of ~kXtcChunk atoms start in every frame's stream (one lane per
-    // frame, no decoding), then the chunks (one lane per frame and chunk).  The checkpoints between them live in the
-    // caller's buffer (a slot of gorder_hip_run_trajectory has its own: several batches decode at once) or the handle's.
-    const uint32_t n_chunks = (std::max(n_stop, 1u) + kXtcChunk - 1u) / kXtcChunk;
-    if (!d_cp) {
-        const int st = ensure(h, &h->d_xtc_cp, &h->xtc_cp_cap, xtc_checkpoints(n_frames, n_stop));
-        if (st != GORDER_OK) return st;
-        d_cp = h->d_xtc_cp;
+    if (kinds & kXtcTableXtc) {
+        // two kernels (kernels_xtc.h): where the chunks of ~kXtcChunk atoms start in every frame's stream (one lane per
+        // frame, no decoding), then the chunks (one lane per frame and chunk).  The checkpoints between them live in the
+        // caller's buffer (a slot of gorder_hip_run_trajectory has its own: several batches decode at once) or the handle's.
+        const uint32_t n_chunks = (std::max(n_stop, 1u) + kXtcChunk - 1u) / kXtcChunk;
+        if (!d_cp) {
+            const int st = ensure(h, &h->d_xtc_cp, &h->xtc_cp_cap, xtc_checkpoints(n_frames, n_stop));
+            if (st != GORDER_OK) return st;
+            d_cp = h->d_xtc_cp;
+        }
+        hipLaunchKernelGGL(k_xtc_scan, dim3((n_frames + 3u) / 4u), dim3(256), 0, stream, d_blob, (unsigned long long)blob_bytes,
+                           d_frames, n_frames, n_atoms_file, d_slot_of, n_stop, d_xyz, n_atoms_out,
+                           d_err_key ? d_err_key : h->d_err, d_stat, d_short, d_cp, n_chunks);
+        const unsigned long long items = (unsigned long long)n_frames * n_chunks;
+        if (items + 63ull > 64ull * 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_xtc_decode: batch too large");
+        hipLaunchKernelGGL(k_xtc_chunks, dim3((uint32_t)((items + 63ull) / 64ull)), dim3(64), 0, stream, d_blob,
+                           (unsigned long long)blob_bytes, d_frames, n_frames, n_atoms_file, d_slot_of, n_stop, d_xyz, n_atoms_out,
+                           d_cp, n_chunks);
     }
-    hipLaunchKernelGGL(k_xtc_scan, dim3((n_frames + 3u) / 4u), dim3(256), 0, stream, d_blob, (unsigned long long)blob_bytes,
-                       d_frames, n_frames, n_atoms_file, d_slot_of, n_stop, d_xyz, n_atoms_out,
-                       d_err_key ? d_err_key : h->d_err, d_stat, d_short, d_cp, n_chunks);
-    const unsigned long long items = (unsigned long long)n_frames * n_chunks;
-    if (items + 63ull > 64ull * 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_xtc_decode: batch too large");
-    hipLaunchKernelGGL(k_xtc_chunks, dim3((uint32_t)((items + 63ull) / 64ull)), dim3(64), 0, stream, d_blob,
-                       (unsigned long long)blob_bytes, d_frames, n_frames, n_atoms_file, d_slot_of, n_stop, d_xyz, n_atoms_out,
-                       d_cp, n_chunks);
+    if (kinds & kXtcTableTrr) {
+        // one kernel (kernels_trr.h): a thread per four floats of a frame's stream (per atom with a slot table), the frames
+        // along the grid's second axis; timed as a group of its own where it runs on the handle's stream
+        const unsigned long long items = d_slot_of ? std::max(n_stop, 1u) : (3ull * n_stop) / 4ull + 1ull;
+        const uint32_t pieces = (uint32_t)std::min<unsigned long long>((items + kTrrBlock - 1u) / kTrrBlock, 0x7fffffffull);
+        const bool timed = stream == h->stream;
+        if (timed) TIMING_MARK(h, "k_trr_unpack");
+        hipLaunchKernelGGL(k_trr_unpack, dim3(pieces, std::min(n_frames, 65535u)), dim3(kTrrBlock), 0, stream, d_blob,
+                           (unsigned long long)blob_bytes, d_frames, n_frames, n_atoms_file, d_slot_of, n_stop, d_xyz, n_atoms_out,
+                           d_err_key ? d_err_key : h->d_err);
+        if (timed) TIMING_MARK(h, nullptr);
+    }
     HIP_TRY(h, hipGetLastError());
     return GORDER_OK;
 }
@@ -2674,8 +2697,20 @@ int gorder_hip_xtc_decode(gorder_hip_handle *h, const uint8_t *d_blob, uint64_t 
                           const gorder_xtc_frame_t *d_frames, uint32_t n_frames, uint32_t n_atoms_file,
                           const int32_t *d_slot_of, uint32_t n_stop, float *d_xyz, uint32_t n_atoms_out) {
     if (!h) return GORDER_ERR_INVALID_ARGUMENT;
+    if (!d_frames) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_xtc_decode: bad arguments");
+    // which kernels the table needs: its `kind` words, read back in the order of the handle's stream (the table is the
+    // caller's, on the device) — the call waits for what the stream holds so far, the kernels themselves are asynchronous
+    HIP_TRY(h, hipSetDevice(h->device));
+    std::vector<uint32_t> kind(n_frames);
+    if (n_frames) {
+        HIP_TRY(h, hipMemcpy2DAsync(kind.data(), sizeof(uint32_t), reinterpret_cast<const uint8_t *>(d_frames) + offsetof(gorder_xtc_frame_t, kind),
+                                    sizeof(gorder_xtc_frame_t), sizeof(uint32_t), n_frames, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    uint32_t kinds = 0;
+    for (uint32_t k : kind) kinds |= (k & (kTrrKindF32 | kTrrKindF64)) ? kXtcTableTrr : kXtcTableXtc;
     return xtc_decode_on(h, h->stream, d_blob, blob_bytes, d_frames, n_frames, n_atoms_file, d_slot_of, n_stop, d_xyz,
-                         n_atoms_out);
+                         n_atoms_out, kinds);
 }
 
 }  // extern "C"

@@ -194,6 +194,10 @@ __global__ __launch_bounds__(256) void k_xtc_scan(const uint8_t *__restrict__ bl
     const uint32_t last_byte = bad ? 62u : (uint32_t)(region > 0xfffffffeull ? 0xfffffffeull : region) - 2u;   // two bytes are read at a time
     XtcCheckpoint *mycp = cp + (size_t)fr * (n_chunks + 1u);
 
+    if (d.kind & 12u) {      // a TRR frame of a mixed table (bits 2 / 3 of kind): k_trr_unpack's; the chunks are empty
+        for (uint32_t c = lane; c <= n_chunks; c += 64u) mycp[c] = XtcCheckpoint{0ull, n_stop, (uint32_t)kXtcFirstIdx};
+        return;
+    }
     if (natoms <= 9u) {      // uncompressed small systems: big-endian floats, written here; the chunks are empty
         float *o = out + (size_t)fr * n_out * 3u;
         for (uint32_t t = lane; t < n_stop; t += 64u) {

@@ -12,7 +12,11 @@
 // that read it have completed (the copy stream waits for that event) — no stream-wide synchronisation anywhere.
 // With gorder_trajectory_t::device_decode the host threads only COPY the compressed blocks (gorder_xtc_pack_window),
 // the slot's own stream carries blob + frame table + boxes to the device and runs the decoder (k_xtc_scan + k_xtc_chunks)
-// into the slot's coordinate buffer; the handle's stream waits for that kernel instead of for a copy.
+// into the slot's coordinate buffer; the handle's stream waits for that kernel instead of for a copy.  TRR files take the
+// same route: the leading atoms of their positions blocks travel as they are in the file and k_trr_unpack makes the floats.
+// Measured against the host route on V-AA files (tools/trr_bench.py, profiles/trr_bench.json: single and double precision,
+// bare and in front of three times as many solvent atoms): 1.6 to 2.6 times the host route's frames/s, double precision
+// with nothing to leave behind — twice the bytes on the link — included; no case is kept from the device route.
 #pragma once
 
 #include <atomic>
@@ -40,6 +44,7 @@ struct TrajSlot {
     std::vector<int64_t> file_pos;
     std::vector<uint32_t> file_idx;
     uint32_t prefix_q16 = 65536;    // the part of every block this batch was packed with
+    uint32_t kinds = 0;             // what the batch's table holds (kXtcTableXtc | kXtcTableTrr)
     size_t moved = 0;               // bytes copied to the device for this batch
     uint64_t blob_bytes = 0;
     hipStream_t stream = nullptr;
@@ -54,7 +59,7 @@ struct TrajSlot {
 struct TrajCache {
     static constexpr int kSlots = 4;     // the host-decode route uses three of them
     TrajSlot slot[kSlots];
-    bool dev = false;
+    bool dev = false, has_xtc = false;
     uint32_t batch = 0, n_stop = 0;
     size_t blob_cap = 0, xyz_bytes = 0;
     hipStream_t copy_stream = nullptr;
@@ -128,21 +133,32 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
     const uint32_t n_atoms = h->plan.n_atoms;
     // (0: the machine's threads, at most 16 — the copies and the decoder saturate there, and a node runs one rank per GPU)
     uint32_t n_threads = tr->n_threads ? tr->n_threads : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-    // device decode: every file must be XTC (TRR / GRO have nothing to decompress); the atoms per frame of the
-    // first file size the blob
+    // device decode: every file must be XTC or TRR (GRO is text), with the same atoms per frame; the files may mix the
+    // two formats
     bool dev = tr->device_decode != 0;
+    bool has_xtc = false;
     uint32_t n_file_atoms = 0, n_stop = 0, first_frame_bytes = 0;
+    uint32_t trr_real_size = 0;          // the widest real of the run's TRR files (0: none), for the blob's size
+    std::vector<uint8_t> file_is_xtc(tr->n_paths, 0);
     uint64_t total_file_bytes = 0;
     std::vector<int32_t> slot_of;
     for (uint32_t f = 0; dev && f < tr->n_paths; f++) {
         uint32_t na = 0, first = 0;
         uint64_t fbytes = 0;
-        if (gorder_xtc_probe(tr->paths[f], &na, &fbytes, &first) != 1) { dev = false; break; }     // (an unreadable file: the reader thread reports it)
+        int format = GORDER_XTC_FORMAT_OTHER;
+        if (gorder_xtc_probe_format(tr->paths[f], &format, &na, &fbytes, &first) != GORDER_XTC_OK || format == GORDER_XTC_FORMAT_OTHER ||
+            na == 0) { dev = false; break; }     // (an unreadable file: the reader thread reports it)
         total_file_bytes += fbytes;
+        file_is_xtc[f] = format == GORDER_XTC_FORMAT_XTC;
+        if (format == GORDER_XTC_FORMAT_XTC) has_xtc = true;
+        // header + positions of the first frame: 12 bytes per atom and about a hundred in single precision, 24 in double
+        // (a file of a few atoms may be taken for double: its blob is then a few bytes larger than it need be)
+        else trr_real_size = std::max(trr_real_size, first / 3u / na >= 8u ? 8u : 4u);
         if (f == 0) first_frame_bytes = first;
         if (f == 0) n_file_atoms = na;
         else if (na != n_file_atoms) dev = false;
     }
+    if (!dev) has_xtc = false;
     if (dev) {
         n_stop = n_file_atoms;
         if (tr->group && tr->n_group) {
@@ -163,6 +179,11 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
             slot_of[tr->group[k]] = (int32_t)k;
         }
         if (!dev) slot_of.clear();
+        // the leading atoms of the file in their order, in a run of TRR files alone: k_trr_unpack then takes a frame as one
+        // flat stream (16-byte loads and stores) and needs no table
+        bool leading = dev && !has_xtc;
+        for (uint32_t k = 0; k < tr->n_group && leading; k++) leading = tr->group[k] == k;
+        if (leading) slot_of.clear();
     }
     // contiguous frame shards: count what the window selects, headers only, and take this rank's share
     uint64_t shard_lo = 0, shard_n = UINT64_MAX, shard_total = 0;
@@ -234,10 +255,12 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
         // frames per launch the host's decoder threads are faster.  Large systems get a larger budget (4 GiB of
         // coordinates per slot; HBM has the room), and beyond that (about a million atoms per frame) the run uses
         // the host decoder.
+        // That rule is k_xtc_scan's (it walks a frame serially): a run of TRR files alone unpacks a frame with as many
+        // threads as it has reals and keeps the device route with however many frames fit, at least one.
         size_t b = std::min<size_t>(16384, ((size_t)1 << 30) / ((size_t)n_atoms * 12u));
         if (b < 512) b = std::min<size_t>(512, ((size_t)4 << 30) / ((size_t)n_atoms * 12u));
-        if (b < 512) dev = false;
-        else batch = (uint32_t)b;
+        if (b < 512 && has_xtc) dev = has_xtc = false;
+        else batch = (uint32_t)std::max<size_t>(b, 1);
         // A short trajectory does not need (and should not pay for pinning) four full-size slots: about a third of its
         // frames per batch, estimated from the files' sizes and the first frame's
         if (dev && first_frame_bytes) {
@@ -251,10 +274,14 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
     // and room for one worst-case frame
     // (a file with much more in it than the analysed atoms — water — would ask for gigabytes: at most 1 GiB per slot,
     // a batch then simply ends when its blob is full)
-    const size_t blob_cap = dev ? std::max<size_t>(std::min<size_t>((size_t)batch * n_file_atoms * 6u, (size_t)1 << 30),
-                                                   (size_t)n_file_atoms * 12u + 4096u) + 4096u : 0;
+    // A TRR frame's share is known exactly: the leading n_stop atoms of its positions block, in whole 64-byte pieces and
+    // one piece of zeros.  A run that mixes the formats takes the larger of the two per frame.
+    const size_t trr_frame = trr_real_size ? ((((size_t)n_stop * 3u * trr_real_size) + 63u) & ~(size_t)63u) + 64u : 0;
+    const size_t per_frame = std::max<size_t>(has_xtc ? (size_t)n_file_atoms * 6u : 0, trr_frame);
+    const size_t one_frame = std::max<size_t>(has_xtc ? (size_t)n_file_atoms * 12u + 4096u : 0, trr_frame);
+    const size_t blob_cap = dev ? std::max<size_t>(std::min<size_t>((size_t)batch * per_frame, (size_t)1 << 30), one_frame) + 4096u : 0;
     TrajCache *cache = static_cast<TrajCache *>(h->traj_cache);
-    if (cache && !(cache->dev == dev && cache->batch == batch && cache->blob_cap == blob_cap && cache->xyz_bytes == xyz_bytes &&
+    if (cache && !(cache->dev == dev && cache->has_xtc == has_xtc && cache->batch == batch && cache->blob_cap == blob_cap && cache->xyz_bytes == xyz_bytes &&
                    cache->n_stop == n_stop)) {
         traj_cache_free(h);            // another shape of run: start over
         cache = nullptr;
@@ -262,7 +289,7 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
     if (!cache) {
         cache = new (std::nothrow) TrajCache();
         if (!cache) return fail(h, GORDER_ERR_DEVICE, "out of host memory");
-        cache->dev = dev; cache->batch = batch; cache->blob_cap = blob_cap; cache->xyz_bytes = xyz_bytes; cache->n_stop = n_stop;
+        cache->dev = dev; cache->has_xtc = has_xtc; cache->batch = batch; cache->blob_cap = blob_cap; cache->xyz_bytes = xyz_bytes; cache->n_stop = n_stop;
         h->traj_cache = cache;
         h->traj_cache_free = &traj_cache_free;
     }
@@ -303,7 +330,7 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
             ok(hipMalloc((void **)&s.d_box_in, box_bytes));
             ok(hipMalloc((void **)&s.d_stat, 4 * sizeof(uint32_t)));      // [0..1] the decoder's report, [2..3] its error key
             ok(hipMalloc((void **)&s.d_short, (size_t)batch * sizeof(uint32_t)));
-            ok(hipMalloc((void **)&s.d_cp, xtc_checkpoints(batch, n_stop) * sizeof(XtcCheckpoint)));
+            if (has_xtc) ok(hipMalloc((void **)&s.d_cp, xtc_checkpoints(batch, n_stop) * sizeof(XtcCheckpoint)));
             ok(hipHostMalloc((void **)&s.h_stat, 2 * sizeof(uint32_t), hipHostMallocDefault));
             ok(hipHostMalloc((void **)&s.h_short, (size_t)batch * sizeof(uint32_t), hipHostMallocDefault));
             s.file_pos.resize(batch);
@@ -354,11 +381,12 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
     gorder_xtc_pool *pool = nullptr;
     if (dev && gorder_xtc_pool_create(n_threads, &pool) != GORDER_XTC_OK) pool = nullptr;
     const char *forced_prefix = getenv("GORDER_HIP_PREFIX_Q16");          // test switch: a fixed part, whatever it leads to
-    const bool adapt_prefix = dev && !forced_prefix && !env_flag("GORDER_HIP_NO_PREFIX") && n_stop < n_file_atoms;
+    // (XTC frames only: of a TRR frame exactly the analysed part travels, there is nothing to learn and no SHORT frame)
+    const bool adapt_prefix = dev && has_xtc && !forced_prefix && !env_flag("GORDER_HIP_NO_PREFIX") && n_stop < n_file_atoms;
     if (dev && forced_prefix) pipe.prefix_q16.store((uint32_t)std::max(1l, std::min(65536l, atol(forced_prefix))));
     // only a run that copies parts of blocks has anything to look at between the two stages; any other queues stage B
     // right behind stage A and never waits for the device
-    const bool verify = dev && (adapt_prefix || forced_prefix);
+    const bool verify = dev && has_xtc && (adapt_prefix || forced_prefix);
     // ---- reader thread: the sequential part of read_trajectory (time window, step, concatenation) + decoding
     const int device = h->device;
     std::thread reader([&, device]() {
@@ -368,7 +396,7 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
         uint32_t f = 0;                       // next file to open
         gorder_xtc_reader *r = nullptr;       // the open one
         bool done = shard_n == 0;
-        uint32_t n_filled = 0;                // batches this thread has started to fill
+        uint32_t n_filled = 0;                // batches with XTC frames in them this thread has filled
         uint64_t to_skip = shard_lo, left = shard_n;      // frames before this rank's shard; frames of it still to read
         auto give_up = [&](int st, const std::string &msg) {
             std::lock_guard<std::mutex> lk(pipe.mu);
@@ -401,8 +429,10 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
             // A run that will copy only parts of blocks learns the part from the decoder's first report: its first
             // two batches are short (256 and 1024 frames) and the third waits for that report, so that no more than
             // ~1 300 frames travel whole.
+            // (Batches of XTC frames, that is: TRR frames travel exactly as far as they are needed and report nothing, so
+            // a batch that starts in a TRR file is a full one and does not count.)
             uint32_t fill = batch;
-            if (adapt_prefix && tr->batch_frames == 0) {
+            if (adapt_prefix && tr->batch_frames == 0 && f < tr->n_paths && file_is_xtc[f]) {
                 if (n_filled == 0) fill = std::min(batch, 256u);
                 else if (n_filled == 1) fill = std::min(batch, 1024u);
                 else if (n_filled == 2) {
@@ -410,7 +440,6 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
                     pipe.cv.wait(lk, [&] { return pipe.stop || pipe.reports > 0; });
                 }
             }
-            n_filled++;
             s.prefix_q16 = pipe.prefix_q16.load();
             while (!done && s.n < fill) {
                 if (left == 0) { done = true; break; }
@@ -482,6 +511,7 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
                 pipe.free_q.push_front(k);
                 break;
             }
+            if (dev && (xtc_table_kinds(s.h_frames, s.n) & kXtcTableXtc)) n_filled++;
             s.fidx.resize((size_t)s.n);
             // SystemTopology::frame of the k-th analysed frame = k * step (topology/mod.rs:141-144)
             for (uint32_t q = 0; q < s.n; q++) s.fidx[q] = tr->first_frame_index + (analysed + q) * tr->step;
@@ -526,9 +556,10 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
             if (e == hipSuccess) e = hipEventRecord(s.staged, feed);
             if (e == hipSuccess && s.compute_issued) e = hipStreamWaitEvent(feed, s.computed, 0);
             if (e == hipSuccess) e = hipMemcpyAsync(s.d_box, s.d_box_in, nb, hipMemcpyDeviceToDevice, feed);
+            s.kinds = xtc_table_kinds(s.h_frames, s.n);
             if (e == hipSuccess && status == GORDER_OK)
                 status = xtc_decode_on(h, feed, s.d_blob, s.blob_bytes, s.d_frames, s.n, n_file_atoms, d_slot_of, n_stop,
-                                       s.d_xyz, n_atoms, s.d_stat, s.d_short, s.d_stat + 2, s.d_cp);
+                                       s.d_xyz, n_atoms, s.kinds, s.d_stat, s.d_short, s.d_stat + 2, s.d_cp);
             if (e == hipSuccess) e = hipMemcpyAsync(s.h_stat, s.d_stat, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, feed);
             if (e == hipSuccess) e = hipMemcpyAsync(s.h_short, s.d_short, (size_t)s.n * sizeof(uint32_t), hipMemcpyDeviceToHost, feed);
         } else {
@@ -575,7 +606,8 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
             if (e == hipSuccess) {
                 const uint32_t n_short = s.h_stat[0], q = s.h_stat[1];
                 if (n_short) fix_short_frames(s, std::min(n_short, s.n));
-                if (adapt_prefix) {
+                // (a batch of TRR frames alone reports nothing — k_xtc_scan did not run for it — and teaches nothing)
+                if (adapt_prefix && (s.kinds & kXtcTableXtc)) {
                     // what this batch needed, as a part of the whole block; the next batches get an eighth and 1 % more
                     // (nothing less than nine tenths is worth the trouble), and more at once when frames came out short
                     need_q16 = std::max<uint32_t>(need_q16, (uint32_t)std::min<uint64_t>(65536u, ((uint64_t)q * s.prefix_q16) >> 16));
@@ -584,7 +616,7 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
                     pipe.prefix_q16.store(next >= 58982u ? 65536u : next);
                 }
                 std::lock_guard<std::mutex> lk(pipe.mu);
-                pipe.reports++;
+                if (s.kinds & kXtcTableXtc) pipe.reports++;          // (what the reader's third XTC batch waits for)
                 pipe.cv.notify_all();
             }
         }

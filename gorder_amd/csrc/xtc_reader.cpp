@@ -319,19 +319,16 @@ struct TrrHeader {
     double t;
 };
 
-int trr_read_header(gorder_xtc_reader *r, TrrHeader &h) {
-    uint8_t b[8];
-    const size_t got = fread(b, 1, 8, r->fp);
+// The header out of `got` bytes that start at a frame (the ONE place that knows its layout: the FILE reader below, and
+// gorder_xtc_pack_window* and gorder_xtc_probe_format, which move no FILE).  kTrrHeadMax bytes hold the longest header
+// accepted.  *len = bytes of the header.
+constexpr size_t kTrrHeadMax = 12 + 128 + 52 + 16;
+int trr_parse_header(const uint8_t *b, size_t got, TrrHeader &h, size_t *len) {
     if (got == 0) return GORDER_XTC_EOF;
-    if (got != 8 || be32(b) != 1993u) return GORDER_XTC_ERR_FORMAT;
-    const uint32_t slen = be32(b + 4);                       // length of the version string incl. terminator
-    uint8_t s4[4];
-    if (slen > 128 || !read_exact(r->fp, s4, 4)) return GORDER_XTC_ERR_FORMAT;
-    const uint32_t n = be32(s4), padded = (n + 3u) & ~3u;
-    uint8_t str[132];
-    if (n > 128 || !read_exact(r->fp, str, padded)) return GORDER_XTC_ERR_FORMAT;
-    uint8_t ints[13 * 4];
-    if (!read_exact(r->fp, ints, sizeof(ints))) return GORDER_XTC_ERR_FORMAT;
+    if (got < 12 || be32(b) != 1993u || be32(b + 4) > 128u) return GORDER_XTC_ERR_FORMAT;
+    const uint32_t n = be32(b + 8), padded = (n + 3u) & ~3u;
+    if (n > 128 || got < 12 + (size_t)padded + 52) return GORDER_XTC_ERR_FORMAT;
+    const uint8_t *ints = b + 12 + padded;
     for (int k = 0; k < 10; k++) h.sizes[k] = be32(ints + 4 * k);
     h.natoms = be32(ints + 40);
     h.step = (int32_t)be32(ints + 44);
@@ -341,10 +338,22 @@ int trr_read_header(gorder_xtc_reader *r, TrrHeader &h) {
     else if (h.sizes[9] && h.natoms) h.real_size = h.sizes[9] / (3u * h.natoms);
     else h.real_size = 4;
     if (h.real_size != 4 && h.real_size != 8) return GORDER_XTC_ERR_FORMAT;
-    uint8_t tl[16];
-    if (!read_exact(r->fp, tl, 2 * h.real_size)) return GORDER_XTC_ERR_FORMAT;
+    const uint8_t *tl = ints + 52;
+    if (got < 12 + (size_t)padded + 52 + 2 * (size_t)h.real_size) return GORDER_XTC_ERR_FORMAT;
     h.t = h.real_size == 4 ? (double)bef(tl) : bed(tl);
+    *len = 12 + (size_t)padded + 52 + 2 * (size_t)h.real_size;
     return GORDER_XTC_OK;
+}
+
+// the header at the FILE's position; leaves the FILE behind it
+int trr_read_header(gorder_xtc_reader *r, TrrHeader &h) {
+    const off_t pos = ftello(r->fp);
+    uint8_t b[kTrrHeadMax];
+    const size_t got = fread(b, 1, sizeof(b), r->fp);
+    size_t len = 0;
+    const int st = trr_parse_header(b, got, h, &len);
+    if (st != GORDER_XTC_OK) return st;
+    return fseeko(r->fp, pos + (off_t)len, SEEK_SET) == 0 ? GORDER_XTC_OK : GORDER_XTC_ERR_FORMAT;
 }
 
 int trr_next(gorder_xtc_reader *r, float *xyz, float *box9, int64_t *step, float *time_ps, float *precision) {
@@ -998,7 +1007,41 @@ int gorder_xtc_probe(const char *path, uint32_t *n_atoms, uint64_t *file_bytes, 
     }
     return 1;
 }
+int gorder_xtc_probe_format(const char *path, int *format, uint32_t *n_atoms, uint64_t *file_bytes, uint32_t *first_frame_bytes) {
+    if (!path || !format) return GORDER_XTC_ERR_ARGUMENT;
+    *format = GORDER_XTC_FORMAT_OTHER;
+    if (n_atoms) *n_atoms = 0;
+    if (first_frame_bytes) *first_frame_bytes = 0;
+    const int xtc = gorder_xtc_probe(path, n_atoms, file_bytes, first_frame_bytes);
+    if (xtc < 0) return xtc;
+    if (xtc == 1) { *format = GORDER_XTC_FORMAT_XTC; return GORDER_XTC_OK; }
+    FILE *fp = fopen(path, "rb");
+    if (!fp) return GORDER_XTC_ERR_OPEN;
+    // TRR: the headers up to the first frame that has positions (a file that is not TRR fails at its first bytes)
+    off_t pos = 0;
+    for (bool first = true;; first = false) {
+        uint8_t th[kTrrHeadMax];
+        TrrHeader h{};
+        size_t hlen = 0;
+        const size_t got = fseeko(fp, pos, SEEK_SET) == 0 ? fread(th, 1, sizeof(th), fp) : 0;
+        if (trr_parse_header(th, got, h, &hlen) != GORDER_XTC_OK) break;      // (with no frame that has positions: 0 bytes)
+        if (first) {
+            *format = GORDER_XTC_FORMAT_TRR;
+            if (n_atoms) *n_atoms = h.natoms;
+        }
+        uint64_t body = 0;
+        for (int k = 0; k < 10; k++) body += h.sizes[k];
+        if (h.sizes[7]) {
+            if (first_frame_bytes) *first_frame_bytes = (uint32_t)std::min<uint64_t>(hlen + (uint64_t)h.sizes[7], UINT32_MAX);
+            break;
+        }
+        pos += (off_t)(hlen + body);
+    }
+    fclose(fp);
+    return GORDER_XTC_OK;
+}
 int gorder_xtc_is_xtc(const gorder_xtc_reader *r) { return (r && !r->trr && !r->gro) ? 1 : 0; }
+int gorder_xtc_can_pack(const gorder_xtc_reader *r) { return (r && !r->gro) ? 1 : 0; }
 uint32_t gorder_xtc_n_atoms_needed(const gorder_xtc_reader *r) {
     return r ? (r->n_needed ? std::min(r->n_needed, r->natoms) : r->natoms) : 0;
 }
@@ -1054,7 +1097,7 @@ int64_t pack_window_impl(gorder_xtc_reader *r, float begin_ps, float end_ps, uin
                          double *last_time, uint8_t *blob, uint64_t blob_capacity, uint64_t *blob_bytes,
                          gorder_xtc_frame_t *frames, float *box9, float *time_ps, uint64_t capacity,
                          uint32_t n_threads, gorder_xtc_pool *pool, uint32_t prefix_q16 = 65536u, int64_t *file_pos = nullptr) {
-    if (!r || !r->fp || r->trr || r->gro || !state || !last_time || !blob || !blob_bytes || !frames || !box9 || step == 0)
+    if (!r || !r->fp || r->gro || !state || !last_time || !blob || !blob_bytes || !frames || !box9 || step == 0)
         return GORDER_XTC_ERR_ARGUMENT;
     *blob_bytes = 0;
     const auto t_scan0 = std::chrono::steady_clock::now();
@@ -1088,61 +1131,97 @@ int64_t pack_window_impl(gorder_xtc_reader *r, float begin_ps, float end_ps, uin
     // trajectories another process rewrites, or on file systems that return I/O errors late, set GORDER_XTC_PREAD=1.)
     if (r->map && (getenv("GORDER_XTC_PREAD") || (file_end >= 0 && (size_t)file_end < r->map->size))) r->map.reset();
     const FileMap *map = r->map.get();
+    // `n` bytes of the file at `at`: out of the mapping where it covers them (no system call per frame), else — the last
+    // bytes of the mapping, or behind it (the file has grown) — the file itself decides
+    auto fetch = [&](off_t at, uint8_t *dst, size_t n) -> ssize_t {
+        if (map && map->base && at >= 0 && (size_t)at + n <= map->size) {
+            memcpy(dst, map->base + at, n);
+            return (ssize_t)n;
+        }
+        return pread(fd, dst, n, at);
+    };
+    const uint32_t n_stop = gorder_xtc_n_atoms_needed(r);
     while (src.size() < capacity) {
         const off_t pos0 = pos;
         uint8_t head[56 + 36];
-        ssize_t got;
-        if (map && map->base && pos0 >= 0 && (size_t)pos0 + sizeof(head) <= map->size) {      // (no system call per frame)
-            got = (ssize_t)sizeof(head);
-            memcpy(head, map->base + pos0, sizeof(head));
-        } else {            // the last bytes of the mapping, or behind it (the file has grown): the file itself decides
-            got = pread(fd, head, sizeof(head), pos0);
-        }
-        if (got == 0) break;
-        if (got < 56 || be32(head) != 1995u || be32(head + 4) != natoms || be32(head + 52) != natoms)
-            return GORDER_XTC_ERR_FORMAT;
-        const float t = bef(head + 12);
+        float t;
+        float trr_box[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         gorder_xtc_frame_t fr{};
         uint32_t block = 0;       // bytes of the coordinate block in the file
+        uint32_t copy = 0;        // bytes of it that travel
         off_t pos_block;
-        if (natoms <= 9) {
-            fr.kind = 1;
-            fr.n_bytes = block = natoms * 12u;
-            pos_block = pos0 + 56;
+        if (r->trr) {
+            // A TRR frame (trr_next's rules): the uncompressed positions block, of which the leading n_stop atoms travel —
+            // exactly what the device needs, known before reading: there is no part to learn and no SHORT frame.
+            uint8_t th[kTrrHeadMax];
+            const ssize_t got = fetch(pos0, th, sizeof(th));
+            if (got < 0) return GORDER_XTC_ERR_FORMAT;
+            TrrHeader h{};
+            size_t hlen = 0;
+            const int st = trr_parse_header(th, (size_t)got, h, &hlen);
+            if (st == GORDER_XTC_EOF) break;
+            if (st != GORDER_XTC_OK || h.natoms != natoms) return GORDER_XTC_ERR_FORMAT;
+            const off_t before_x = (off_t)hlen + (off_t)h.sizes[0] + h.sizes[1] + h.sizes[2] + h.sizes[3] + h.sizes[4] + h.sizes[5] + h.sizes[6];
+            pos = pos0 + before_x + (off_t)h.sizes[7] + h.sizes[8] + h.sizes[9];
+            if (h.sizes[7] == 0) continue;                 // velocities / forces only: not a frame
+            if (h.sizes[7] != (uint64_t)natoms * 3u * h.real_size) return GORDER_XTC_ERR_FORMAT;
+            pos_block = pos0 + before_x;
+            block = h.sizes[7];
+            if (file_end >= 0 && pos_block + (off_t)block > file_end) return GORDER_XTC_ERR_FORMAT;     // cut inside the positions
+            if (h.sizes[2]) {
+                uint8_t b[72];
+                if (h.sizes[2] > sizeof(b) || fetch(pos0 + (off_t)hlen + h.sizes[0] + h.sizes[1], b, h.sizes[2]) != (ssize_t)h.sizes[2])
+                    return GORDER_XTC_ERR_FORMAT;
+                for (int q = 0; q < 9; q++) trr_box[q] = h.real_size == 4 ? bef(b + 4 * q) : (float)bed(b + 8 * q);
+            }
+            t = (float)h.t;
+            fr.kind = h.real_size == 4 ? 4u : 8u;
+            fr.n_bytes = copy = n_stop * 3u * h.real_size;
         } else {
-            if (got != (ssize_t)sizeof(head)) return GORDER_XTC_ERR_FORMAT;
-            const uint8_t *h2 = head + 56;
-            for (int k = 0; k < 3; k++) {
-                const int minint = (int32_t)be32(h2 + 4 + 4 * k), maxint = (int32_t)be32(h2 + 16 + 4 * k);
-                const int64_t sz = (int64_t)maxint - (int64_t)minint + 1;
-                if (sz <= 0 || sz > 0xffffffffll) return GORDER_XTC_ERR_FORMAT;
-                fr.minint[k] = minint;
-                fr.sizeint[k] = (uint32_t)sz;
-            }
-            if ((fr.sizeint[0] | fr.sizeint[1] | fr.sizeint[2]) > 0xffffff) {
-                fr.bitsize = 0;
-                for (int k = 0; k < 3; k++) fr.bitsizeint |= (uint32_t)size_of_int(fr.sizeint[k]) << (8 * k);
+            ssize_t got = fetch(pos0, head, sizeof(head));
+            if (got == 0) break;
+            if (got < 56 || be32(head) != 1995u || be32(head + 4) != natoms || be32(head + 52) != natoms)
+                return GORDER_XTC_ERR_FORMAT;
+            t = bef(head + 12);
+            if (natoms <= 9) {
+                fr.kind = 1;
+                fr.n_bytes = block = natoms * 12u;
+                pos_block = pos0 + 56;
             } else {
-                fr.bitsize = (uint32_t)size_of_ints(fr.sizeint);
+                if (got != (ssize_t)sizeof(head)) return GORDER_XTC_ERR_FORMAT;
+                const uint8_t *h2 = head + 56;
+                for (int k = 0; k < 3; k++) {
+                    const int minint = (int32_t)be32(h2 + 4 + 4 * k), maxint = (int32_t)be32(h2 + 16 + 4 * k);
+                    const int64_t sz = (int64_t)maxint - (int64_t)minint + 1;
+                    if (sz <= 0 || sz > 0xffffffffll) return GORDER_XTC_ERR_FORMAT;
+                    fr.minint[k] = minint;
+                    fr.sizeint[k] = (uint32_t)sz;
+                }
+                if ((fr.sizeint[0] | fr.sizeint[1] | fr.sizeint[2]) > 0xffffff) {
+                    fr.bitsize = 0;
+                    for (int k = 0; k < 3; k++) fr.bitsizeint |= (uint32_t)size_of_int(fr.sizeint[k]) << (8 * k);
+                } else {
+                    fr.bitsize = (uint32_t)size_of_ints(fr.sizeint);
+                }
+                fr.recip1 = reciprocal_of(fr.sizeint[1]);
+                fr.recip2 = reciprocal_of(fr.sizeint[2]);
+                fr.smallidx = (int32_t)be32(h2 + 28);
+                if (fr.smallidx < kFirstIdx || fr.smallidx >= kLastIdx) return GORDER_XTC_ERR_FORMAT;
+                fr.inv_precision = 1.0f / bef(h2);
+                block = (uint32_t)(((size_t)be32(h2 + 32) + 3) & ~(size_t)3);
+                fr.n_bytes = block;
+                pos_block = pos0 + (off_t)sizeof(head);
             }
-            fr.recip1 = reciprocal_of(fr.sizeint[1]);
-            fr.recip2 = reciprocal_of(fr.sizeint[2]);
-            fr.smallidx = (int32_t)be32(h2 + 28);
-            if (fr.smallidx < kFirstIdx || fr.smallidx >= kLastIdx) return GORDER_XTC_ERR_FORMAT;
-            fr.inv_precision = 1.0f / bef(h2);
-            block = (uint32_t)(((size_t)be32(h2 + 32) + 3) & ~(size_t)3);
-            fr.n_bytes = block;
-            pos_block = pos0 + (off_t)sizeof(head);
+            // only the leading part of the block (the analysed atoms come first in the frame and the decoder stops behind
+            // them): `copy` bytes are copied and described, bit 1 of `kind` says that the block goes on in the file
+            copy = block;
+            if (prefix_q16 < 65536u && natoms > 9) {
+                const uint64_t c = (((uint64_t)block * prefix_q16 >> 16) + 2048u + 3u) & ~3ull;
+                if (c < block) { copy = (uint32_t)c; fr.kind |= 2u; fr.n_bytes = copy; }
+            }
+            pos = pos_block + (off_t)block;
+            if (file_end >= 0 && pos > file_end) return GORDER_XTC_ERR_FORMAT;     // a byte count the file cannot hold
         }
-        // only the leading part of the block (the analysed atoms come first in the frame and the decoder stops behind
-        // them): `copy` bytes are copied and described, bit 1 of `kind` says that the block goes on in the file
-        uint32_t copy = block;
-        if (prefix_q16 < 65536u && natoms > 9) {
-            const uint64_t c = (((uint64_t)block * prefix_q16 >> 16) + 2048u + 3u) & ~3ull;
-            if (c < block) { copy = (uint32_t)c; fr.kind |= 2u; fr.n_bytes = copy; }
-        }
-        pos = pos_block + (off_t)block;
-        if (file_end >= 0 && pos > file_end) return GORDER_XTC_ERR_FORMAT;     // a byte count the file cannot hold
         // selection: as in gorder_xtc_read_window
         if ((double)t == *last_time) continue;             // duplicate frame at a file boundary
         const double time_before = *last_time;
@@ -1167,7 +1246,7 @@ int64_t pack_window_impl(gorder_xtc_reader *r, float begin_ps, float end_ps, uin
         fr.offset = used;
         used += need;
         frames[i] = fr;
-        for (int q = 0; q < 9; q++) box9[9 * i + q] = bef(head + 16 + 4 * q);
+        for (int q = 0; q < 9; q++) box9[9 * i + q] = r->trr ? trr_box[q] : bef(head + 16 + 4 * q);
         if (time_ps) time_ps[i] = t;
         if (file_pos) file_pos[i] = (int64_t)pos0;
         src.push_back({pos_block, copy, fr.offset});

@@ -50,6 +50,10 @@ def _lib():
                                                   C.c_uint64, C.c_uint32, vp, C.c_uint32, vp]
         lib.gorder_xtc_pack_window_ex.restype = C.c_int64
         lib.gorder_xtc_is_xtc.argtypes = [vp]
+        lib.gorder_xtc_can_pack.argtypes = [vp]
+        lib.gorder_xtc_probe_format.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                                C.POINTER(C.c_uint32)]
+        lib.gorder_xtc_read_at.argtypes = [vp, C.c_int64, vp, vp]
         lib.gorder_xtc_probe.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
         lib.gorder_xtc_n_atoms_needed.argtypes = [vp]
         lib.gorder_xtc_n_atoms_needed.restype = C.c_uint32
@@ -132,13 +136,14 @@ def read_trajectory(paths: Sequence[str], group: Optional[np.ndarray] = None, be
 
 
 def pack_trajectory(paths: Sequence[str], group: Optional[np.ndarray] = None, begin: float = 0.0, end: float = -1.0,
-                    step: int = 1, chunk: int = 64, blob_capacity: int = 0, threads: int = 1, pool: bool = False):
-    """The frames `read_trajectory` would return, still compressed: windows of at most `chunk` frames as
-    gorder_xtc_pack_window packs them for the device decoder (gorder_hip_xtc_decode).
+                    step: int = 1, chunk: int = 64, blob_capacity: int = 0, threads: int = 1, pool: bool = False,
+                    file_pos: bool = False):
+    """The frames `read_trajectory` would return, still compressed (XTC) or as the file's big-endian reals (TRR):
+    windows of at most `chunk` frames as gorder_xtc_pack_window packs them for the device decoder (gorder_hip_xtc_decode).
     `pool`: the block copies go through a pool of `threads` copying threads (gorder_xtc_pack_window_pool), waited for
-    after every window.
+    after every window.  `file_pos`: pack through gorder_xtc_pack_window_ex and return every frame's place in its file.
     -> list of dicts {blob: uint8 [bytes], frames: structured array of CXtcFrame, box [n, 3, 3], time [n],
-                      n_atoms_file, n_stop, slot_of (int32 [n_atoms_file] or None)}."""
+                      n_atoms_file, n_stop, slot_of (int32 [n_atoms_file] or None), path[, file_pos: int64 [n]]}."""
     from .abi import CXtcFrame
     lib = _lib()
     grp = None if group is None else np.ascontiguousarray(group, dtype=np.uint32)
@@ -149,13 +154,13 @@ def pack_trajectory(paths: Sequence[str], group: Optional[np.ndarray] = None, be
         raise IOError("cannot create the copy pool")
     try:
         return _pack_files(lib, paths, grp, begin, end, step, chunk, blob_capacity, threads, cpool if pool else None, state,
-                           last, out)
+                           last, out, file_pos)
     finally:
         if pool:
             lib.gorder_xtc_pool_destroy(cpool)
 
 
-def _pack_files(lib, paths, grp, begin, end, step, chunk, blob_capacity, threads, cpool, state, last, out):
+def _pack_files(lib, paths, grp, begin, end, step, chunk, blob_capacity, threads, cpool, state, last, out, want_pos=False):
     from .abi import CXtcFrame
     for path in paths:
         r = C.c_void_p()
@@ -164,21 +169,29 @@ def _pack_files(lib, paths, grp, begin, end, step, chunk, blob_capacity, threads
         if st != 0:
             raise IOError(f"cannot open {path}: status {st}")
         try:
-            if not lib.gorder_xtc_is_xtc(r):
-                raise IOError(f"{path}: not an XTC file")
+            if not lib.gorder_xtc_can_pack(r):
+                raise IOError(f"{path}: neither an XTC nor a TRR file")
             n_file, n_stop = lib.gorder_xtc_n_atoms_file(r), lib.gorder_xtc_n_atoms_needed(r)
             slot_of = None
             if grp is not None:
                 slot_of = np.full(n_file, -1, dtype=np.int32)
                 slot_of[grp] = np.arange(grp.size, dtype=np.int32)
-            cap = blob_capacity or (chunk * (n_file * 12 + 256) + 4096)
+            per_atom = 12 if lib.gorder_xtc_is_xtc(r) else 24      # (a TRR file may hold doubles)
+            cap = blob_capacity or (chunk * (n_file * per_atom + 256) + 4096)
             while True:
                 blob = np.empty(cap, dtype=np.uint8)
                 frames = (CXtcFrame * chunk)()
                 b = np.empty((chunk, 3, 3), dtype=np.float32)
                 t = np.empty(chunk, dtype=np.float32)
                 used = C.c_uint64(0)
-                if cpool is not None:
+                fpos = np.zeros(chunk, dtype=np.int64)
+                if want_pos:
+                    got = lib.gorder_xtc_pack_window_ex(r, begin, end, step, C.byref(state), C.byref(last), blob.ctypes.data,
+                                                        cap, C.byref(used), C.cast(frames, C.c_void_p), b.ctypes.data,
+                                                        t.ctypes.data, chunk, threads, cpool, 65536, fpos.ctypes.data)
+                    if got >= 0 and cpool is not None and lib.gorder_xtc_pool_wait(cpool) != 0:
+                        got = -2
+                elif cpool is not None:
                     got = lib.gorder_xtc_pack_window_pool(r, begin, end, step, C.byref(state), C.byref(last), blob.ctypes.data,
                                                           cap, C.byref(used), C.cast(frames, C.c_void_p), b.ctypes.data,
                                                           t.ctypes.data, chunk, cpool)
@@ -194,10 +207,59 @@ def _pack_files(lib, paths, grp, begin, end, step, chunk, blob_capacity, threads
                     break
                 fr = np.frombuffer(frames, dtype=np.dtype(CXtcFrame))[:got].copy()
                 out.append({"blob": blob[:used.value].copy(), "frames": fr, "box": b[:got].copy(), "time": t[:got].copy(),
-                            "n_atoms_file": n_file, "n_stop": n_stop, "slot_of": slot_of})
+                            "n_atoms_file": n_file, "n_stop": n_stop, "slot_of": slot_of, "path": path})
+                if want_pos:
+                    out[-1]["file_pos"] = fpos[:got].copy()
         finally:
             lib.gorder_xtc_close(r)
     return out
+
+
+FORMAT_OTHER, FORMAT_XTC, FORMAT_TRR = 0, 1, 2
+
+
+def probe_format(path: str) -> dict:
+    """A file's first bytes (gorder_xtc_probe_format) -> {format: FORMAT_XTC / FORMAT_TRR / FORMAT_OTHER, n_atoms,
+    file_bytes, first_frame_bytes}."""
+    lib = _lib()
+    fmt, na, fb, first = C.c_int(), C.c_uint32(), C.c_uint64(), C.c_uint32()
+    st = lib.gorder_xtc_probe_format(path.encode(), C.byref(fmt), C.byref(na), C.byref(fb), C.byref(first))
+    if st != 0:
+        raise IOError(f"cannot look at {path}: status {st}")
+    return {"format": fmt.value, "n_atoms": na.value, "file_bytes": fb.value, "first_frame_bytes": first.value}
+
+
+def read_at(path: str, file_pos: int, group: Optional[np.ndarray] = None):
+    """The frame whose header starts at `file_pos` (as gorder_xtc_pack_window_ex reports it), decoded by the host
+    (gorder_xtc_read_at) -> xyz [n_out, 3], box [3, 3]."""
+    lib = _lib()
+    grp = None if group is None else np.ascontiguousarray(group, dtype=np.uint32)
+    r = C.c_void_p()
+    st = lib.gorder_xtc_open(path.encode(), None if grp is None else grp.ctypes.data, 0 if grp is None else grp.size, C.byref(r))
+    if st != 0:
+        raise IOError(f"cannot open {path}: status {st}")
+    try:
+        x = np.empty((lib.gorder_xtc_n_atoms_out(r), 3), dtype=np.float32)
+        b = np.empty((3, 3), dtype=np.float32)
+        st = lib.gorder_xtc_read_at(r, file_pos, x.ctypes.data, b.ctypes.data)
+        if st != 0:
+            raise IOError(f"{path}: read error {st} at {file_pos}")
+        return x, b
+    finally:
+        lib.gorder_xtc_close(r)
+
+
+def can_pack(path: str) -> bool:
+    """Whether gorder_xtc_pack_window accepts a reader of the file (XTC and TRR: yes; GRO: no)."""
+    lib = _lib()
+    r = C.c_void_p()
+    st = lib.gorder_xtc_open(path.encode(), None, 0, C.byref(r))
+    if st != 0:
+        raise IOError(f"cannot open {path}: status {st}")
+    try:
+        return bool(lib.gorder_xtc_can_pack(r))
+    finally:
+        lib.gorder_xtc_close(r)
 
 
 def count_frames(paths: Sequence[str], begin: float = 0.0, end: float = -1.0, step: int = 1) -> int:

@@ -304,9 +304,13 @@ typedef struct {
                                     blocks into pinned memory (gorder_xtc_pack_window), the copy engine moves those
                                     (about a third of the decoded bytes) and gorder_hip_xtc_decode unpacks them (k_xtc_scan:
                                     a wave per frame finds where every 256-atom chunk starts; k_xtc_chunks: a lane per
-                                    chunk decodes).  Same coordinates bit for bit.  A run with a TRR or GRO file in it, or of frames
-                                    so large that fewer than 512 fit a 4-GiB batch (about 700 000 analysed atoms; a launch
-                                    takes 0.6 us per atom whatever its size), uses the host decoder.  When the analysed
+                                    chunk decodes).  TRR files take the route too, also mixed with XTC files in one run: the
+                                    positions of the atoms up to the last analysed one travel as the file holds them
+                                    (big-endian f32 or f64) and k_trr_unpack swaps and rounds them.  Same coordinates bit
+                                    for bit.  A run with a GRO file in it, or with files of different atom counts, or —
+                                    when there is an XTC file in it — of frames so large that fewer than 512 fit a 4-GiB
+                                    batch (about 700 000 analysed atoms; an XTC launch takes 0.6 us per atom whatever its
+                                    size), uses the host decoder.  When the analysed
                                     atoms end before the frame does, only the leading part of every compressed block the
                                     decoder needs is copied (learned from the first batches; a frame that needs more is
                                     decoded by the host).  0: host decoder threads */
@@ -330,7 +334,7 @@ typedef struct {
     double seconds_reader_stalled;   /* the reader waited for a free staging slot: copies / kernels are the bottleneck */
     double seconds_gpu_starved;      /* the submitter waited for a decoded batch: the decoder is the bottleneck */
     uint32_t batch_frames, decoder_threads;   /* what was used */
-    uint32_t device_decode;          /* 1: the frames were decompressed on the device */
+    uint32_t device_decode;          /* 1: the frames were decompressed (XTC) / unpacked (TRR) on the device */
     uint32_t frames_decoded_by_host; /* device route: frames of which too short a leading part had been copied (see
                                         gorder_xtc_pack_window_ex) and which the host decoded after all */
     uint64_t shard_first, shard_frames_total;   /* with shards: ordinal of this shard's first frame among the F selected; F */
@@ -346,7 +350,8 @@ int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_trajectory_t *t
  * replaces them, gorder_hip_destroy frees them — and so does this call, for a host that wants the memory back. */
 void gorder_hip_release_staging(gorder_hip_handle *h);
 
-/* Decompress XTC frames on the device (the decoding half of groan_rs' GroupXtcReader, common.rs:283-304):
+/* Decompress XTC frames — and unpack TRR frames — on the device (the decoding half of groan_rs' GroupXtcReader and
+ * TrrReader, common.rs:283-320):
  * `d_blob` / `d_frames` are device copies of what gorder_xtc_pack_window produced (d_blob 64-byte aligned, blob_bytes >= 64), `d_slot_of`
  * [n_atoms_file] maps a file atom to its place in the output frame or -1 (NULL: every atom, in order), `n_stop` is
  * the number of atoms to go through (gorder_xtc_n_atoms_needed), `d_xyz` [n_frames][n_atoms_out][3] receives exactly
@@ -354,7 +359,12 @@ void gorder_hip_release_staging(gorder_hip_handle *h);
  * reported as GORDER_ERR_TRAJECTORY_FORMAT by the next synchronising call.  Two kernels: k_xtc_scan (a wave per frame walks the
  * group headers, 64 groups a step, and leaves a checkpoint per 256 atoms) and k_xtc_chunks (a lane per chunk decodes from
  * its checkpoint); a frame table with widths no writer produces (more than 72 bits per atom, a field of more than 32, none at
- * all) is a format error too.  2.5 ms per 3 566 frames of 25 088 atoms. */
+ * all) is a format error too.  2.5 ms per 3 566 frames of 25 088 atoms.
+ * The table may hold TRR frames (bits 2 / 3 of `kind`), alone or beside XTC frames — a trajectory concatenated from files
+ * of both formats: those go through k_trr_unpack (byte swap; f64 rounded to nearest even like the host's cast; a thread
+ * per four floats of a frame, or per atom with `d_slot_of`), each kernel passes over the frames of the other kind, and a
+ * table without frames of a kind queues no kernel for it.  To know which, the call reads the table's `kind` words back in
+ * the stream's order first (it waits for what the stream holds so far); the kernels themselves are asynchronous. */
 int gorder_hip_xtc_decode(gorder_hip_handle *h, const uint8_t *d_blob, uint64_t blob_bytes,
                           const gorder_xtc_frame_t *d_frames, uint32_t n_frames, uint32_t n_atoms_file,
                           const int32_t *d_slot_of, uint32_t n_stop, float *d_xyz, uint32_t n_atoms_out);
@@ -538,7 +548,8 @@ const char *gorder_hip_strerror(int status);
  * "k_local_rowprefix", "k_local_flags_rows", "k_local_flags_todo" per 256-frame slab; ...), "k_dyn_cov + k_dyn_eigen",
  * "k_geom_shapes", the order kernels ("k_bonds_tiled", "k_ua_extras", "k_bonds_tiled_maps", ...), "k_map_accumulate",
  * "k_bonds_direct", with manual tables "k_replay_flags" and "k_replay_normals" (ahead of the order kernels), with collection
- * "k_collect_flags" and "k_collect_normals" (the copy to the host included), "k_batch_end" —; *ms is the sum over all segments, i.e. the WHOLE step on the device. */
+ * "k_collect_flags" and "k_collect_normals" (the copy to the host included), "k_batch_end", and for gorder_hip_xtc_decode on a
+ * table with TRR frames "k_trr_unpack" —; *ms is the sum over all segments, i.e. the WHOLE step on the device. */
 int gorder_hip_kernel_time(gorder_hip_handle *h, double *ms, uint64_t *launches, int reset);
 /* Group `index` of the same measurement (in order of first appearance since the last reset): its name, the device time
  * of its segments and their number.  GORDER_ERR_INVALID_ARGUMENT past the last group.  The times of all groups add up to

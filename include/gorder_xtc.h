@@ -82,14 +82,22 @@ int64_t gorder_xtc_read_window_mt(gorder_xtc_reader *r, float begin_ps, float en
  * later").  Instead of decoding, gorder_xtc_pack_window copies the still-compressed coordinate blocks of the selected
  * frames into one caller buffer (`blob`, meant to be pinned host memory) and describes each with a gorder_xtc_frame_t;
  * the device decodes them (a wave per frame finds where chunks of 256 atoms start, a lane per chunk unpacks).  Frame selection (time window, step, duplicate boundary frame), `state`,
- * `last_time`, box and time outputs are exactly those of gorder_xtc_read_window.  XTC only (not TRR / GRO). */
+ * `last_time`, box and time outputs are exactly those of gorder_xtc_read_window.
+ * A TRR reader is packed too: there is nothing to decompress, but the host need not swap, round and copy the reals either —
+ * of every selected frame the leading gorder_xtc_n_atoms_needed(r) atoms of the positions block travel as they are in the
+ * file (big-endian f32 or f64; a frame without positions is not a frame, as for gorder_xtc_next), and k_trr_unpack makes
+ * the floats.  The bytes that travel are known before reading, so a TRR frame is never copied in part and never SHORT.
+ * GRO (text) is not packed. */
 typedef struct {
     uint64_t offset;         /* of the frame's bit stream in the blob: a multiple of 64; the stream is followed by zeros up to
                                 the next multiple of 64 and by 64 more (the device reads whole 64-byte pieces) */
     uint64_t recip1, recip2; /* floor(2^64 / sizeint[1]), floor(2^64 / sizeint[2]) (all ones for a size of 1) */
-    uint32_t n_bytes;        /* length of the bit stream, padded to a multiple of 4 as in the file */
+    uint32_t n_bytes;        /* length of the bit stream, padded to a multiple of 4 as in the file; TRR: the bytes copied,
+                                n_atoms_needed * 3 * (4 or 8) */
     uint32_t kind;           /* bit 0: raw big-endian floats (files of <= 9 atoms) instead of a compressed block;
-                                bit 1: only a leading part of the block was copied (gorder_xtc_pack_window_ex) */
+                                bit 1: only a leading part of the block was copied (gorder_xtc_pack_window_ex; never TRR);
+                                bit 2: big-endian f32 positions of a TRR frame; bit 3: big-endian f64 positions of a TRR
+                                frame (with bit 2 or 3 every field below is zero) */
     int32_t minint[3];
     uint32_t sizeint[3];     /* maxint - minint + 1 */
     int32_t smallidx;
@@ -101,8 +109,9 @@ typedef struct {
 /* Returns the number of frames packed (0 at the end of the file), fewer than `capacity` also when the next frame
  * would not fit `blob_capacity` (a later call continues with that frame), or a negative gorder_xtc_status_t
  * (GORDER_XTC_ERR_NO_SPACE when not even ONE frame fits the blob — nothing has happened then: file position, *state
- * and *last_time are those of the call's entry; GORDER_XTC_ERR_ARGUMENT for a TRR / GRO reader; GORDER_XTC_ERR_FORMAT
- * also for a block whose byte count runs past the end of the file).
+ * and *last_time are those of the call's entry; GORDER_XTC_ERR_ARGUMENT for a GRO reader; GORDER_XTC_ERR_FORMAT
+ * also for a block whose byte count runs past the end of the file — for TRR: a positions block the file ends in, or one
+ * whose size is not natoms * 3 reals).
  * `*blob_bytes` receives the bytes of the blob in use.  The blocks are copied by `n_threads` threads: out of a read-only
  * mapping of the file made at the reader's first window (streaming stores into the blob), `pread` where there is no
  * mapping.  A file that has shrunk since it was mapped is read by `pread` from then on, the part of a file that has
@@ -130,7 +139,8 @@ int64_t gorder_xtc_pack_window_pool(gorder_xtc_reader *r, float begin_ps, float 
  * only the leading prefix_q16 / 65536 of every block (+ 2 KB): the analysed atoms come first in a frame and the decoder
  * stops behind them, so the tail — the solvent — need not travel; such a frame has bit 1 of `kind` set and `n_bytes` =
  * the bytes copied, and a decoder that runs past them must report the frame as SHORT, not as corrupt (k_xtc_scan
- * does; the trajectory driver then decodes that frame on the host from `file_pos`).  `file_pos` (may be NULL)
+ * does; the trajectory driver then decodes that frame on the host from `file_pos`).  A TRR reader ignores `prefix_q16`
+ * (what it copies is exactly what is needed).  `file_pos` (may be NULL)
  * receives the file offset of every packed frame's header, for gorder_xtc_read_at. */
 int64_t gorder_xtc_pack_window_ex(gorder_xtc_reader *r, float begin_ps, float end_ps, uint32_t step, uint64_t *state,
                                   double *last_time, uint8_t *blob, uint64_t blob_capacity, uint64_t *blob_bytes,
@@ -143,8 +153,17 @@ int gorder_xtc_read_at(gorder_xtc_reader *r, int64_t file_pos, float *xyz, float
  * *first_frame_bytes = header + coordinate block of its first frame; each may be NULL), 0 = something else
  * (TRR, GRO, ...), negative = cannot be opened / too short. */
 int gorder_xtc_probe(const char *path, uint32_t *n_atoms, uint64_t *file_bytes, uint32_t *first_frame_bytes);
-/* 1 when the reader's file is an XTC file (what gorder_xtc_pack_window accepts), else 0 */
+/* The same look with the format named: *format = one of the values below; for GORDER_XTC_FORMAT_TRR *n_atoms = atoms per
+ * frame and *first_frame_bytes = header + positions block of the first frame that has positions (0: none found); for
+ * GORDER_XTC_FORMAT_OTHER (GRO, anything else) both are 0.  n_atoms, file_bytes and first_frame_bytes may be NULL.
+ * Returns GORDER_XTC_OK, or negative = cannot be opened / too short. */
+enum { GORDER_XTC_FORMAT_OTHER = 0, GORDER_XTC_FORMAT_XTC = 1, GORDER_XTC_FORMAT_TRR = 2 };
+int gorder_xtc_probe_format(const char *path, int *format, uint32_t *n_atoms, uint64_t *file_bytes,
+                            uint32_t *first_frame_bytes);
+/* 1 when the reader's file is an XTC file, else 0 */
 int gorder_xtc_is_xtc(const gorder_xtc_reader *r);
+/* 1 when gorder_xtc_pack_window* accepts the reader (XTC and TRR), else 0 (GRO) */
+int gorder_xtc_can_pack(const gorder_xtc_reader *r);
 /* atoms of a frame the decoder has to go through: up to the last atom of the group (all atoms without a group) */
 uint32_t gorder_xtc_n_atoms_needed(const gorder_xtc_reader *r);
 
