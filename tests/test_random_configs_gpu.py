@@ -84,6 +84,23 @@ def test_random_configuration(built, seed):
     t = system.tables
     xyz = system.frames(n, seed=seed)
     box = system.box9(n) if t.handle_pbc else None
+    check_configuration(t, xyz, box, n, batches)
+
+
+@pytest.mark.parametrize("seed", range(40))
+def test_random_configuration_rotated(built, seed):
+    """The first 40 configurations with the membrane normal along x (even seeds) or y (odd seeds): the frames of the z
+    system relabelled cyclically, every axis-valued option moved with them (tests/axis_rotation.py)."""
+    import axis_rotation
+    system, n, batches, kind = make_case(1000 + seed)
+    xyz = system.frames(n, seed=seed)
+    box = system.box9(n) if system.tables.handle_pbc else None
+    t, xyz, box = axis_rotation.rotate(system.tables, xyz, box, (1000 + seed) % 2)
+    assert t.leaflets.normal_dim == (1000 + seed) % 2 and t.normal[(1000 + seed) % 2] == 1.0
+    check_configuration(t, xyz, box, n, batches)
+
+
+def check_configuration(t, xyz, box, n, batches):
     trig = oracle.TRIG_MIRROR if (t.flags & abi.FLAG_TRIG_ACOS_COS) else oracle.TRIG_DIRECT
     eng = HipEngine(t)
     o = oracle.OracleEngine(t, trig=trig, n_threads=2)
