@@ -323,6 +323,8 @@ _EXPORTS = [
     "gorder_hip_spherical_stats", "gorder_hip_clustering_stats",
     "gorder_hip_set_collect", "gorder_hip_collected_counts", "gorder_hip_collected_leaflets", "gorder_hip_collected_normals",
     "gorder_hip_set_manual_leaflet_table", "gorder_hip_set_manual_normal_table",
+    "gorder_hip_timewise_chunk_frames", "gorder_hip_timewise_rows", "gorder_hip_timewise_blocks", "gorder_hip_error_estimate",
+    "gorder_hip_convergence",
 ]
 
 _lib = None
@@ -415,8 +417,29 @@ def load_library() -> C.CDLL:
     lib.gorder_hip_collected_normals.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
     lib.gorder_hip_set_manual_leaflet_table.argtypes = [vp, vp, u64, u64]
     lib.gorder_hip_set_manual_normal_table.argtypes = [vp, vp, u32, u64, u64]
+    lib.gorder_hip_timewise_chunk_frames.argtypes = []
+    lib.gorder_hip_timewise_chunk_frames.restype = u32
+    lib.gorder_hip_timewise_rows.argtypes = [vp]
+    lib.gorder_hip_timewise_rows.restype = u64
+    lib.gorder_hip_timewise_blocks.argtypes = [vp, u32, u64, u64, vp, vp, C.POINTER(u64)]
+    lib.gorder_hip_error_estimate.argtypes = [vp, u32, vp, vp, u32, vp, vp, vp]
+    lib.gorder_hip_convergence.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
+
+
+def timewise_chunk_frames() -> int:
+    """Rows a workgroup of the device's block-sum pass folds (gorder_hip_timewise_chunk_frames); needs no device."""
+    return int(load_library().gorder_hip_timewise_chunk_frames())
+
+
+def _pack_groups(groups):
+    """Lists of accumulator slots -> CSR (group_begin [n + 1], slots) as the C ABI takes them."""
+    begin = np.zeros(len(groups) + 1, dtype=np.uint32)
+    begin[1:] = np.cumsum([len(g) for g in groups])
+    flat = [int(k) for g in groups for k in g]
+    slots = np.array(flat if flat else [0], dtype=np.uint32)      # (never a null pointer: the library names what is wrong)
+    return begin, slots
 
 
 def selftest_trig(fn: str, first_bits: int, stride: int, n: int, device: int = 0) -> np.ndarray:
@@ -713,6 +736,60 @@ class HipEngine:
         self._check(self.lib.gorder_hip_timewise(self._h, s.ctypes.data_as(C.c_void_p),
                                                  c.ctypes.data_as(C.c_void_p), n_frames))
         return s, c
+
+    def timewise_rows(self) -> int:
+        """Per-frame rows the handle holds: the frames analysed since it was made or reset (0 with timewise off)."""
+        return int(self.lib.gorder_hip_timewise_rows(self._h))
+
+    def timewise_blocks(self, n_blocks: int, total_frames: Optional[int] = None, first_position: int = 0):
+        """Block sums of the handle's rows, made on the device (gorder_hip_timewise_blocks) -> (sums int64, counts uint64
+        [n_blocks, 3, n_acc], block_size).  The block grid is that of an analysis of `total_frames` frames (default: this
+        handle's rows) in which the handle's first row sits at `first_position`; the outputs of the shards of one analysis
+        add up element by element to the block sums of the whole run."""
+        if total_frames is None:
+            total_frames = self.timewise_rows()
+        s = np.zeros((n_blocks, 3, self.n_acc), dtype=np.int64)
+        c = np.zeros((n_blocks, 3, self.n_acc), dtype=np.uint64)
+        bs = C.c_uint64()
+        self._check(self.lib.gorder_hip_timewise_blocks(self._h, n_blocks, total_frames, first_position, s.ctypes.data_as(C.c_void_p),
+                                                        c.ctypes.data_as(C.c_void_p), C.byref(bs)))
+        return s, c, int(bs.value)
+
+    def error_estimate(self, groups, n_blocks: int = 5, blocks=None) -> np.ndarray:
+        """estimate_error of every group (a list of accumulator slots whose rows are added) and leaflet, on the device
+        (gorder_hip_error_estimate) -> float32 [n_groups, 3], bit for bit structure.estimate_error on the rows.
+        blocks = (sums, counts) [n_blocks, 3, n_acc]: the merged timewise_blocks() of the shards instead of this handle's rows."""
+        begin, slots = _pack_groups(groups)
+        out = np.zeros((len(groups), 3), dtype=np.float32)
+        bs = bc = None
+        if blocks is not None:
+            bs = np.ascontiguousarray(blocks[0], dtype=np.int64)
+            bc = np.ascontiguousarray(blocks[1], dtype=np.uint64)
+            assert bs.shape == bc.shape == (n_blocks, 3, self.n_acc)
+        self._check(self.lib.gorder_hip_error_estimate(self._h, n_blocks, begin.ctypes.data_as(C.c_void_p), slots.ctypes.data_as(C.c_void_p),
+                                                       len(groups), None if bs is None else bs.ctypes.data_as(C.c_void_p),
+                                                       None if bc is None else bc.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def convergence(self, groups, carry=None):
+        """Running averages of every group and leaflet over the handle's rows, on the device (gorder_hip_convergence) ->
+        (prefix float32 [rows, 3, n_groups]: NaN while nothing was sampled, no sign flip; end = (sums int64, counts uint64)
+        [3, n_groups] behind the last row).  carry: the `end` of the shard before this one."""
+        begin, slots = _pack_groups(groups)
+        n = len(groups)
+        prefix = np.zeros((self.timewise_rows(), 3, n), dtype=np.float32)
+        es, ec = np.zeros((3, n), dtype=np.int64), np.zeros((3, n), dtype=np.uint64)
+        cs = cc = None
+        if carry is not None:
+            cs = np.ascontiguousarray(carry[0], dtype=np.int64)
+            cc = np.ascontiguousarray(carry[1], dtype=np.uint64)
+            assert cs.shape == cc.shape == (3, n)
+        self._check(self.lib.gorder_hip_convergence(self._h, begin.ctypes.data_as(C.c_void_p), slots.ctypes.data_as(C.c_void_p), n,
+                                                    None if cs is None else cs.ctypes.data_as(C.c_void_p),
+                                                    None if cc is None else cc.ctypes.data_as(C.c_void_p),
+                                                    prefix.ctypes.data_as(C.c_void_p), es.ctypes.data_as(C.c_void_p),
+                                                    ec.ctypes.data_as(C.c_void_p)))
+        return prefix, (es, ec)
 
     def leaflets(self):
         flags = np.zeros(self.tables.n_molecules_total, dtype=np.uint8)

@@ -37,6 +37,7 @@
 #include "plan.h"
 #include "collect_store.h"
 #include "replay_rows.h"
+#include "timewise_blocks.h"
 
 #pragma clang fp contract(off)
 
@@ -56,6 +57,7 @@ using gorder::Tile;
 #include "kernels_trr.h"
 #include "kernels_collect.h"
 #include "kernels_replay.h"
+#include "kernels_timewise.h"
 
 // ============================================================================================
 // host side
@@ -111,6 +113,12 @@ struct gorder_hip_handle {
     uint32_t map_max_mol = 1;      // most molecules of one type = most samples per tile and frame
     unsigned long long *d_tw_sums = nullptr, *d_tw_cnts = nullptr;
     uint64_t tw_cap = 0;
+    // scratch of the passes over those rows (kernels_timewise.h): block sums then counts [2][n_blocks][3][n_acc], the groups in
+    // CSR form, the groups' per-frame rows and their chunk totals [2][..][3][n_groups], carry and end [4][3][n_groups], the columns
+    unsigned long long *d_twx_blocks = nullptr, *d_twx_rows = nullptr, *d_twx_totals = nullptr, *d_twx_edge = nullptr;
+    uint32_t *d_twx_groups = nullptr;
+    float *d_twx_out = nullptr;
+    size_t twx_blocks_cap = 0, twx_rows_cap = 0, twx_totals_cap = 0, twx_edge_cap = 0, twx_groups_cap = 0, twx_out_cap = 0;
     ExtraArgs extra{};
     uint32_t *d_geom_group = nullptr;
     float *d_shapes = nullptr;
@@ -1515,6 +1523,7 @@ void gorder_hip_destroy(gorder_hip_handle *h) {
     (void)hipFree(h->d_direct); (void)hipFree(h->d_err); (void)hipFree(h->d_xtc_cp);
     (void)hipFree(h->d_ua_tiles); (void)hipFree(h->d_ua_items); (void)hipFree(h->d_ua_tile_slots);
     (void)hipFree(h->d_map_sums); (void)hipFree(h->d_map_cnts); (void)hipFree(h->d_map_packed); (void)hipFree(h->d_tw_sums); (void)hipFree(h->d_tw_cnts);
+    (void)hipFree(h->d_twx_blocks); (void)hipFree(h->d_twx_rows); (void)hipFree(h->d_twx_totals); (void)hipFree(h->d_twx_edge); (void)hipFree(h->d_twx_groups); (void)hipFree(h->d_twx_out);
     (void)hipFree(h->d_geom_group); (void)hipFree(h->d_shapes); (void)hipFree(h->d_inv_box);
     (void)hipFree(h->d_map_rec); (void)hipFree(h->d_ua_runs); (void)hipFree(h->d_ua_run_begin);
     (void)hipFree(h->d_runs); (void)hipFree(h->d_run_begin); (void)hipFree(h->d_items_by_slot);
@@ -2345,6 +2354,161 @@ int gorder_hip_timewise(gorder_hip_handle *h, int64_t *tw_sums, uint64_t *tw_cou
             }
         }
     }
+    return GORDER_OK;
+}
+
+// ---- error estimates and convergence from the rows, on the device (kernels_timewise.h, timewise_blocks.h) ---------------
+uint32_t gorder_hip_timewise_chunk_frames(void) { return gorder::kTwChunkFrames; }
+
+uint64_t gorder_hip_timewise_rows(const gorder_hip_handle *h) { return h && h->extra.tw ? h->n_frames : 0; }
+
+// what every entry point below refuses, and the wait for the rows (a device error of the run is returned as by gorder_hip_synchronize)
+static int tw_enter(gorder_hip_handle *h, const char *who, uint32_t n_blocks) {
+    if (!h) return GORDER_ERR_INVALID_ARGUMENT;
+    if (!h->extra.tw) return fail(h, GORDER_ERR_INVALID_ARGUMENT, std::string(who) + ": the handle keeps no per-frame rows (tables.timewise = 0)");
+    if (n_blocks < 2) return fail(h, GORDER_ERR_INVALID_ARGUMENT, std::string(who) + ": n_blocks must be at least 2");
+    return gorder_hip_synchronize(h);
+}
+
+// the groups, checked and copied to d_twx_groups: group_begin rebased to 0 [n_groups + 1], then the slots
+static int tw_upload_groups(gorder_hip_handle *h, const char *who, const uint32_t *group_begin, const uint32_t *slots, uint32_t n_groups) {
+    uint32_t bad = 0;
+    const gorder::TwGroupStatus gs = gorder::tw_check_groups(group_begin, slots, n_groups, h->plan.n_acc, &bad);
+    if (gs != gorder::kTwGroupsOk)
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, std::string(who) + ": " + gorder::tw_group_status_text(gs) + " (at " + std::to_string(bad) + ")");
+    std::vector<uint32_t> csr((size_t)n_groups + 1u);
+    for (uint32_t g = 0; g <= n_groups; g++) csr[g] = group_begin[g] - group_begin[0];
+    csr.insert(csr.end(), slots + group_begin[0], slots + group_begin[n_groups]);
+    const int st = ensure(h, &h->d_twx_groups, &h->twx_groups_cap, csr.size());
+    if (st != GORDER_OK) return st;
+    HIP_TRY(h, hipMemcpyAsync(h->d_twx_groups, csr.data(), csr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));      // (csr leaves scope)
+    return GORDER_OK;
+}
+
+// d_twx_blocks = the block sums [n_blocks][3][n_acc], then the counts, of this handle's rows; queued on the stream
+static int tw_blocks_device(gorder_hip_handle *h, uint32_t n_blocks, uint64_t total_frames, uint64_t first_position, uint64_t *block_size) {
+    const uint32_t n_acc = h->plan.n_acc, row_words = 3u * n_acc;
+    const bool leaflets = h->tables.leaflets.method != GORDER_LEAFLETS_NONE;
+    if (!gorder::tw_positions_ok(first_position, h->n_frames))
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "first_position + the handle's rows passes 2^64");
+    const uint64_t bs = gorder::tw_block_size(total_frames, n_blocks);
+    if (block_size) *block_size = bs;
+    const size_t n = (size_t)n_blocks * row_words;
+    int st = ensure(h, &h->d_twx_blocks, &h->twx_blocks_cap, 2 * n);
+    if (st != GORDER_OK) return st;
+    unsigned long long *d_sums = h->d_twx_blocks, *d_cnts = h->d_twx_blocks + n;
+    HIP_TRY(h, hipMemsetAsync(h->d_twx_blocks, 0, 2 * n * sizeof(unsigned long long), h->stream));
+    const uint64_t n_used = gorder::tw_rows_used(first_position, h->n_frames, bs, n_blocks);
+    if (n_used == 0) return GORDER_OK;
+    TIMING_MARK(h, "k_tw_blocks");
+    const uint32_t fold_words = leaflets ? 2u * n_acc : row_words;
+    const uint32_t threads = fold_words <= 64u ? 64u : (fold_words <= 128u ? 128u : 256u);
+    hipLaunchKernelGGL(k_tw_blocks, dim3((uint32_t)gorder::tw_n_chunks(n_used), (fold_words + threads - 1u) / threads), dim3(threads), 0,
+                       h->stream, h->d_tw_sums, h->d_tw_cnts, row_words, fold_words, (tw_u64)n_used, (tw_u64)first_position, (tw_u64)bs,
+                       d_sums, d_cnts);
+    HIP_TRY(h, hipGetLastError());
+    if (leaflets) {
+        const uint64_t m = (uint64_t)n_blocks * n_acc;
+        hipLaunchKernelGGL(k_tw_lower, dim3((uint32_t)((m + 255u) / 256u)), dim3(256), 0, h->stream, d_sums, d_cnts, n_acc, (tw_u64)m);
+        HIP_TRY(h, hipGetLastError());
+    }
+    TIMING_MARK(h, nullptr);
+    return GORDER_OK;
+}
+
+int gorder_hip_timewise_blocks(gorder_hip_handle *h, uint32_t n_blocks, uint64_t total_frames, uint64_t first_position,
+                               int64_t *block_sums, uint64_t *block_counts, uint64_t *block_size) {
+    int st = tw_enter(h, "gorder_hip_timewise_blocks", n_blocks);
+    if (st != GORDER_OK) return st;
+    if (!block_sums || !block_counts) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_timewise_blocks: null output");
+    if ((st = tw_blocks_device(h, n_blocks, total_frames, first_position, block_size)) != GORDER_OK) return st;
+    const size_t n = (size_t)n_blocks * 3u * h->plan.n_acc;
+    HIP_TRY(h, hipMemcpyAsync(block_sums, h->d_twx_blocks, n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(block_counts, h->d_twx_blocks + n, n * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return GORDER_OK;
+}
+
+int gorder_hip_error_estimate(gorder_hip_handle *h, uint32_t n_blocks, const uint32_t *group_begin, const uint32_t *slots,
+                              uint32_t n_groups, const int64_t *block_sums, const uint64_t *block_counts, float *errors) {
+    int st = tw_enter(h, "gorder_hip_error_estimate", n_blocks);
+    if (st != GORDER_OK) return st;
+    if (!errors || (block_sums == nullptr) != (block_counts == nullptr))
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_error_estimate: null output, or only one of block_sums / block_counts");
+    if ((st = tw_upload_groups(h, "gorder_hip_error_estimate", group_begin, slots, n_groups)) != GORDER_OK) return st;
+    const uint32_t n_acc = h->plan.n_acc;
+    const size_t n = (size_t)n_blocks * 3u * n_acc;
+    if (block_sums) {            // merged blocks of several shards
+        if ((st = ensure(h, &h->d_twx_blocks, &h->twx_blocks_cap, 2 * n)) != GORDER_OK) return st;
+        HIP_TRY(h, hipMemcpyAsync(h->d_twx_blocks, block_sums, n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->d_twx_blocks + n, block_counts, n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+    } else if ((st = tw_blocks_device(h, n_blocks, h->n_frames, 0, nullptr)) != GORDER_OK) return st;
+    if ((st = ensure(h, &h->d_twx_out, &h->twx_out_cap, (size_t)n_groups * 3u)) != GORDER_OK) return st;
+    TIMING_MARK(h, "k_tw_errors");
+    hipLaunchKernelGGL(k_tw_errors, dim3(n_groups * 3u), dim3(64), 0, h->stream, h->d_twx_blocks, h->d_twx_blocks + n, n_blocks, n_acc,
+                       h->d_twx_groups, h->d_twx_groups + n_groups + 1u, h->d_twx_out);
+    HIP_TRY(h, hipGetLastError());
+    TIMING_MARK(h, nullptr);
+    HIP_TRY(h, hipMemcpyAsync(errors, h->d_twx_out, (size_t)n_groups * 3u * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return GORDER_OK;
+}
+
+int gorder_hip_convergence(gorder_hip_handle *h, const uint32_t *group_begin, const uint32_t *slots, uint32_t n_groups,
+                           const int64_t *carry_sums, const uint64_t *carry_counts, float *prefix, int64_t *end_sums,
+                           uint64_t *end_counts) {
+    int st = tw_enter(h, "gorder_hip_convergence", 2);
+    if (st != GORDER_OK) return st;
+    if ((carry_sums == nullptr) != (carry_counts == nullptr))
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_convergence: only one of carry_sums / carry_counts");
+    if ((st = tw_upload_groups(h, "gorder_hip_convergence", group_begin, slots, n_groups)) != GORDER_OK) return st;
+    const uint64_t n_frames = h->n_frames;
+    const uint32_t n_cols = 3u * n_groups;
+    if (n_frames == 0) {         // nothing to scan: the carry passes through
+        for (uint32_t k = 0; k < n_cols; k++) {
+            if (end_sums) end_sums[k] = carry_sums ? carry_sums[k] : 0;
+            if (end_counts) end_counts[k] = carry_counts ? carry_counts[k] : 0;
+        }
+        return GORDER_OK;
+    }
+    if (!prefix) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_convergence: null output");
+    const uint64_t n_chunks = gorder::tw_n_chunks(n_frames);
+    const size_t n_rows = (size_t)n_frames * n_cols, n_tot = (size_t)n_chunks * n_cols;
+    if ((st = ensure(h, &h->d_twx_rows, &h->twx_rows_cap, 2 * n_rows)) != GORDER_OK) return st;
+    if ((st = ensure(h, &h->d_twx_totals, &h->twx_totals_cap, 2 * n_tot)) != GORDER_OK) return st;
+    if ((st = ensure(h, &h->d_twx_edge, &h->twx_edge_cap, 4 * (size_t)n_cols)) != GORDER_OK) return st;
+    if ((st = ensure(h, &h->d_twx_out, &h->twx_out_cap, n_rows)) != GORDER_OK) return st;
+    unsigned long long *d_rs = h->d_twx_rows, *d_rc = d_rs + n_rows, *d_ts = h->d_twx_totals, *d_tc = d_ts + n_tot;
+    unsigned long long *d_cs = nullptr, *d_cc = nullptr, *d_es = h->d_twx_edge + 2 * (size_t)n_cols, *d_ec = d_es + n_cols;
+    if (carry_sums) {
+        d_cs = h->d_twx_edge; d_cc = d_cs + n_cols;
+        HIP_TRY(h, hipMemcpyAsync(d_cs, carry_sums, n_cols * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(d_cc, carry_counts, n_cols * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+    }
+    const uint32_t *d_begin = h->d_twx_groups, *d_slots = h->d_twx_groups + n_groups + 1u;
+    const uint64_t n_waves = n_frames * n_groups;
+    if ((n_waves + 3u) / 4u > 0x7fffffffull || (n_tot + 255u) / 256u > 0x7fffffffull)
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_convergence: more (frame, group) pairs than one launch takes");
+    TIMING_MARK(h, "k_tw_group_rows");
+    hipLaunchKernelGGL(k_tw_group_rows, dim3((uint32_t)((n_waves + 3u) / 4u)), dim3(256), 0, h->stream, h->d_tw_sums, h->d_tw_cnts,
+                       h->plan.n_acc, h->tables.leaflets.method != GORDER_LEAFLETS_NONE ? 1 : 0, (tw_u64)n_frames, n_groups, d_begin, d_slots,
+                       d_rs, d_rc);
+    HIP_TRY(h, hipGetLastError());
+    TIMING_MARK(h, "k_tw_chunk_totals + k_tw_scan_totals + k_tw_apply");
+    const dim3 per_chunk((uint32_t)((n_tot + 255u) / 256u));
+    hipLaunchKernelGGL(k_tw_chunk_totals, per_chunk, dim3(256), 0, h->stream, d_rs, d_rc, (tw_u64)n_frames, n_cols, (tw_u64)n_tot, d_ts, d_tc);
+    HIP_TRY(h, hipGetLastError());
+    hipLaunchKernelGGL(k_tw_scan_totals, dim3(n_cols), dim3(256), 0, h->stream, d_ts, d_tc, (tw_u64)n_chunks, n_cols, d_cs, d_cc, d_es, d_ec);
+    HIP_TRY(h, hipGetLastError());
+    hipLaunchKernelGGL(k_tw_apply, per_chunk, dim3(256), 0, h->stream, d_rs, d_rc, d_ts, d_tc, (tw_u64)n_frames, n_cols, (tw_u64)n_tot,
+                       h->d_twx_out);
+    HIP_TRY(h, hipGetLastError());
+    TIMING_MARK(h, nullptr);
+    HIP_TRY(h, hipMemcpyAsync(prefix, h->d_twx_out, n_rows * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (end_sums) HIP_TRY(h, hipMemcpyAsync(end_sums, d_es, n_cols * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    if (end_counts) HIP_TRY(h, hipMemcpyAsync(end_counts, d_ec, n_cols * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     return GORDER_OK;
 }
 

@@ -45,6 +45,11 @@ __device__ __forceinline__ double dpp_or_zero(double v) {            // two 32-b
     return __hiloint2double(hi, lo);
 }
 template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ unsigned long long dpp_or_zero(unsigned long long v) {   // two 32-bit moves: the exact i64 / u64 sums of kernels_timewise.h
+    const uint32_t lo = dpp_or_zero<CTRL, ROW_MASK>((uint32_t)v), hi = dpp_or_zero<CTRL, ROW_MASK>((uint32_t)(v >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+template <int CTRL, int ROW_MASK = 0xf>
 __device__ __forceinline__ float dpp_or_self(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
 }
@@ -55,8 +60,11 @@ __device__ __forceinline__ float lane_value(float v, int l) { return __int_as_fl
 __device__ __forceinline__ double lane_value(double v, int l) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
 }
+__device__ __forceinline__ unsigned long long lane_value(unsigned long long v, int l) {
+    return ((unsigned long long)lane_value((uint32_t)(v >> 32), l) << 32) | lane_value((uint32_t)v, l);
+}
 
-// ---- row order (int, uint32_t, float, double) -----------------------------------------------------
+// ---- row order (int, uint32_t, unsigned long long, float, double) -----------------------------------------------------
 template <class T>
 __device__ __forceinline__ T row_sum(T v) {             // steps 1-4: lane 15 of every row gets the row's total
     v = v + dpp_or_zero<0x111>(v); v = v + dpp_or_zero<0x112>(v); v = v + dpp_or_zero<0x114>(v); v = v + dpp_or_zero<0x118>(v);
@@ -93,6 +101,12 @@ __device__ __forceinline__ uint32_t wave_scan_rows(uint32_t v, uint32_t lane) {
     const uint32_t t0 = lane_value(v, 15), t1 = lane_value(v, 31), t2 = lane_value(v, 47);
     const uint32_t r = lane >> 4;
     return v + (r > 0u ? t0 : 0u) + (r > 1u ? t1 : 0u) + (r > 2u ? t2 : 0u);
+}
+__device__ __forceinline__ unsigned long long wave_scan_rows(unsigned long long v, uint32_t lane) {
+    v = row_sum(v);
+    const unsigned long long t0 = lane_value(v, 15), t1 = lane_value(v, 31), t2 = lane_value(v, 47);
+    const uint32_t r = lane >> 4;
+    return v + (r > 0u ? t0 : 0ull) + (r > 1u ? t1 : 0ull) + (r > 2u ? t2 : 0ull);
 }
 __device__ __forceinline__ double wave_scan_rows(double v, uint32_t lane) {
     v = row_sum(v);

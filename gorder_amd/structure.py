@@ -427,10 +427,11 @@ def build_tables_ua(structure: Structure, saturated: np.ndarray, unsaturated: np
     return tables, labels, midx
 
 
-def _collector(res: Results, leaflets: bool, sign: float, min_samples: int, timewise, n_blocks: int):
+def _collector(res: Results, leaflets: bool, sign: float, min_samples: int, timewise, n_blocks: int, errors=None):
     """Value of a set of accumulator slots as the writers print it: mean of the summed accumulators (x sign, 4
     decimals, NaN below min_samples); with timewise = (tw_sums, tw_counts) [frames][3][n_acc] the `estimate_error`
-    layout {mean, error}, the error from the members' per-frame rows added up (TimeWiseData merge, timewise.rs:31-76)."""
+    layout {mean, error}, the error from the members' per-frame rows added up (TimeWiseData merge, timewise.rs:31-76);
+    with errors = {tuple(slots): [3] errors} the same layout, the error looked up (HipEngine.error_estimate)."""
     which = ["total", "upper", "lower"] if leaflets else ["total"]
 
     def coll(slots):
@@ -440,22 +441,23 @@ def _collector(res: Results, leaflets: bool, sign: float, min_samples: int, time
             n = int(sum(int(res.counts[w, k]) for k in slots))
             v = _mean_ticks(s, n, min_samples)
             mean = round4(sign * v) if v == v else float("nan")
-            if timewise is None:
+            if timewise is None and errors is None:
                 out[key] = mean
             else:
-                ts = np.asarray(timewise[0])[:, w, slots].sum(axis=1)
-                tc = np.asarray(timewise[1])[:, w, slots].sum(axis=1)
-                e = estimate_error(ts, tc, n_blocks) if mean == mean else float("nan")   # below min_samples: no error either
+                if mean != mean:                # below min_samples: no error either
+                    e = float("nan")
+                elif errors is not None:
+                    e = float(errors[tuple(slots)][w])
+                else:
+                    ts = np.asarray(timewise[0])[:, w, slots].sum(axis=1)
+                    tc = np.asarray(timewise[1])[:, w, slots].sum(axis=1)
+                    e = estimate_error(ts, tc, n_blocks)
                 out[key] = {"mean": mean, "error": round4(e) if e == e else float("nan")}
         return out
     return coll
 
 
-def results_tree_ua(res: Results, labels: Sequence[UaMolLabels], leaflets: bool, min_samples: int = 1,
-                    timewise=None, n_blocks: int = 5) -> dict:
-    """UA YAML shape (uaresults): per carbon `total` (+ upper/lower) and `bonds`: list per virtual hydrogen."""
-    coll = _collector(res, leaflets, -1.0, min_samples, timewise, n_blocks)
-
+def _tree_ua(labels: Sequence[UaMolLabels], coll) -> dict:
     tree: Dict[str, object] = {}
     all_slots: List[int] = []
     for ml in labels:
@@ -472,6 +474,29 @@ def results_tree_ua(res: Results, labels: Sequence[UaMolLabels], leaflets: bool,
         all_slots += mol_slots
         tree[ml.name] = {"average order": coll(mol_slots), "order parameters": op}
     return {"average order": coll(all_slots), **tree}
+
+
+def results_tree_ua(res: Results, labels: Sequence[UaMolLabels], leaflets: bool, min_samples: int = 1,
+                    timewise=None, n_blocks: int = 5, errors=None) -> dict:
+    """UA YAML shape (uaresults): per carbon `total` (+ upper/lower) and `bonds`: list per virtual hydrogen.
+    errors: as in results_tree."""
+    return _tree_ua(labels, _collector(res, leaflets, -1.0, min_samples, timewise, n_blocks, errors))
+
+
+def error_groups(labels, analysis: str) -> List[List[int]]:
+    """The slot lists results_tree / results_tree_ua (whichever fits `labels`) ask an error for, in the order of their
+    first request, each once: what HipEngine.error_estimate takes as `groups`.  dict(zip(map(tuple, groups), errors)) is
+    the `errors` mapping of the tree builders."""
+    seen: Dict[tuple, None] = {}
+
+    def record(slots):
+        seen.setdefault(tuple(int(k) for k in slots))
+        return {}
+    if labels and hasattr(labels[0], "carbons"):
+        _tree_ua(labels, record)
+    else:
+        _tree(labels, analysis, record)
+    return [list(k) for k in seen]
 
 
 # ---- finalisation (presentation layer arithmetic) -------------------------------------------
@@ -521,16 +546,7 @@ def round4(x: float) -> float:
     return float(r / 10000.0)
 
 
-def results_tree(res: Results, labels: Sequence[MolLabels], analysis: str, leaflets: bool, min_samples: int = 1,
-                 timewise=None, n_blocks: int = 5) -> dict:
-    """Nested dict shaped like gorder's YAML output (aaresults.rs:47-61, cgresults.rs:202-217), values
-    rounded to 4 decimals; AA reports -S (presentation/mod.rs:618-625).
-    timewise = (tw_sums, tw_counts) [frames][3][n_acc] switches to the `estimate_error` layout: every value
-    becomes {mean, error}; an aggregate's error comes from its members' per-frame rows added up
-    (TimeWiseData merge, timewise.rs:31-76)."""
-    sign = -1.0 if analysis in ("aa", "ua") else 1.0
-    coll = _collector(res, leaflets, sign, min_samples, timewise, n_blocks)
-
+def _tree(labels: Sequence[MolLabels], analysis: str, coll) -> dict:
     tree: Dict[str, object] = {}
     all_slots: List[int] = []
     for ml in labels:
@@ -556,6 +572,19 @@ def results_tree(res: Results, labels: Sequence[MolLabels], analysis: str, leafl
         mol["order parameters"] = op
         tree[ml.name] = mol
     return {"average order": coll(all_slots), **tree}
+
+
+def results_tree(res: Results, labels: Sequence[MolLabels], analysis: str, leaflets: bool, min_samples: int = 1,
+                 timewise=None, n_blocks: int = 5, errors=None) -> dict:
+    """Nested dict shaped like gorder's YAML output (aaresults.rs:47-61, cgresults.rs:202-217), values
+    rounded to 4 decimals; AA reports -S (presentation/mod.rs:618-625).
+    timewise = (tw_sums, tw_counts) [frames][3][n_acc] switches to the `estimate_error` layout: every value
+    becomes {mean, error}; an aggregate's error comes from its members' per-frame rows added up
+    (TimeWiseData merge, timewise.rs:31-76).
+    errors = {tuple(slots): [3] errors (total, upper, lower)} gives the same layout without the rows: the errors of the
+    groups of error_groups(), e.g. from HipEngine.error_estimate.  The min_samples rule stays here: a NaN mean prints a NaN error."""
+    sign = -1.0 if analysis in ("aa", "ua") else 1.0
+    return _tree(labels, analysis, _collector(res, leaflets, sign, min_samples, timewise, n_blocks, errors))
 
 
 def compare_trees(got, want, tol=2e-4, path="") -> List[str]:

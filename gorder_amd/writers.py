@@ -205,14 +205,46 @@ def xvg_text(tree: dict, molecule: str, header: Optional[str] = None, united: bo
     return "\n".join(out) + "\n"
 
 
-def convergence_text(timewise, labels, analysis: str, leaflets: bool, header: Optional[str] = None, step: int = 1) -> str:
+def convergence_groups(labels) -> list:
+    """The slots of every molecule type, in the order of the labels: the groups whose running averages convergence_text
+    prints (what HipEngine.convergence takes as `groups`)."""
+    out = []
+    for ml in labels:
+        n_slots = sum(c.n_h for c in ml.carbons) if hasattr(ml, "carbons") else len(ml.bonds)
+        out.append(list(range(ml.slot0, ml.slot0 + n_slots)))
+    return out
+
+
+def _prefix_columns(timewise, groups, leaflets: bool = True):
+    """prefix [frames][3][n_groups] float32 from the rows: cumulative tick sum / cumulative sample count by the truncating
+    integer division, / 1e6 as f32; NaN while nothing was sampled (without `leaflets` only [:, 0] is filled in).  (The device's gorder_hip_convergence makes the same.)"""
+    import numpy as np
+    sums, counts = (np.asarray(x) for x in timewise)
+    prefix = np.full((sums.shape[0], 3, len(groups)), np.nan, dtype=np.float32)
+    for g, slots in enumerate(groups):
+        for w in range(3 if leaflets else 1):
+            cs = np.cumsum(sums[:, w, slots].sum(axis=1).astype(np.int64))
+            cn = np.cumsum(counts[:, w, slots].sum(axis=1).astype(np.int64))
+            for f, (s_, n_) in enumerate(zip(cs, cn)):
+                if n_ != 0:
+                    q = abs(int(s_)) // int(n_)
+                    prefix[f, w, g] = np.float32((-q if s_ < 0 else q) / 1e6)
+    return prefix
+
+
+def convergence_text(timewise, labels, analysis: str, leaflets: bool, header: Optional[str] = None, step: int = 1,
+                     prefix=None) -> str:
     """Convergence of the molecule types' average order parameters (TimeWiseData::prefix_average, timewise.rs:259-274;
     presentation/convergence.rs): line n holds, per molecule type (and leaflet), the average over the first n analysed
     frames — cumulative tick sum / cumulative sample count by the truncating integer division, sign as in the
     other outputs.  `timewise` = (sums, counts) [frames][3][n_acc] as returned by the engines; `labels` as from
-    build_tables*; x = the frame's number in the trajectory, 1 + n * step."""
+    build_tables*; x = the frame's number in the trajectory, 1 + n * step.
+    prefix [frames][3][n_molecule_types] (HipEngine.convergence(convergence_groups(labels))): the columns made on the
+    device, in place of `timewise` (which may then be None)."""
     import numpy as np
-    sums, counts = (np.asarray(x) for x in timewise)
+    if prefix is None:
+        prefix = _prefix_columns(timewise, convergence_groups(labels), leaflets)
+    prefix = np.asarray(prefix)
     sign = -1.0 if analysis in ("aa", "ua") else 1.0
     which = ["full", "upper", "lower"] if leaflets else [""]
     out = [header or "# order parameters",
@@ -220,23 +252,12 @@ def convergence_text(timewise, labels, analysis: str, leaflets: bool, header: Op
            '@    xaxis label "Frame number"',
            f'@    yaxis label "{"-Sch" if analysis in ("aa", "ua") else "S"}"']
     cols = []
-    for ml in labels:
-        n_slots = sum(c.n_h for c in ml.carbons) if hasattr(ml, "carbons") else len(ml.bonds)
-        sl = slice(ml.slot0, ml.slot0 + n_slots)
+    for g, ml in enumerate(labels):
         for w, name in enumerate(which):
             out.append(f'@    s{len(cols)} legend "{(ml.name + " " + name).strip()}"')
-            cs = np.cumsum(sums[:, w, sl].sum(axis=1).astype(np.int64))
-            cn = np.cumsum(counts[:, w, sl].sum(axis=1).astype(np.int64))
-            col = []
-            for s_, n_ in zip(cs, cn):
-                if n_ == 0:
-                    col.append(float("nan"))
-                else:
-                    q = abs(int(s_)) // int(n_)
-                    col.append(sign * float(np.float32((-q if s_ < 0 else q) / 1e6)))
-            cols.append(col)
+            cols.append([float("nan") if v != v else sign * float(v) for v in prefix[:, w, g]])
     out.append("@TYPE xy")
-    for f in range(sums.shape[0]):
+    for f in range(prefix.shape[0]):
         out.append(f"{f * step + 1:<4d} " + " ".join(f"{_fixed(c[f]):>8s}" for c in cols) + " ")
     return "\n".join(out) + "\n"
 

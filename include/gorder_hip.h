@@ -425,6 +425,45 @@ int gorder_hip_finish(gorder_hip_handle *h, int64_t *sums, uint64_t *counts, int
 int gorder_hip_timewise(gorder_hip_handle *h, int64_t *tw_sums, uint64_t *tw_counts,
                         uint64_t capacity_frames);
 
+/* Error estimates (TimeWiseData::estimate_error, timewise.rs:191-231) and convergence columns (prefix_average,
+ * timewise.rs:259-274) made from those rows on the device (kernels_timewise.h): what crosses the link is n_blocks x 3 x n_acc
+ * (sum, count) pairs, or one float per (frame, leaflet, group), not the rows.  A group is a list of accumulator slots whose rows
+ * are added (a bond, the bonds of a heavy atom, a molecule type, the whole system), in CSR form: group g =
+ * slots[group_begin[g] .. group_begin[g + 1]).  Everything is exact integer addition up to one truncating division per value, so
+ * the results are those of the host route on gorder_hip_timewise's rows bit for bit, however the frames were batched.
+ * All four calls need tables.timewise = 1, wait for the handle's stream like gorder_hip_finish (a device error of the run is
+ * returned), leave the rows as they are — a later submit followed by a second call sees the longer history — and keep their
+ * scratch in the handle (freed by gorder_hip_destroy); gorder_hip_reset empties the rows, and a call behind it sees none.
+ * GORDER_ERR_INVALID_ARGUMENT with a message: tables.timewise = 0, n_blocks < 2, a slot >= n_acc, an empty group, no group,
+ * group_begin not ascending.  Zero rows, or total_frames / n_blocks == 0: NaN errors, zero block sums, GORDER_OK.
+ * Sharded runs: every rank calls gorder_hip_timewise_blocks with the frame count of the whole analysis and the position of
+ * its first row; the outputs are added element by element (they are plain sums) and one rank calls
+ * gorder_hip_error_estimate with the merged blocks.  Convergence is chained: rank k's end_* are rank k + 1's carry_*. */
+uint32_t gorder_hip_timewise_chunk_frames(void);   /* kTwChunkFrames: rows a workgroup folds; host-only */
+uint64_t gorder_hip_timewise_rows(const gorder_hip_handle *h);   /* rows held (frames analysed since create / reset); host-only, does not wait */
+
+/* block sums of this handle's rows against the block grid of the WHOLE analysis:
+ * block size = total_frames / n_blocks; this handle's row r sits at position first_position + r; positions from
+ * n_blocks * block size on are dropped.  out: [n_blocks][3][n_acc]; partial results of shards add up element by element.
+ * *block_size (may be NULL): the block size used. */
+int gorder_hip_timewise_blocks(gorder_hip_handle *h, uint32_t n_blocks, uint64_t total_frames,
+                               uint64_t first_position, int64_t *block_sums, uint64_t *block_counts,
+                               uint64_t *block_size);
+
+/* errors[n_groups][3] (total, upper, lower; NaN where a block holds no sample — without leaflets: upper and lower).
+ * block_sums/_counts NULL: this handle's own rows (total_frames = its row count, first_position 0); non-NULL: merged
+ * blocks [n_blocks][3][n_acc], uploaded. */
+int gorder_hip_error_estimate(gorder_hip_handle *h, uint32_t n_blocks, const uint32_t *group_begin,
+                              const uint32_t *slots, uint32_t n_groups, const int64_t *block_sums,
+                              const uint64_t *block_counts, float *errors);
+
+/* prefix[n_rows][3][n_groups]: per row the average over the rows up to it (cumulative sum / cumulative count, truncating,
+ * / 1e6 as f32; NaN while the cumulative count is 0; no sign flip).  carry_* / end_* [3][n_groups]: the sums and counts
+ * before this handle's first row (NULL: zero) and behind its last one (may be NULL).  n_rows = gorder_hip_timewise_rows. */
+int gorder_hip_convergence(gorder_hip_handle *h, const uint32_t *group_begin, const uint32_t *slots,
+                           uint32_t n_groups, const int64_t *carry_sums, const uint64_t *carry_counts,
+                           float *prefix, int64_t *end_sums, uint64_t *end_counts);
+
 /* Leaflet flags of the most recent assignment frame, [n_molecules_total] (Upper=0, Lower=1). */
 int gorder_hip_leaflets(gorder_hip_handle *h, uint8_t *flags, uint64_t *assignment_frame);
 /* ---- collected history ("Exporting internal data": LeafletClassification::..with_collect, AssignedLeaflets, NormalsStorage,
