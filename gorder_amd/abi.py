@@ -46,6 +46,7 @@ LEAFLETS_CLUSTERING = 6      # spectral clustering (include/gorder_hip.h): membr
 COLLECT_LEAFLETS, COLLECT_NORMALS = 1, 2   # gorder_collect_t: what HipEngine.set_collect keeps of every frame
 FLAG_TRIG_ACOS_COS = 1
 FLAG_UA_FAST_NORMALISE = 2      # united atoms: tolerance-bounded hydrogen construction (include/gorder_hip.h)
+FLAG_CLUSTER_CUTOFF = 4         # LEAFLETS_CLUSTERING: 6 nm cut-off route for groups of up to 131072 atoms (include/gorder_hip.h)
 UA_CH1_SAT, UA_CH2, UA_CH3, UA_CH1_UNSAT = 1, 2, 3, 4
 UA_N_H = {UA_CH1_SAT: 1, UA_CH2: 2, UA_CH3: 3, UA_CH1_UNSAT: 1}
 

@@ -52,6 +52,7 @@ using gorder::Tile;
 #include "kernels_extras.h"
 #include "kernels_leaflets.h"
 #include "kernels_cluster.h"
+#include "kernels_cluster_cutoff.h"
 #include "kernels_normals.h"
 #include "kernels_xtc.h"
 #include "kernels_trr.h"
@@ -168,6 +169,8 @@ struct gorder_hip_handle {
     uint32_t cl_slab = 1, cl_m_max = 0;
     bool cl_stored_w = false;              // GORDER_HIP_CLUSTER_STORED_W: S v reads W stored once a frame instead of recomputing it
     bool cl_have_carry = false;
+    bool cl_cut = false;                   // GORDER_FLAG_CLUSTER_CUTOFF: kernels_cluster_cutoff.h, its own scratch layout
+    uint32_t cl_tiles = 0, cl_sort = 0;    // row tiles and counting-sort blocks of a frame (cut-off route)
     std::vector<uint8_t> cl_is0;           // per assignment frame of the call in flight: frame_index == 0
     // Local leaflets scratch (sized for local_slab assignment frames)
     uint32_t *d_lcell_of = nullptr, *d_lcell_count = nullptr, *d_lcell_fill = nullptr;
@@ -1152,6 +1155,7 @@ int gorder_hip_plan_tables(const gorder_tables_t *tables, gorder_hip_plan_t *out
 }
 
 static size_t cl_frame_bytes(uint32_t n, uint32_t m_max);
+static size_t clcut_frame_bytes(uint32_t n, uint32_t m_max);
 
 int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
     if (!t || !out) return GORDER_ERR_INVALID_ARGUMENT;
@@ -1170,6 +1174,8 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
     HIP_TRY(h, hipSetDevice(h->device));
     if ((t->flags & GORDER_FLAG_UA_FAST_NORMALISE) && (t->flags & GORDER_FLAG_TRIG_ACOS_COS))
         return fail(h, GORDER_ERR_INVALID_ARGUMENT, "GORDER_FLAG_UA_FAST_NORMALISE (tolerance-bounded) and GORDER_FLAG_TRIG_ACOS_COS (literal) exclude each other");
+    if ((t->flags & GORDER_FLAG_CLUSTER_CUTOFF) && t->leaflets.method != GORDER_LEAFLETS_CLUSTERING)
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "GORDER_FLAG_CLUSTER_CUTOFF needs leaflets.method == GORDER_LEAFLETS_CLUSTERING");
     // united atoms: a wave = 4 slots x 16 molecules (plan.h) — except for per-frame rows and nothing else, where a wave of
     // ONE slot sends a fourth of the atomics (0.433 against 0.449 ms per 3 000 frames of the 256-lipid membrane)
     const bool ua_rows_only = t->timewise && !t->ordermap.enabled && t->geometry.kind == GORDER_GEOM_NONE && !t->dynamic_normal.enabled;
@@ -1417,8 +1423,11 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
             // n x (steps + 1) basis vectors a frame, hence the bound
             if (!lf.membrane || lf.n_membrane < kClMinGroup)
                 return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.n_membrane: clustering needs at least two group atoms");
-            if (lf.n_membrane > kClMaxGroup)
+            h->cl_cut = (t->flags & GORDER_FLAG_CLUSTER_CUTOFF) != 0;
+            if (!h->cl_cut && lf.n_membrane > kClMaxGroup)
                 return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.n_membrane: clustering takes at most 8192 group atoms");
+            if (h->cl_cut && lf.n_membrane > kClCutMaxGroup)
+                return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.n_membrane: clustering with GORDER_FLAG_CLUSTER_CUTOFF takes at most 131072 group atoms");
             std::vector<uint32_t> grp(lf.membrane, lf.membrane + lf.n_membrane);
             std::vector<int32_t> slot_of(t->n_atoms, -1);
             for (uint32_t i = 0; i < lf.n_membrane; i++) {
@@ -1438,7 +1447,10 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
             h->cl_m_max = std::min<uint32_t>(n - 1u, (uint32_t)kClMaxSteps);
             // at most 512 MiB of scratch whatever the batch, at most 1024 frames a launch
             h->cl_stored_w = env_flag("GORDER_HIP_CLUSTER_STORED_W");
-            const size_t per_frame = cl_frame_bytes(n, h->cl_m_max) + (h->cl_stored_w ? (size_t)n * n * 4 : 0);
+            h->cl_tiles = (n + kClCutTile - 1u) / kClCutTile;
+            h->cl_sort = (n + kClCutSort - 1u) / kClCutSort;
+            const size_t per_frame = h->cl_cut ? clcut_frame_bytes(n, h->cl_m_max)
+                                               : cl_frame_bytes(n, h->cl_m_max) + (h->cl_stored_w ? (size_t)n * n * 4 : 0);
             h->cl_slab = (uint32_t)std::min<size_t>(std::max<size_t>(((size_t)512 << 20) / per_frame, 1), 1024);
             HIP_TRY(h, hipMalloc(&h->d_cl_scratch, (size_t)h->cl_slab * per_frame));
             HIP_TRY(h, hipMalloc((void **)&h->d_cl_carry, n));
@@ -1632,7 +1644,88 @@ static size_t cl_frame_bytes(uint32_t n, uint32_t m_max) {
     return cl_round(3 * (size_t)n * 4) + 3 * cl_round((size_t)n * 4) + cl_round((size_t)(m_max + 1u) * n * 4) +
            cl_round(kClSol * 8) + cl_round(n) + cl_round(kClMeta * 4) + 16;
 }
+// the cut-off route's arrays of one frame, in carving order: {bytes}
+static void clcut_sizes(uint32_t n, uint32_t m_max, size_t (&b)[22]) {
+    const size_t tiles = (n + kClCutTile - 1u) / kClCutTile, sort = (n + kClCutSort - 1u) / kClCutSort, nf = cl_round((size_t)n * 4);
+    const size_t v[22] = {cl_round(kClSol * 8), cl_round((size_t)tiles * kClLd * 8), cl_round(kClLd * 8), cl_round(2 * kClLd * 8),
+                          cl_round(kClCutScal * 8), cl_round(sizeof(ClCutGrid)), cl_round(sort * kClCutMaxCells * 4),
+                          cl_round((kClCutMaxCells + 1u) * 4), nf /* cell_of */, nf /* perm */, cl_round(3 * (size_t)n * 4), nf /* s */,
+                          nf /* q */, nf /* emb */, nf /* e0 */, nf /* e1 */, cl_round((size_t)(m_max + 1u) * n * 4),
+                          cl_round(kClMeta * 4), 16 /* fail */, 16 /* done */, cl_round(n) /* lab */, 0};
+    for (int k = 0; k < 22; k++) b[k] = v[k];
+}
+static size_t clcut_frame_bytes(uint32_t n, uint32_t m_max) {
+    size_t b[22], sum = 0;
+    clcut_sizes(n, m_max, b);
+    for (size_t v : b) sum += v;
+    return sum;
+}
+// GORDER_FLAG_CLUSTER_CUTOFF: the launches of kernels_cluster_cutoff.h.  The whole step budget is queued; a frame that has
+// converged sets its `done` word on the device and its workgroups leave at once — nothing is read back here.
+static int run_clustering_cutoff(gorder_hip_handle *h, const float *d_xyz, const float *d_box, size_t n_assign, uint32_t row0) {
+    const gorder_leaflets_t &lf = h->tables.leaflets;
+    const uint32_t n = lf.n_membrane, slab = h->cl_slab, tiles = h->cl_tiles, sort = h->cl_sort;
+    size_t bytes[22];
+    clcut_sizes(n, h->cl_m_max, bytes);
+    ClCutArgs ca{};
+    ca.c.xyz = d_xyz; ca.c.box9 = d_box; ca.c.n_atoms = h->plan.n_atoms; ca.c.group = h->d_membrane; ca.c.n = n;
+    ca.c.pbc = h->tables.handle_pbc ? 1 : 0; ca.c.m_max = h->cl_m_max; ca.c.err = h->d_err; ca.c.W = nullptr;
+    ca.n_tiles = tiles; ca.n_sort = sort;
+    char *base = (char *)h->d_cl_scratch;
+    int at = 0;
+    auto carve = [&]() { char *p = base; base += bytes[at++] * slab; return p; };
+    ca.c.sol = (double *)carve(); ca.part = (double *)carve(); ca.coef = (double *)carve(); ca.albe = (double *)carve();
+    ca.scal = (double *)carve(); ca.grid = (ClCutGrid *)carve(); ca.cnt = (uint32_t *)carve(); ca.cell_start = (uint32_t *)carve();
+    ca.cell_of = (uint32_t *)carve(); ca.perm = (uint32_t *)carve(); ca.c.pos = (float *)carve(); ca.c.s = (float *)carve();
+    ca.c.q = (float *)carve(); ca.c.emb = (float *)carve(); ca.e0 = (float *)carve(); ca.e1 = (float *)carve();
+    ca.c.V = (float *)carve(); ca.c.meta = (float *)carve(); ca.c.fail = (uint32_t *)carve(); ca.done = (uint32_t *)carve();
+    ca.c.lab = (uint8_t *)carve();
+    ClOrientArgs oa{};
+    oa.n = n; oa.lab = ca.c.lab; oa.emb = ca.c.emb; oa.meta = ca.c.meta; oa.fail = ca.c.fail; oa.carry = h->d_cl_carry;
+    oa.aflags = h->d_aflags; oa.n_mol_total = h->plan.n_mol_total; oa.head_slot = h->d_cl_head_slot;
+    oa.flip = lf.flip ? 1 : 0; oa.err = h->d_err; oa.is_frame0 = h->d_cl_is0;
+    for (size_t done = 0; done < n_assign; done += slab) {
+        const uint32_t ns = (uint32_t)std::min<size_t>(n_assign - done, slab);
+        const bool last = done + ns == n_assign;
+        ca.c.aframes = h->d_aframes + done; ca.c.n_assign = ns;
+        oa.aframes = ca.c.aframes; oa.n_assign = ns; oa.row0 = row0 + (uint32_t)done;
+        oa.adist = last ? h->d_adist : nullptr;
+        oa.stats = last ? h->d_cl_stats : nullptr;
+        const dim3 rows(tiles, ns), blocks(sort, ns);
+        HIP_TRY(h, hipMemsetAsync(ca.c.fail, 0, (size_t)ns * sizeof(uint32_t), h->stream));
+        HIP_TRY(h, hipMemsetAsync(ca.done, 0, (size_t)ns * sizeof(uint32_t), h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->d_cl_is0, h->cl_is0.data() + done, ns, hipMemcpyHostToDevice, h->stream));
+        TIMING_MARK(h, "k_clcut_cells");
+        hipLaunchKernelGGL(k_clcut_grid, dim3(ns), dim3(256), 0, h->stream, ca);
+        hipLaunchKernelGGL(k_clcut_count, blocks, dim3(1024), 0, h->stream, ca);
+        hipLaunchKernelGGL(k_clcut_scan, dim3(ns), dim3(1024), 0, h->stream, ca);
+        hipLaunchKernelGGL(k_clcut_scatter, blocks, dim3(1024), 0, h->stream, ca);
+        TIMING_MARK(h, "k_clcut_lanczos");
+        hipLaunchKernelGGL(k_clcut_degrees, rows, dim3(kClCutTile), 0, h->stream, ca);
+        hipLaunchKernelGGL(k_clcut_start, dim3(ns), dim3(1024), 0, h->stream, ca);
+        for (int j = 0; j < (int)h->cl_m_max; j++) {
+            hipLaunchKernelGGL(k_clcut_spmv, rows, dim3(kClCutTile), 0, h->stream, ca, j);
+            hipLaunchKernelGGL(k_clcut_coef, dim3(ns), dim3(512), 0, h->stream, ca, j, 0);
+            hipLaunchKernelGGL(k_clcut_update, rows, dim3(kClCutTile), 0, h->stream, ca, j, 0);
+            hipLaunchKernelGGL(k_clcut_dots, rows, dim3(kClCutTile), 0, h->stream, ca, j);
+            hipLaunchKernelGGL(k_clcut_coef, dim3(ns), dim3(512), 0, h->stream, ca, j, 1);
+            hipLaunchKernelGGL(k_clcut_update, rows, dim3(kClCutTile), 0, h->stream, ca, j, 1);
+            hipLaunchKernelGGL(k_clcut_small, dim3(ns), dim3(1024), 0, h->stream, ca, j);
+            hipLaunchKernelGGL(k_clcut_scale, rows, dim3(kClCutTile), 0, h->stream, ca, j);
+        }
+        TIMING_MARK(h, "k_clcut_embed");
+        hipLaunchKernelGGL(k_clcut_ritz, rows, dim3(kClCutTile), 0, h->stream, ca);
+        hipLaunchKernelGGL(k_clcut_embed, dim3(ns), dim3(1024), 0, h->stream, ca);
+        TIMING_MARK(h, "k_cluster_orient");
+        hipLaunchKernelGGL(k_cluster_orient, dim3(1), dim3(1024), 0, h->stream, oa);
+        HIP_TRY(h, hipGetLastError());
+    }
+    h->cl_have_carry = true;
+    return GORDER_OK;
+}
+
 static int run_clustering(gorder_hip_handle *h, const float *d_xyz, const float *d_box, size_t n_assign, uint32_t row0) {
+    if (h->cl_cut) return run_clustering_cutoff(h, d_xyz, d_box, n_assign, row0);
     const gorder_leaflets_t &lf = h->tables.leaflets;
     const uint32_t n = lf.n_membrane, slab = h->cl_slab;
     ClArgs ca{};

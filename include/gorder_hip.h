@@ -111,6 +111,8 @@ typedef enum {
                                         result is "the precise result, when they succeed", and are not reproduced.
                                         `membrane` / `n_membrane` carry the group, ascending and distinct, 2 <= n_membrane <=
                                         8192 (dense route: the scratch holds n x 301 floats a frame, 512 MiB at most);
+                                        with GORDER_FLAG_CLUSTER_CUTOFF (below) 2 <= n_membrane <= 131072: the same definition
+                                        with W_ij = 0 where d_ij^2 >= 36 nm^2, spread over the device;
                                         each molecule's heads[k] is its own atom of the group; normal_dim and radius unused */
 } gorder_leaflet_method_t;
 
@@ -227,10 +229,22 @@ typedef struct {
  *   stays within one 1e-6 tick; single samples move more often than with the default (a hydrogen position is
  *   target + 0.109 nm * unit vector rounded to the grid of the target's coordinates, so an ulp in the unit vector
  *   flips that rounding in ~1 % of the components): measured in profiles/r04_ua_fast_fidelity.json.  Not with
- *   GORDER_FLAG_TRIG_ACOS_COS (gorder_hip_create refuses the pair).  The default path is bit-unchanged. */
+ *   GORDER_FLAG_TRIG_ACOS_COS (gorder_hip_create refuses the pair).  The default path is bit-unchanged.
+ * GORDER_FLAG_CLUSTER_CUTOFF (GORDER_LEAFLETS_CLUSTERING only, opt-in; any other method: gorder_hip_create refuses): the
+ *   clustering definition truncated where f32 cannot see the difference — W_ij = expf(-d_ij^2) where d_ij^2 < 36 nm^2 (the
+ *   reference's cut-off distance, 6 nm) and 0 otherwise, d_ij the one 3-D minimum image of the pair also where a box edge is
+ *   shorter than 12 nm; expf(-36) = 2.3e-16 adds nothing to a degree that is at least 1.  Everything else (sigma, the
+ *   deflation of D^1/2 1, 300 Lanczos steps at most with the same start vector, tolerances, row normalisation, 2-means,
+ *   orientation, errors, statistics, priming, frequency, flip, collection) is the method's as stated above.  The group may
+ *   hold 2 <= n_membrane <= 131072 atoms.  The heads go into a cell list per assignment frame (cells of at least 6 nm; without
+ *   handle_pbc over the heads' bounding box), every row of S v is summed over the cells around its own in a fixed order, and
+ *   a frame is spread over the whole device, one launch per Lanczos step and kind of work: a frame's flags and statistics
+ *   depend on the frame alone.  Sums are associated in another order than on the dense route, so statistics agree with it
+ *   to rounding, not bit for bit.  Without the flag nothing changes, the refusal above 8192 atoms included. */
 typedef enum {
     GORDER_FLAG_TRIG_ACOS_COS = 1u,
-    GORDER_FLAG_UA_FAST_NORMALISE = 2u
+    GORDER_FLAG_UA_FAST_NORMALISE = 2u,
+    GORDER_FLAG_CLUSTER_CUTOFF = 4u
 } gorder_flags_t;
 
 typedef struct {
@@ -583,7 +597,8 @@ const char *gorder_hip_strerror(int status);
 /* Device time of the submits since the last call with reset != 0 (ms, HIP events on the stream the handle launches on) and
  * their number.  The first call switches the timing on; submits before it are not timed.  A submit is timed as a chain of
  * segments, one per kernel group it queues — the leaflet kernels ("k_leaflets_global_contig"; "k_leaflets_spherical";
- * "k_cluster_degrees", "k_cluster_lanczos", "k_cluster_embed", "k_cluster_orient" per slab of frames; "k_local_build",
+ * "k_cluster_degrees", "k_cluster_lanczos", "k_cluster_embed", "k_cluster_orient" per slab of frames (with
+ * GORDER_FLAG_CLUSTER_CUTOFF: "k_clcut_cells", "k_clcut_lanczos", "k_clcut_embed", "k_cluster_orient"); "k_local_build",
  * "k_local_rowprefix", "k_local_flags_rows", "k_local_flags_todo" per 256-frame slab; ...), "k_dyn_cov + k_dyn_eigen",
  * "k_geom_shapes", the order kernels ("k_bonds_tiled", "k_ua_extras", "k_bonds_tiled_maps", ...), "k_map_accumulate",
  * "k_bonds_direct", with manual tables "k_replay_flags" and "k_replay_normals" (ahead of the order kernels), with collection

@@ -10,7 +10,10 @@ and a buckled one of 3 000 lipids (synthetic.cg_buckled) — go through the same
   manual_host      LEAFLETS_MANUAL, the only route before: per frame the heads copied back, the method in numpy (dense eigh
                    after projecting out D^1/2 1, 2-means, orientation by overlap), set_manual_leaflets, a submit per frame
 A run whose frames the method cannot match (GORDER_ERR_CLUSTER_MATCH at the synchronise, after all the work) is timed all the
-same and listed under "statuses".  Times are host clocks around submits that end in a synchronise (median of the repetitions, the routes alternating).  The GPU
+same and listed under "statuses".
+With --cutoff the tool measures GORDER_FLAG_CLUSTER_CUTOFF instead (default --out profiles/cluster_cutoff_bench.json): the
+buckled 3 000-lipid membrane on the dense and the cut-off route in one run (every frame and once), cg_buckled(n_lipids=8400,
+box=(84, 28, 16)) and a 32 768-lipid membrane (box 166 x 56 x 16) on the cut-off route alone.  Times are host clocks around submits that end in a synchronise (median of the repetitions, the routes alternating).  The GPU
 work runs in a child process under a time limit; the parent prints ONE JSON line (and writes it to --out)."""
 import argparse
 import json
@@ -174,6 +177,85 @@ def measure(name, tables, d_xyz, d_box, box, F, reps, manual_frames):
     }
 
 
+def measure_cutoff(name, make, F, reps, dense):
+    """frames/s of the cut-off route (and of the dense route on the same frames) every frame and once."""
+    import copy
+    import numpy as np
+    from gorder_amd import HipEngine
+    from gorder_amd.abi import FLAG_CLUSTER_CUTOFF, LEAFLETS_CLUSTERING, GorderHipError
+    ref = make(leaflets=LEAFLETS_CLUSTERING, frequency=1)[0]
+    d_xyz, d_box = ref.frames_device(F, seed=1)
+    tables = {"dense": ref.tables, "dense_once": make(leaflets=LEAFLETS_CLUSTERING, frequency=0)[0].tables}
+    for k in ("dense", "dense_once"):
+        t = copy.copy(tables[k])
+        t.flags = t.flags | FLAG_CLUSTER_CUTOFF
+        tables["cutoff" + k[5:]] = t
+    order = [k for k in ("dense", "cutoff", "dense_once", "cutoff_once") if dense or not k.startswith("dense")]
+    engines = {k: HipEngine(tables[k]) for k in order}
+    statuses = {}
+    for e in engines.values():
+        e.use_torch_stream()
+
+    def run(route):
+        e = engines[route]
+        e.reset()
+        t0 = time.perf_counter()
+        e.submit_device(d_xyz, d_box)
+        try:
+            e.synchronize()
+        except GorderHipError as err:
+            statuses[route] = err.status
+        return (time.perf_counter() - t0) / F
+    for route in order:
+        run(route)
+    per_frame = {k: [] for k in order}
+    for _ in range(reps):
+        for route in order:
+            per_frame[route].append(run(route))
+    flags, stats = {}, {}
+    for route in order:
+        if route.endswith("_once"):
+            continue
+        engines[route].reset()
+        engines[route].submit_device(d_xyz[:1], d_box[:1], np.array([0]))
+        flags[route], stats[route] = engines[route].leaflets()[0], engines[route].clustering_stats()
+    e = engines["cutoff"]
+    e.kernel_time(reset=True)
+    e.reset()
+    e.submit_device(d_xyz, d_box)
+    try:
+        e.synchronize()
+    except GorderHipError:
+        pass
+    groups = {g: ms for g, ms, _ in e.kernel_groups()}
+    e.kernel_time(reset=True)
+    med = {k: float(np.median(v)) for k, v in per_frame.items()}
+    out = {"system": name, "atoms_per_frame": int(d_xyz.shape[1]), "heads": len(ref.tables.leaflets.membrane), "frames": F,
+           "reps": reps, "statuses": statuses, "frames_per_s": {k: 1.0 / v for k, v in med.items()},
+           "seconds_per_frame_spread": {k: [float(min(v)), float(max(v))] for k, v in per_frame.items()},
+           "device_ms_per_frame": {g: ms / F for g, ms in groups.items() if g.startswith("k_cl")},
+           "lanczos_steps_frame_0": {k: v["steps"] for k, v in stats.items()}}
+    if dense:
+        out["flags_cutoff_equal_dense"] = bool(np.array_equal(flags["cutoff"], flags["dense"]))
+        out["cutoff_over_dense_time"] = med["cutoff"] / med["dense"]
+        out["cutoff_once_over_dense_once_time"] = med["cutoff_once"] / med["dense_once"]
+    return out
+
+
+def child_cutoff(args):
+    import torch
+    from gorder_amd import synthetic
+    assert torch.cuda.is_available(), "cluster_bench needs a GPU"
+    out = {"tool": "tools/cluster_bench.py --cutoff", "device": torch.cuda.get_device_name(0), "systems": [
+        measure_cutoff("buckled3000", lambda **kw: synthetic.cg_buckled(n_lipids=3000, **kw), args.frames_large, args.reps, True),
+        measure_cutoff("buckled8400", lambda **kw: synthetic.cg_buckled(n_lipids=8400, box=(84.0, 28.0, 16.0), **kw), 16,
+                       args.reps, False),
+        measure_cutoff("buckled32768", lambda **kw: synthetic.cg_buckled(n_lipids=32768, box=(166.0, 56.0, 16.0), **kw), 4,
+                       args.reps, False),
+    ]}
+    print("CLUSTER_BENCH " + json.dumps(out))
+
+
 def child(args):
     import torch
     from gorder_amd import synthetic
@@ -195,9 +277,12 @@ def main():
     ap.add_argument("--timeout", type=int, default=540)
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", action="store_true")
+    ap.add_argument("--cutoff", action="store_true")
     args = ap.parse_args()
+    if args.cutoff and args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "cluster_cutoff_bench.json")
     if args.child:
-        return child(args)
+        return child_cutoff(args) if args.cutoff else child(args)
     cmd = [sys.executable, os.path.abspath(__file__), "--child"] + [a for a in sys.argv[1:] if a != "--child"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
     line = next((ln for ln in res.stdout.splitlines() if ln.startswith("CLUSTER_BENCH ")), None)
