@@ -325,7 +325,7 @@ _EXPORTS = [
     "gorder_hip_set_collect", "gorder_hip_collected_counts", "gorder_hip_collected_leaflets", "gorder_hip_collected_normals",
     "gorder_hip_set_manual_leaflet_table", "gorder_hip_set_manual_normal_table",
     "gorder_hip_timewise_chunk_frames", "gorder_hip_timewise_rows", "gorder_hip_timewise_blocks", "gorder_hip_error_estimate",
-    "gorder_hip_convergence",
+    "gorder_hip_convergence", "gorder_hip_ordermaps",
 ]
 
 _lib = None
@@ -425,6 +425,7 @@ def load_library() -> C.CDLL:
     lib.gorder_hip_timewise_blocks.argtypes = [vp, u32, u64, u64, vp, vp, C.POINTER(u64)]
     lib.gorder_hip_error_estimate.argtypes = [vp, u32, vp, vp, u32, vp, vp, vp]
     lib.gorder_hip_convergence.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp]
+    lib.gorder_hip_ordermaps.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, u64, vp]
     _lib = lib
     return lib
 
@@ -791,6 +792,34 @@ class HipEngine:
                                                     prefix.ctypes.data_as(C.c_void_p), es.ctypes.data_as(C.c_void_p),
                                                     ec.ctypes.data_as(C.c_void_p)))
         return prefix, (es, ec)
+
+    def ordermaps(self, groups, min_samples: int = 1, negate: bool = True, device_maps=None) -> np.ndarray:
+        """The finished ordermap of every group (a list of accumulator slots whose tiles are added) and plane, made on the
+        device (gorder_hip_ordermaps) -> float32 [n_groups, 3, nx, ny] (total, upper, lower; NaN below min_samples, and in
+        the upper and lower planes without leaflets), bit for bit structure.ordermap_values on finish()'s maps.
+        negate: True for all-atom and united-atom analyses (-S), False for coarse-grained.
+        device_maps = (sums, counts): two torch.int64 CUDA tensors in export_maps' layout — the maps of several ranks added
+        up — instead of this handle's own maps."""
+        begin, slots = _pack_groups(groups)
+        nx, ny = self.ordermap_dims()
+        out = np.zeros((len(groups), 3, nx, ny), dtype=np.float32)
+        buf = out if out.size else np.zeros(1, dtype=np.float32)      # (never a null pointer: the library names what is wrong)
+        ds = dc = None
+        n_u64 = 0
+        if device_maps is not None:
+            import torch
+            ds, dc = device_maps
+            for t in (ds, dc):
+                assert t.is_cuda and t.is_contiguous() and t.element_size() == 8
+            assert ds.numel() == dc.numel()
+            n_u64 = ds.numel()
+            torch.cuda.synchronize(ds.device)          # the tensors are torch's work: complete before the handle's stream reads them
+        self._check(self.lib.gorder_hip_ordermaps(self._h, begin.ctypes.data_as(C.c_void_p), slots.ctypes.data_as(C.c_void_p), len(groups),
+                                                  int(min_samples), 1 if negate else 0,
+                                                  None if ds is None else C.c_void_p(ds.data_ptr()),
+                                                  None if dc is None else C.c_void_p(dc.data_ptr()), n_u64,
+                                                  buf.ctypes.data_as(C.c_void_p)))
+        return out
 
     def leaflets(self):
         flags = np.zeros(self.tables.n_molecules_total, dtype=np.uint8)

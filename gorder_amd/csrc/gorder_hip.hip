@@ -38,6 +38,7 @@
 #include "collect_store.h"
 #include "replay_rows.h"
 #include "timewise_blocks.h"
+#include "ordermap_final.h"
 
 #pragma clang fp contract(off)
 
@@ -59,6 +60,7 @@ using gorder::Tile;
 #include "kernels_collect.h"
 #include "kernels_replay.h"
 #include "kernels_timewise.h"
+#include "kernels_ordermap.h"
 
 // ============================================================================================
 // host side
@@ -120,6 +122,10 @@ struct gorder_hip_handle {
     uint32_t *d_twx_groups = nullptr;
     float *d_twx_out = nullptr;
     size_t twx_blocks_cap = 0, twx_rows_cap = 0, twx_totals_cap = 0, twx_edge_cap = 0, twx_groups_cap = 0, twx_out_cap = 0;
+    // scratch of gorder_hip_ordermaps (kernels_ordermap.h): the groups in CSR form, the finished maps [n_groups][3][nx*ny]
+    uint32_t *d_omx_groups = nullptr;
+    float *d_omx_out = nullptr;
+    size_t omx_groups_cap = 0, omx_out_cap = 0;
     ExtraArgs extra{};
     uint32_t *d_geom_group = nullptr;
     float *d_shapes = nullptr;
@@ -1536,6 +1542,7 @@ void gorder_hip_destroy(gorder_hip_handle *h) {
     (void)hipFree(h->d_ua_tiles); (void)hipFree(h->d_ua_items); (void)hipFree(h->d_ua_tile_slots);
     (void)hipFree(h->d_map_sums); (void)hipFree(h->d_map_cnts); (void)hipFree(h->d_map_packed); (void)hipFree(h->d_tw_sums); (void)hipFree(h->d_tw_cnts);
     (void)hipFree(h->d_twx_blocks); (void)hipFree(h->d_twx_rows); (void)hipFree(h->d_twx_totals); (void)hipFree(h->d_twx_edge); (void)hipFree(h->d_twx_groups); (void)hipFree(h->d_twx_out);
+    (void)hipFree(h->d_omx_groups); (void)hipFree(h->d_omx_out);
     (void)hipFree(h->d_geom_group); (void)hipFree(h->d_shapes); (void)hipFree(h->d_inv_box);
     (void)hipFree(h->d_map_rec); (void)hipFree(h->d_ua_runs); (void)hipFree(h->d_ua_run_begin);
     (void)hipFree(h->d_runs); (void)hipFree(h->d_run_begin); (void)hipFree(h->d_items_by_slot);
@@ -2602,6 +2609,49 @@ int gorder_hip_convergence(gorder_hip_handle *h, const uint32_t *group_begin, co
     if (end_sums) HIP_TRY(h, hipMemcpyAsync(end_sums, d_es, n_cols * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     if (end_counts) HIP_TRY(h, hipMemcpyAsync(end_counts, d_ec, n_cols * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return GORDER_OK;
+}
+
+// ---- ordermaps finished on the device (kernels_ordermap.h, ordermap_final.h) ---------------------------------------------
+int gorder_hip_ordermaps(gorder_hip_handle *h, const uint32_t *group_begin, const uint32_t *slots, uint32_t n_groups,
+                         uint32_t min_samples, uint32_t negate, const void *d_sums, const void *d_counts, uint64_t n_u64, float *maps) {
+    if (!h) return GORDER_ERR_INVALID_ARGUMENT;
+    const std::string who = "gorder_hip_ordermaps: ";
+    if (!h->extra.maps) return fail(h, GORDER_ERR_INVALID_ARGUMENT, who + "the handle keeps no ordermaps (tables.ordermap.enabled = 0)");
+    if (!maps) return fail(h, GORDER_ERR_INVALID_ARGUMENT, who + "null output");
+    if ((d_sums == nullptr) != (d_counts == nullptr)) return fail(h, GORDER_ERR_INVALID_ARGUMENT, who + "only one of d_sums / d_counts");
+    const uint32_t n_acc = h->plan.n_acc;
+    gorder::TwGroupStatus gs = gorder::kTwGroupsOk;
+    uint32_t bad = 0;
+    const gorder::OmStatus os = gorder::om_check(group_begin, slots, n_groups, n_acc, min_samples, &gs, &bad);
+    if (os == gorder::kOmMinSamples) return fail(h, GORDER_ERR_INVALID_ARGUMENT, who + "min_samples must be at least 1");
+    if (os != gorder::kOmOk)
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, who + gorder::tw_group_status_text(gs) + " (at " + std::to_string(bad) + ")");
+    const uint64_t n_tiles = (uint64_t)h->map_nx * h->map_ny, n_words = gorder::om_map_words(n_acc, h->map_nx, h->map_ny);
+    if (d_sums && n_u64 != n_words)
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, who + "n_u64 is " + std::to_string(n_u64) + ", the maps hold " + std::to_string(n_words) + " words");
+    const uint64_t tile_blocks = (n_tiles + 255u) / 256u, n_blocks = (uint64_t)n_groups * 3u * tile_blocks;
+    if (n_blocks > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, who + "more (group, tile) pairs than one launch takes");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int st = fold_maps(h);
+    if (st != GORDER_OK) return st;
+    if ((st = gorder_hip_synchronize(h)) != GORDER_OK) return st;        // a device error of the run is returned here
+    std::vector<uint32_t> csr((size_t)n_groups + 1u);
+    for (uint32_t g = 0; g <= n_groups; g++) csr[g] = group_begin[g] - group_begin[0];
+    csr.insert(csr.end(), slots + group_begin[0], slots + group_begin[n_groups]);
+    if ((st = ensure(h, &h->d_omx_groups, &h->omx_groups_cap, csr.size())) != GORDER_OK) return st;
+    const size_t n_out = (size_t)n_groups * 3u * n_tiles;
+    if ((st = ensure(h, &h->d_omx_out, &h->omx_out_cap, n_out)) != GORDER_OK) return st;
+    HIP_TRY(h, hipMemcpyAsync(h->d_omx_groups, csr.data(), csr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    TIMING_MARK(h, "k_map_finalise");
+    hipLaunchKernelGGL(k_map_finalise, dim3((uint32_t)n_blocks), dim3(256), 0, h->stream,
+                       d_sums ? (const om_u64 *)d_sums : h->d_map_sums, d_counts ? (const om_u64 *)d_counts : h->d_map_cnts, n_acc,
+                       (om_u64)n_tiles, (uint32_t)tile_blocks, h->tables.leaflets.method != GORDER_LEAFLETS_NONE ? 3u : 1u,
+                       h->d_omx_groups, h->d_omx_groups + n_groups + 1u, min_samples, negate ? 1 : 0, h->d_omx_out);
+    HIP_TRY(h, hipGetLastError());
+    TIMING_MARK(h, nullptr);
+    HIP_TRY(h, hipMemcpyAsync(maps, h->d_omx_out, n_out * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));      // (csr leaves scope)
     return GORDER_OK;
 }
 

@@ -537,6 +537,91 @@ def estimate_error(sums: np.ndarray, counts: np.ndarray, n_blocks: int = 5) -> f
     return float(np.sqrt(np.float32(var / np.float32(n_blocks - 1)), dtype=np.float32))
 
 
+# ---- ordermaps: which maps the reference writes, and their values (presentation layer arithmetic) ----------
+@dataclass
+class OrdermapGroup:
+    """One slot set of error_groups and every file the reference writes its map to: (sub-directory — '' for the top of the
+    ordermap directory —, file stem without `_full` / `_upper` / `_lower`, first comment line).  A set has more than one
+    file where the reference writes equal maps twice: a carbon with a single hydrogen and that bond, a system of one
+    molecule type and that type."""
+    slots: List[int]
+    files: List[Tuple[str, str, str]]
+
+
+def ordermap_groups(labels, analysis: str) -> List[OrdermapGroup]:
+    """The maps of the reference's ordermap directory (presentation/ordermaps_presenter.rs:110-322) as groups of
+    accumulator slots: the slot sets are error_groups(labels, analysis) in its order — what HipEngine.ordermaps and
+    ordermap_values take as `groups` is [g.slots for g in ...] — each with its file names and comment lines."""
+    files: Dict[tuple, List[Tuple[str, str, str]]] = {}
+    head = "# Map of average order parameters calculated for "
+
+    def add(slots, directory, stem, comment):
+        files.setdefault(tuple(int(k) for k in slots), []).append((directory, stem, head + comment))
+
+    all_slots: List[int] = []
+    for ml in labels:
+        if hasattr(ml, "carbons"):
+            slot, mol_slots = ml.slot0, []
+            for c in ml.carbons:
+                slots = list(range(slot, slot + c.n_h))
+                slot += c.n_h
+                mol_slots += slots
+                atom = f"{c.res or ml.name}-{c.name}-{c.rel}"
+                add(slots, ml.name, f"ordermap_{atom}", f"an atom type {atom} of a molecule type {ml.name}.")
+                for k, sl in enumerate(slots):
+                    add([sl], ml.name, f"ordermap_{atom}--{c.res or ml.name}-H{k + 1}-{c.rel}",
+                        f"bonds between an atom type {atom} and a virtual hydrogen #{k + 1} of molecule type {ml.name}.")
+        else:
+            mol_slots = list(range(ml.slot0, ml.slot0 + len(ml.bonds)))
+
+            def bond_file(k, b):
+                a1, a2 = f"{b.res1 or ml.name}-{b.name1}-{b.rel1}", f"{b.res2 or ml.name}-{b.name2}-{b.rel2}"
+                add([ml.slot0 + k], ml.name, f"ordermap_{a1}--{a2}",
+                    f"bonds between atom types {a1} and {a2} of a molecule type {ml.name}.")
+            if analysis == "aa":
+                for rel, name, resn in ml.heavy_atoms:
+                    mine = [(k, b) for k, b in enumerate(ml.bonds) if b.rel1 == rel or b.rel2 == rel]
+                    if not mine:
+                        continue
+                    atom = f"{resn or ml.name}-{name}-{rel}"
+                    add([ml.slot0 + k for k, _ in mine], ml.name, f"ordermap_{atom}",
+                        f"an atom type {atom} of a molecule type {ml.name}.")
+                    for k, b in mine:
+                        bond_file(k, b)
+            else:
+                for k, b in enumerate(ml.bonds):
+                    bond_file(k, b)
+        add(mol_slots, ml.name, "ordermap_average", f"a molecule type {ml.name}.")
+        all_slots += mol_slots
+    add(all_slots, "", "ordermap_average", "all bonds of all molecule types.")
+    groups = error_groups(labels, analysis)
+    if set(map(tuple, groups)) != set(files):
+        raise ValueError("the labels' slot sets and their ordermap files do not match")
+    return [OrdermapGroup(list(g), files[tuple(g)]) for g in groups]
+
+
+def ordermap_values(res: Results, groups, min_samples: int = 1, negate: bool = True) -> np.ndarray:
+    """Finished ordermaps float32 [n_groups, 3, nx, ny] from Results.map_sums / map_counts by the reference's sequence
+    (ResultsConverter::convert_ordermap, converter.rs:226-256): the members' tiles added, NaN below min_samples, else
+    f32(f64(sum) / 1e6) / f32(count) in f32, negated for all-atom and united-atom analyses (a zero sum gives -0.0).  Not
+    calc_order's truncating division (_mean_ticks): a map divides floats.  HipEngine.ordermaps makes the same on the device."""
+    if min_samples < 1:
+        raise ValueError("min_samples must be at least 1")
+    sums, counts = np.asarray(res.map_sums, dtype=np.int64), np.asarray(res.map_counts, dtype=np.uint64)
+    out = np.empty((len(groups),) + sums.shape[:1] + sums.shape[2:], dtype=np.float32)
+    for g, slots in enumerate(groups):
+        slots = [int(k) for k in slots]
+        s = sums[:, slots].sum(axis=1, dtype=np.int64)
+        c = counts[:, slots].sum(axis=1, dtype=np.uint64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            v = (s.astype(np.float64) / 1e6).astype(np.float32) / c.astype(np.float32)
+        if negate:
+            v = -v
+        v[c < np.uint64(min_samples)] = np.nan
+        out[g] = v
+    return out
+
+
 def round4(x: float) -> float:
     """RoundTo4 (presentation/mod.rs:496-504): (x as f64 * 10000).round() / 10000, half away from zero."""
     if x != x:

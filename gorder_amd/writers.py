@@ -2,7 +2,9 @@
 YAML (presentation/yaml_presenter.rs:80-136: nested mapping, values rounded to 4 decimals, NaN as `.nan`) and CSV
 (presentation/csv_presenter.rs: one line per heavy atom or coarse-grained bond, fixed 4 decimals, NaN as `NaN`, empty
 fields for hydrogens an atom does not have).  Both can be compared with the reference's files by its own rule
-(tests/common/mod.rs:95-150: same items line by line, numbers within 2e-4)."""
+(tests/common/mod.rs:95-150: same items line by line, numbers within 2e-4).  Ordermaps: the `.dat` files and the directory
+tree of presentation/ordermaps_presenter.rs, from the values of `HipEngine.ordermaps` / `structure.ordermap_values`."""
+import os
 import re
 from typing import List, Optional
 
@@ -313,3 +315,54 @@ def normals_export_text(normals, frames, labels, header: Optional[str] = None) -
             out.append(f"# Frame index {int(f) + 1}")
             out.append("  - [" + ",".join("[" + ",".join(_component(c) for c in v) + "]" for v in row[cols]) + "]")
     return "\n".join(out) + "\n"
+
+
+_PLANE_LABELS = {0: ("x", "y"), 1: ("x", "z"), 2: ("z", "y")}     # Plane::get_labels (input/ordermap.rs:54-60)
+_LEAFLET_NAMES = ("full", "upper", "lower")
+
+
+def ordermap_text(values, ordermap, analysis: str, comment: str, calculated_with: str = "gorder_amd") -> str:
+    """One ordermap file (write_ordermap, presentation/ordermaps_presenter.rs:352-385) from the values [nx, ny] of one group
+    and plane: `comment` (the line ordermap_groups gives) and the line naming the program, the axis labels of the plane, the
+    z label and range of the analysis type, then `x y value` per tile, x-major, four decimals, NaN as `NaN`.  A tile sits at
+    span minimum + index * bin."""
+    import numpy as np
+    v = np.asarray(values, dtype=np.float32)
+    if v.ndim != 2:
+        raise ValueError("values [nx, ny] of one map")
+    atomistic = analysis in ("aa", "ua")
+    lx, ly = _PLANE_LABELS[int(ordermap.plane)]
+    head = [comment, f"# Calculated with '{calculated_with}'.",
+            f"@ xlabel {lx}-dimension [nm]", f"@ ylabel {ly}-dimension [nm]",
+            "@ zlabel order parameter ($-S_{CH}$)" if atomistic else "@ zlabel order parameter ($S$)",
+            "@ zrange -1.0 0.5 0.25" if atomistic else "@ zrange -0.5 1.0 0.25",
+            "$ type colorbar", "$ colormap seismic_r"]
+    if v.size == 0:
+        return "\n".join(head) + "\n"
+    x = np.char.mod("%.4f", ordermap.span_x[0] + np.arange(v.shape[0]) * ordermap.bin[0])
+    y = np.char.mod("%.4f", ordermap.span_y[0] + np.arange(v.shape[1]) * ordermap.bin[1])
+    flat = v.ravel().astype(np.float64)
+    z = np.where(np.isnan(flat), "NaN", np.char.mod("%.4f", flat))
+    lines = np.char.add(np.char.add(np.repeat(x, v.shape[1]), " "), np.char.add(np.char.add(np.tile(y, v.shape[0]), " "), z))
+    return "\n".join(head) + "\n" + "\n".join(lines.tolist()) + "\n"
+
+
+def write_ordermaps(directory, values, groups, ordermap, analysis: str, leaflets: bool, calculated_with: str = "gorder_amd") -> list:
+    """The reference's ordermap directory (OrderMapPresenter::write, presentation/ordermaps_presenter.rs:110-322) from
+    values [n_groups, 3, nx, ny] and the groups of structure.ordermap_groups: the maps of the whole system at the top, a
+    directory per molecule type with its average, atom and bond maps, each as `_full` and, with leaflets, `_upper` and
+    `_lower`.  The reference's plotting script is not written.  Returns the paths written, relative to `directory`."""
+    if len(values) != len(groups):
+        raise ValueError(f"{len(values)} maps for {len(groups)} groups")
+    written = []
+    os.makedirs(directory, exist_ok=True)
+    for vals, group in zip(values, groups):
+        for sub, stem, comment in group.files:
+            if sub:
+                os.makedirs(os.path.join(directory, sub), exist_ok=True)
+            for w in range(3 if leaflets else 1):
+                rel = os.path.join(sub, f"{stem}_{_LEAFLET_NAMES[w]}.dat")
+                with open(os.path.join(directory, rel), "w") as f:
+                    f.write(ordermap_text(vals[w], ordermap, analysis, comment, calculated_with))
+                written.append(rel)
+    return written

@@ -580,6 +580,29 @@ int gorder_hip_reset(gorder_hip_handle *h);
  * (Map::add, ordermap.rs:116-138).  Stream-ordered after everything submitted so far; synchronises. */
 int gorder_hip_export_maps(gorder_hip_handle *h, void *d_sums, void *d_counts, uint64_t n_u64);
 
+/* Ordermaps finished on the device (kernels_ordermap.h): the maps the reference writes into its ordermap directory
+ * (ResultsConverter::convert_ordermap, converter.rs:226-256), made from the raw tile sums where they lie, so that one float per
+ * (group, plane, tile) crosses the link instead of 16 bytes per (slot, plane, tile).  A group is a list of accumulator slots
+ * whose tiles are added (a bond, the bonds of a heavy atom, a molecule type, the whole system) in the CSR form of
+ * gorder_hip_error_estimate: group g = slots[group_begin[g] .. group_begin[g + 1]).  A tile's value (ordermap_final.h):
+ *   count < min_samples -> NaN;  v = (float)((double)sum / 1e6);  v = v / (float)count;  negate != 0 -> -v
+ * — the f32 division of the converter, not the truncating i64 division of calc_order that the order parameters take; the
+ * sums before it are exact integers, so the result is the host's on gorder_hip_finish's maps bit for bit.  negate: 1 for
+ * all-atom and united-atom analyses (they report -S; a zero sum then gives -0.0 as in the reference), 0 for coarse-grained.
+ * maps: host, [n_groups][3][nx*ny] (total, upper, lower; tiles x-major as in gorder_hip_finish); without leaflets the upper and
+ * lower planes are NaN.
+ * d_sums / d_counts NULL: the handle's own maps — after gorder_hip_allreduce those of the whole analysis.  Non-NULL: device
+ * arrays in gorder_hip_export_maps' layout, complete when the call is made (e.g. the exported maps of several ranks added by the
+ * host's collective); n_u64 must then be 3 * n_acc * nx * ny.
+ * The call waits for the handle's stream like gorder_hip_finish (a device error of the run is returned), leaves the maps as
+ * they are — a later submit followed by a second call sees the longer history — and keeps its scratch in the handle (freed
+ * by gorder_hip_destroy).  After gorder_hip_reset, or before any frame, every tile is NaN.
+ * GORDER_ERR_INVALID_ARGUMENT with a message: ordermaps off, min_samples == 0, no group, an empty group, a slot >= n_acc,
+ * group_begin not ascending, only one of d_sums / d_counts, a wrong n_u64, a NULL output. */
+int gorder_hip_ordermaps(gorder_hip_handle *h, const uint32_t *group_begin, const uint32_t *slots, uint32_t n_groups,
+                         uint32_t min_samples, uint32_t negate, const void *d_sums, const void *d_counts,
+                         uint64_t n_u64, float *maps);
+
 /* Make the handle accumulate into caller-owned device memory (>= n_u64 words, 8-byte aligned; e.g.
  * a torch.int64 tensor that the host then hands to torch.distributed.all_reduce = RCCL).  The
  * current contents of the handle's accumulators are copied over. */
