@@ -30,6 +30,7 @@
 #include <new>
 #include <string>
 #include <deque>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gorder_hip.h"
@@ -39,6 +40,7 @@
 #include "replay_rows.h"
 #include "timewise_blocks.h"
 #include "ordermap_final.h"
+#include "order_route.h"
 
 #pragma clang fp contract(off)
 
@@ -190,7 +192,6 @@ struct gorder_hip_handle {
     uint64_t assignment_frame = 0;
     // one read for global leaflets + order parameters (Plan::spec_ok; k_bonds_tiled<..., MOM> + k_spec_*)
     bool spec_enabled = false;         // the plan allows it and GORDER_HIP_NO_SPECULATE is not set
-    bool spec_now = false;             // this batch's order kernel is the MOM variant
     uint2 *d_own = nullptr;
     float4 *d_mom = nullptr;
     size_t mom_cap = 0;
@@ -510,12 +511,25 @@ int run_dynamic_normals(gorder_hip_handle *h, const FrameArgs &a) {
     return GORDER_OK;
 }
 
-int launch_orders(gorder_hip_handle *h, FrameArgs &a) {
+// ---- runtime values as template arguments: f(std::integral_constant<int, V>{}) for the V among Vs... that equals v (the
+// last one where none does), so that one generic lambda holds the launch expression of a whole kernel family
+template <int V, int... Vs, class F>
+void with_int(int v, F &&f) {
+    if constexpr (sizeof...(Vs) > 0) { if (v != V) return with_int<Vs...>(v, f); }
+    f(std::integral_constant<int, V>{});
+}
+template <class F> void with_bool(bool v, F &&f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
+template <class F> void with_axis(int axis, F &&f) { with_int<2, 1, 0, -1>(axis, f); }
+template <class F> void with_npf(int npf, F &&f) { with_int<4, 5>(npf, f); }
+static_assert(gorder::kStageFrames == kRecFrames && gorder::kStageFrames == (uint32_t)kFramesPerStage, "order_route.h: frames of a stage");
+
+// The order kernels of one batch, as `route` has them (every kernel group opens a timing segment of its own).  A combination
+// of template arguments without a kernel (`if constexpr`) is one the route never asks for: tests/test_order_route_cpu.py.
+int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &route) {
+    using gorder::BondFamily, gorder::FrameChunks;
     const Plan &p = h->plan;
     const uint32_t n_tiles = (uint32_t)p.tiles.size();
-    const bool extras = h->extra.maps || h->extra.tw || h->extra.geom_kind || h->dyn || h->manual_active;
-    // (every kernel group of the batch opens a timing segment of its own: gorder_hip_kernel_time_group)
-#define name(k) TIMING_MARK(h, k)
+    const bool ac = (h->tables.flags & GORDER_FLAG_TRIG_ACOS_COS) != 0;
     if (h->dyn && !h->manual_active) {
         const int st2 = run_dynamic_normals(h, a);
         if (st2 != GORDER_OK) return st2;
@@ -531,113 +545,45 @@ int launch_orders(gorder_hip_handle *h, FrameArgs &a) {
         for (int d = 0; d < 2; d++) { ga.xdim[d] = ge.xdim[d]; ga.ydim[d] = ge.ydim[d]; ga.zdim[d] = ge.zdim[d]; ga.span[d] = ge.span[d]; }
         ga.radius = ge.radius; ga.group = h->d_geom_group; ga.n_group = ge.n_group;
         ga.shapes = h->d_shapes; ga.err = h->d_err;
-        name("k_geom_shapes");
+        TIMING_MARK(h, "k_geom_shapes");
         hipLaunchKernelGGL(k_geom_shapes, dim3(a.n_frames), dim3(256), 0, h->stream, ga);
         HIP_TRY(h, hipGetLastError());
     }
-    if (n_tiles && !extras) {
-        // enough workgroups to fill 256 CUs x 8 blocks, frames split into chunks of whole stages
-        // Cut the frame range into chunks of whole stages.  All workgroups do the same amount of work,
-        // so the grid should be a whole number of co-resident rounds: exactly one round when the tiles
-        // fit, otherwise many short rounds so that the last, partial one costs little.
-        const uint32_t G = (uint32_t)h->frames_per_stage;
-        const uint32_t n_stages = (a.n_frames + G - 1) / G;
-        uint32_t target = h->wg_target ? h->wg_target : h->wg_capacity;
-        if (!h->wg_target) target = 12u * h->wg_capacity;   // measured: ~8-12 short rounds beat one long round
-        uint32_t n_chunks = std::max(1u, target / n_tiles);
-        n_chunks = std::min(n_chunks, std::max(1u, n_stages / 4u));   // >= 4 stages per workgroup
-        uint32_t fpc = ((n_stages + n_chunks - 1) / n_chunks) * G;
-        n_chunks = (a.n_frames + fpc - 1) / fpc;
-        a.frames_per_chunk = fpc;
-        const uint64_t grid = (uint64_t)n_tiles * n_chunks;
+    if (route.family == BondFamily::Tiled || route.family == BondFamily::Gather) {
+        const FrameChunks c = gorder::tiled_chunks(a.n_frames, (uint32_t)h->frames_per_stage, n_tiles, h->wg_target, h->wg_capacity);
+        a.frames_per_chunk = c.frames_per_chunk;
+        const uint64_t grid = (uint64_t)n_tiles * c.n_chunks;
         if (grid > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "batch too large");
-        const bool ac = (h->tables.flags & GORDER_FLAG_TRIG_ACOS_COS) != 0;
         const dim3 g((uint32_t)grid), b(kBlock);
-#define GORDER_LAUNCH_TILED_A(G_, NPF_, AC_, PBC_, LF_, AX_)                                               \
-        do {                                                                                                \
-            if (LF_ && h->spec_now)                                                                         \
-                hipLaunchKernelGGL((k_bonds_tiled<G_, NPF_, AC_, PBC_, LF_, AX_, LF_>), g, b, h->lds_bytes, h->stream, a, \
-                                   a.xyz, a.box9, a.aflags, a.arow, h->d_tiles, h->d_items, h->d_tile_slots, n_tiles, h->lw); \
-            else                                                                                            \
-                hipLaunchKernelGGL((k_bonds_tiled<G_, NPF_, AC_, PBC_, LF_, AX_>), g, b, h->lds_bytes, h->stream, a,     \
-                                   a.xyz, a.box9, a.aflags, a.arow, h->d_tiles, h->d_items, h->d_tile_slots, n_tiles,   \
-                                   h->lw);                                                                  \
-        } while (0)
-#define GORDER_LAUNCH_TILED_V(G_, NPF_, AC_, PBC_, LF_)                                                    \
-        do {                                                                                                \
-            if (h->axis == 2) GORDER_LAUNCH_TILED_A(G_, NPF_, AC_, PBC_, LF_, 2);                           \
-            else if (h->axis == 1) GORDER_LAUNCH_TILED_A(G_, NPF_, AC_, PBC_, LF_, 1);                      \
-            else if (h->axis == 0) GORDER_LAUNCH_TILED_A(G_, NPF_, AC_, PBC_, LF_, 0);                      \
-            else GORDER_LAUNCH_TILED_A(G_, NPF_, AC_, PBC_, LF_, -1);                                       \
-        } while (0)
-#define GORDER_LAUNCH_TILED(G_, NPF_)                                                                       \
-        do {                                                                                                \
-            const int v_ = (ac ? 4 : 0) | (a.pbc ? 2 : 0) | (a.leaflets ? 1 : 0);                           \
-            switch (v_) {                                                                                   \
-                case 0: GORDER_LAUNCH_TILED_V(G_, NPF_, false, false, false); break;                        \
-                case 1: GORDER_LAUNCH_TILED_V(G_, NPF_, false, false, true); break;                         \
-                case 2: GORDER_LAUNCH_TILED_V(G_, NPF_, false, true, false); break;                         \
-                case 3: GORDER_LAUNCH_TILED_V(G_, NPF_, false, true, true); break;                          \
-                case 4: GORDER_LAUNCH_TILED_V(G_, NPF_, true, false, false); break;                         \
-                case 5: GORDER_LAUNCH_TILED_V(G_, NPF_, true, false, true); break;                          \
-                case 6: GORDER_LAUNCH_TILED_V(G_, NPF_, true, true, false); break;                          \
-                default: GORDER_LAUNCH_TILED_V(G_, NPF_, true, true, true); break;                          \
-            }                                                                                               \
-        } while (0)
-#define GORDER_LAUNCH_GATHER_V(G_, AC_, PBC_, LF_)                                                         \
-        hipLaunchKernelGGL((k_bonds_gather<G_, AC_, PBC_, LF_>), g, b, 0, h->stream, a, a.xyz, a.box9, a.aflags, \
-                           a.arow, h->d_tiles, h->d_items, h->d_tile_slots, n_tiles)
-#define GORDER_LAUNCH_GATHER(G_)                                                                            \
-        do {                                                                                                \
-            const int v_ = (ac ? 4 : 0) | (a.pbc ? 2 : 0) | (a.leaflets ? 1 : 0);                           \
-            switch (v_) {                                                                                   \
-                case 0: GORDER_LAUNCH_GATHER_V(G_, false, false, false); break;                             \
-                case 1: GORDER_LAUNCH_GATHER_V(G_, false, false, true); break;                              \
-                case 2: GORDER_LAUNCH_GATHER_V(G_, false, true, false); break;                              \
-                case 3: GORDER_LAUNCH_GATHER_V(G_, false, true, true); break;                               \
-                case 4: GORDER_LAUNCH_GATHER_V(G_, true, false, false); break;                              \
-                case 5: GORDER_LAUNCH_GATHER_V(G_, true, false, true); break;                               \
-                case 6: GORDER_LAUNCH_GATHER_V(G_, true, true, false); break;                               \
-                default: GORDER_LAUNCH_GATHER_V(G_, true, true, true); break;                               \
-            }                                                                                               \
-        } while (0)
-        name(h->use_gather ? "k_bonds_gather" : "k_bonds_tiled");
-        if (h->use_gather) {
-            GORDER_LAUNCH_GATHER(4);
-        } else {
-            // prefetch registers per thread: enough float4 for the widest window (64 threads stage a frame)
-            if ((3u * p.max_window + 6u) / 4u <= 4u * 64u && !env_flag("GORDER_HIP_NPF5")) GORDER_LAUNCH_TILED(4, 4);
-            else GORDER_LAUNCH_TILED(4, 5);
-        }
-#undef GORDER_LAUNCH_GATHER
-#undef GORDER_LAUNCH_GATHER_V
-#undef GORDER_LAUNCH_TILED_A
-#undef GORDER_LAUNCH_TILED_V
-#undef GORDER_LAUNCH_TILED
+        TIMING_MARK(h, route.label);
+        with_bool(ac, [&](auto AC) { with_bool(a.pbc, [&](auto PBC) { with_bool(a.leaflets, [&](auto LF) {
+            if (route.family == BondFamily::Gather)
+                hipLaunchKernelGGL((k_bonds_gather<4, AC(), PBC(), LF()>), g, b, 0, h->stream, a, a.xyz, a.box9, a.aflags, a.arow,
+                                   h->d_tiles, h->d_items, h->d_tile_slots, n_tiles);
+            else with_npf(route.npf, [&](auto NPF) { with_axis(h->axis, [&](auto AX) { with_bool(route.mom, [&](auto MOM) {
+                if constexpr (LF() || !MOM())
+                    hipLaunchKernelGGL((k_bonds_tiled<4, NPF(), AC(), PBC(), LF(), AX(), MOM()>), g, b, h->lds_bytes, h->stream, a,
+                                       a.xyz, a.box9, a.aflags, a.arow, h->d_tiles, h->d_items, h->d_tile_slots, n_tiles, h->lw);
+            }); }); });
+        }); }); });
         HIP_TRY(h, hipGetLastError());
     }
-    if (extras || !p.ua_tiles.empty()) {
+    if (route.extras || route.ua_mode >= 0) {
         // scatter-bound modes: plain per-sample kernels (see "Extras" above)
         ExtraArgs e = h->extra;
         e.tw_sums = h->d_tw_sums; e.tw_cnts = h->d_tw_cnts; e.tw_row0 = h->n_frames;
-        e.shapes = h->d_shapes;
-        const bool ua_fast = (h->tables.flags & GORDER_FLAG_UA_FAST_NORMALISE) != 0 && !p.ua_tiles.empty();
-        e.inv_box = nullptr;
-        if (ua_fast && a.pbc) {      // 1 / box edge per frame, once per frame instead of once per lane and frame
+        e.shapes = h->d_shapes; e.inv_box = nullptr;
+        if (route.ua_fast && a.pbc) {      // 1 / box edge per frame, once per frame instead of once per lane and frame
             int st3;
             if ((st3 = ensure(h, &h->d_inv_box, &h->inv_box_cap, (size_t)a.n_frames * 8)) != GORDER_OK) return st3;
             hipLaunchKernelGGL(k_inv_box, dim3((4u * a.n_frames + 255u) / 256u), dim3(256), 0, h->stream, a.box9, a.n_frames, h->d_inv_box);
             e.inv_box = h->d_inv_box;
         }
         e.dyn = (h->dyn || h->manual_active) ? h->d_dyn_normals : nullptr;
-        const bool ac = (h->tables.flags & GORDER_FLAG_TRIG_ACOS_COS) != 0;
-        // with ordermaps the frames go in sub-ranges short enough for the packed map words (k_fold_maps)
-        uint32_t sub = e.maps ? (uint32_t)std::max<uint64_t>(1, (h->map_fold_limit - 1) / h->map_max_mol) : a.n_frames;
-        const bool staged = e.maps && h->map_staged;
-        const size_t rec_per_frame = std::max(p.ua_tiles.size() * 3u, extras ? p.tiles.size() : (size_t)0) * kBlock;   // staged words per frame
-        if (staged) {   // at most 1 GiB of staging per sub-range
-            sub = std::min<uint32_t>(sub, (uint32_t)std::max<size_t>(1, ((size_t)1 << 27) / rec_per_frame));
-            sub = std::min(sub, a.n_frames);
+        const bool staged = route.map_accumulate;
+        const size_t rec_per_frame = std::max(p.ua_tiles.size() * 3u, route.extras ? p.tiles.size() : (size_t)0) * kBlock;   // staged words per frame
+        const uint32_t sub = gorder::map_subrange(a.n_frames, e.maps != 0, staged, h->map_fold_limit, h->map_max_mol, rec_per_frame);
+        if (staged) {
             const int st2 = ensure(h, &h->d_map_rec, &h->map_rec_cap, rec_per_frame * (((size_t)sub + 15) / 16 * 16));
             if (st2 != GORDER_OK) return st2;
         }
@@ -651,145 +597,70 @@ int launch_orders(gorder_hip_handle *h, FrameArgs &a) {
                 }
                 h->map_pending += cost;
             }
-            for (int pass = 0; pass < 2; pass++) {
-                const uint32_t nt = pass == 0 ? (extras ? n_tiles : 0u) : (uint32_t)p.ua_tiles.size();
+            for (int pass = 0; pass < 2; pass++) {      // the bond tiles, then the united-atom tiles
+                const uint32_t nt = pass == 0 ? (route.extras ? n_tiles : 0u) : (uint32_t)p.ua_tiles.size();
                 if (!nt) continue;
-                uint32_t n_chunks = std::max(1u, (h->wg_target ? h->wg_target : 8u * h->wg_capacity) / nt);
-                n_chunks = std::min(n_chunks, nf);
-                uint32_t fpc = (nf + n_chunks - 1) / n_chunks;
-                if (staged) fpc = (fpc + 15u) / 16u * 16u;   // whole frame blocks (kRecFrames) and whole lines per workgroup
-                // per-frame rows and nothing else, the default cosine, four frames per stage: the tiled kernel with the
-                // stage's ticks as a second output (k_bonds_tiled_tw)
-                // (with staged ordermaps as well: the same kernel writes the map words too)
-                const bool tiled_tw = pass == 0 && e.tw && (!e.maps || staged) && !e.geom_kind && !e.dyn && !ac && !h->use_gather && h->d_item_run &&
-                                      h->frames_per_stage == (int)kRecFrames && !env_flag("GORDER_HIP_TW_GATHER");
-                if (tiled_tw) fpc = (fpc + kRecFrames - 1u) / kRecFrames * kRecFrames;       // whole stages
-                n_chunks = (nf + fpc - 1) / fpc;
+                const FrameChunks c = gorder::extras_chunks(nf, nt, h->wg_target, h->wg_capacity, staged, pass == 0 && route.family == BondFamily::TiledTw);
                 FrameArgs b = a;
-                b.frame0 = lo;
-                b.n_frames = hi;
-                b.frames_per_chunk = fpc;
+                b.frame0 = lo; b.n_frames = hi; b.frames_per_chunk = c.frames_per_chunk;
                 e.map_rec = staged ? h->d_map_rec : nullptr;
                 e.item_run = pass == 0 ? h->d_item_run : h->d_ua_item_run;      // (bond tiles: k_bonds_tiled_tw only)
-                e.rec_frame0 = lo;
-                e.rec_stride = (nf + 15u) / 16u * 16u;
-                const dim3 g(pass == 0 ? nt * n_chunks : (nt * n_chunks + 7u) / 8u * 8u), blk(kBlock);   // united atoms: see the XCD mapping in k_ua_extras
+                e.rec_frame0 = lo; e.rec_stride = (nf + 15u) / 16u * 16u;
+                const dim3 g(pass == 0 ? nt * c.n_chunks : (nt * c.n_chunks + 7u) / 8u * 8u), blk(kBlock);   // united atoms: see the XCD mapping in k_ua_extras
                 if (pass == 0) {
-                    const Item *items = (staged || tiled_tw) ? h->d_items_by_slot : h->d_items;
-#define GORDER_LAUNCH_BONDS(AC, MO)                                                                               \
-    hipLaunchKernelGGL((k_bonds_extras<AC, MO>), g, blk, 0, h->stream, b, e, b.xyz, b.box9, b.aflags, b.arow,       \
-                       h->d_tiles, items, h->d_tile_slots, nt)
-                    const bool maps_only = staged && !e.tw && !e.geom_kind && !e.dyn;
-                    // maps and nothing else, the default cosine, four frames per stage: the tiled kernel with the staged
-                    // words as a second output (k_bonds_tiled_maps)
-                    const bool tiled_maps = maps_only && !ac && !h->use_gather && h->frames_per_stage == (int)kRecFrames &&
-                                            !env_flag("GORDER_HIP_MAPS_GATHER");
-#define GORDER_LAUNCH_TM_A(NPF_, PBC_, LF_, AX_)                                                                   \
-    do {                                                                                                            \
-        if (tiled_tw && !staged && LF_ && h->spec_now)                                                              \
-            hipLaunchKernelGGL((k_bonds_tiled_tw<NPF_, PBC_, LF_, AX_, false, LF_>), g, blk, h->lds_bytes, h->stream, b, e, b.xyz, \
-                               b.box9, b.aflags, b.arow, h->d_tiles, items, h->d_tile_slots, nt, h->lw);               \
-        else if (tiled_tw && staged)                                                                                \
-            hipLaunchKernelGGL((k_bonds_tiled_tw<NPF_, PBC_, LF_, AX_, true>), g, blk, h->lds_bytes, h->stream, b, e, b.xyz, \
-                               b.box9, b.aflags, b.arow, h->d_tiles, items, h->d_tile_slots, nt, h->lw);               \
-        else if (tiled_tw)                                                                                          \
-            hipLaunchKernelGGL((k_bonds_tiled_tw<NPF_, PBC_, LF_, AX_, false>), g, blk, h->lds_bytes, h->stream, b, e, b.xyz, \
-                               b.box9, b.aflags, b.arow, h->d_tiles, items, h->d_tile_slots, nt, h->lw);               \
-        else                                                                                                        \
-            hipLaunchKernelGGL((k_bonds_tiled_maps<NPF_, PBC_, LF_, AX_>), g, blk, h->lds_bytes, h->stream, b, e, b.xyz, \
-                               b.box9, b.aflags, b.arow, h->d_tiles, items, h->d_tile_slots, nt, h->lw);               \
-    } while (0)
-#define GORDER_LAUNCH_TM_V(NPF_, PBC_, LF_)                                                                        \
-    do {                                                                                                            \
-        if (h->axis == 2) GORDER_LAUNCH_TM_A(NPF_, PBC_, LF_, 2);                                                   \
-        else if (h->axis == 1) GORDER_LAUNCH_TM_A(NPF_, PBC_, LF_, 1);                                              \
-        else if (h->axis == 0) GORDER_LAUNCH_TM_A(NPF_, PBC_, LF_, 0);                                              \
-        else GORDER_LAUNCH_TM_A(NPF_, PBC_, LF_, -1);                                                               \
-    } while (0)
-#define GORDER_LAUNCH_TM(NPF_)                                                                                     \
-    do {                                                                                                            \
-        switch ((b.pbc ? 2 : 0) | (b.leaflets ? 1 : 0)) {                                                           \
-            case 0: GORDER_LAUNCH_TM_V(NPF_, false, false); break;                                                  \
-            case 1: GORDER_LAUNCH_TM_V(NPF_, false, true); break;                                                   \
-            case 2: GORDER_LAUNCH_TM_V(NPF_, true, false); break;                                                   \
-            default: GORDER_LAUNCH_TM_V(NPF_, true, true); break;                                                   \
-        }                                                                                                           \
-    } while (0)
-                    name(tiled_maps ? "k_bonds_tiled_maps" : (tiled_tw ? "k_bonds_tiled_tw" : "k_bonds_extras"));
-                    if (tiled_maps || tiled_tw) {
-                        if ((3u * p.max_window + 6u) / 4u <= 4u * 64u && !env_flag("GORDER_HIP_NPF5")) GORDER_LAUNCH_TM(4);
-                        else GORDER_LAUNCH_TM(5);
-                    }
-                    else if (maps_only) { if (ac) GORDER_LAUNCH_BONDS(true, true); else GORDER_LAUNCH_BONDS(false, true); }
-                    else { if (ac) GORDER_LAUNCH_BONDS(true, false); else GORDER_LAUNCH_BONDS(false, false); }
-#undef GORDER_LAUNCH_TM
-#undef GORDER_LAUNCH_TM_V
-#undef GORDER_LAUNCH_TM_A
-#undef GORDER_LAUNCH_BONDS
+                    const Item *items = route.items_by_slot ? h->d_items_by_slot : h->d_items;
+                    TIMING_MARK(h, route.label);
+                    if (route.family == BondFamily::Extras)
+                        with_bool(ac, [&](auto AC) { with_bool(route.maps_only, [&](auto MO) {
+                            hipLaunchKernelGGL((k_bonds_extras<AC(), MO()>), g, blk, 0, h->stream, b, e, b.xyz, b.box9, b.aflags, b.arow,
+                                               h->d_tiles, items, h->d_tile_slots, nt);
+                        }); });
+                    else    // the tiled kernel with a second output: the stage's ticks (k_bonds_tiled_tw) or its map words (k_bonds_tiled_maps)
+                        with_npf(route.npf, [&](auto NPF) { with_bool(b.pbc, [&](auto PBC) { with_bool(b.leaflets, [&](auto LF) { with_axis(h->axis, [&](auto AX) {
+                            if (route.family == BondFamily::TiledMaps)
+                                hipLaunchKernelGGL((k_bonds_tiled_maps<NPF(), PBC(), LF(), AX()>), g, blk, h->lds_bytes, h->stream, b, e, b.xyz,
+                                                   b.box9, b.aflags, b.arow, h->d_tiles, items, h->d_tile_slots, nt, h->lw);
+                            else with_bool(route.tw_maps, [&](auto MAPS) { with_bool(route.mom, [&](auto MOM) {
+                                if constexpr (!MOM() || (LF() && !MAPS()))
+                                    hipLaunchKernelGGL((k_bonds_tiled_tw<NPF(), PBC(), LF(), AX(), MAPS(), MOM()>), g, blk, h->lds_bytes, h->stream, b, e,
+                                                       b.xyz, b.box9, b.aflags, b.arow, h->d_tiles, items, h->d_tile_slots, nt, h->lw);
+                            }); });
+                        }); }); }); });
                 } else {
-#define GORDER_LAUNCH_UA(AC, MODE)                                                                                \
-    do {                                                                                                            \
-        if (!AC && ua_fast)                                                                                         \
-            hipLaunchKernelGGL((k_ua_extras_fast<MODE>), g, blk, 0, h->stream, b, e, b.xyz, b.box9, b.aflags,      \
-                               b.arow, h->d_ua_tiles, h->d_ua_items, h->d_ua_tile_slots, nt, (const float *)e.inv_box); \
-        else                                                                                                        \
-            hipLaunchKernelGGL((k_ua_extras<AC, MODE>), g, blk, 0, h->stream, b, e, b.xyz, b.box9, b.aflags,        \
-                               b.arow, h->d_ua_tiles, h->d_ua_items, h->d_ua_tile_slots, nt, (const float *)nullptr); \
-    } while (0)
-                    // staged ordermap samples and nothing else: the lean kernel
-                    const bool maps_only = extras && staged && !e.tw && !e.geom_kind && !e.dyn;
-                    name("k_ua_extras");
-                    if (maps_only) { if (ac) GORDER_LAUNCH_UA(true, 1); else GORDER_LAUNCH_UA(false, 1); }
-                    else if (extras && e.tw && !e.maps && !e.geom_kind && !e.dyn) { if (ac) GORDER_LAUNCH_UA(true, 3); else GORDER_LAUNCH_UA(false, 3); }
-                    else if (extras) { if (ac) GORDER_LAUNCH_UA(true, 2); else GORDER_LAUNCH_UA(false, 2); }
-                    else { if (ac) GORDER_LAUNCH_UA(true, 0); else GORDER_LAUNCH_UA(false, 0); }
-#undef GORDER_LAUNCH_UA
+                    TIMING_MARK(h, "k_ua_extras");
+                    with_bool(ac, [&](auto AC) { with_bool(route.ua_fast, [&](auto FAST) { with_int<0, 1, 2, 3>(route.ua_mode, [&](auto MODE) {
+                        if constexpr (FAST() && !AC())
+                            hipLaunchKernelGGL((k_ua_extras_fast<MODE()>), g, blk, 0, h->stream, b, e, b.xyz, b.box9, b.aflags, b.arow,
+                                               h->d_ua_tiles, h->d_ua_items, h->d_ua_tile_slots, nt, (const float *)e.inv_box);
+                        else if constexpr (!FAST())
+                            hipLaunchKernelGGL((k_ua_extras<AC(), MODE()>), g, blk, 0, h->stream, b, e, b.xyz, b.box9, b.aflags, b.arow,
+                                               h->d_ua_tiles, h->d_ua_items, h->d_ua_tile_slots, nt, (const float *)nullptr);
+                    }); }); });
                 }
-                {
-                    if (staged) {   // second step: slot-major accumulation of the staged samples in LDS
-                        const uint32_t planes = h->tables.leaflets.method != GORDER_LEAFLETS_NONE ? 2u : 1u;
-                        const uint32_t ntm = h->map_nx * h->map_ny, n_words = planes * ntm;
-                        // enough blocks for ~2 per CU; a block flushes <= n_words atomics, so keep its chunk long
-                        // bonds: a lane per molecule of the slot (256 threads do for the slots of one molecule type of up to
-                        // 256 molecules), so more, shorter chunks; united atoms: the whole block strides over long runs
-                        const uint32_t mthreads = 1024u;
-                        uint32_t mchunks = std::max(1u, (pass == 0 ? 512u : 512u) / std::max(1u, p.n_acc));
-                        if (const char *ev = getenv("GORDER_HIP_MAP_CHUNKS")) mchunks = (uint32_t)std::max(1, atoi(ev));
-                        mchunks = std::min(mchunks, std::max(1u, nf / 16u));
-                        const uint32_t mfpc = ((nf + mchunks - 1) / mchunks + 15u) / 16u * 16u;   // whole frame blocks
-                        mchunks = (nf + mfpc - 1) / mfpc;
-                        name("k_map_accumulate");
-                        hipLaunchKernelGGL(k_map_accumulate, dim3(p.n_acc * mchunks), dim3(mthreads),
-                                           n_words * sizeof(unsigned long long), h->stream, h->d_map_rec,
-                                           pass == 0 ? h->d_runs : h->d_ua_runs, pass == 0 ? h->d_run_begin : h->d_ua_run_begin,
-                                           p.n_acc, nf, e.rec_stride, mfpc, pass == 0 ? 1u : 3u, n_words, ntm, h->d_map_packed,
-                                           p.n_acc);
-                    }
+                if (staged) {   // second step: slot-major accumulation of the staged samples in LDS
+                    const uint32_t planes = h->tables.leaflets.method != GORDER_LEAFLETS_NONE ? 2u : 1u;
+                    const uint32_t ntm = h->map_nx * h->map_ny, n_words = planes * ntm;
+                    const char *ev = getenv("GORDER_HIP_MAP_CHUNKS");
+                    const FrameChunks m = gorder::map_chunks(nf, p.n_acc, ev ? (uint32_t)std::max(1, atoi(ev)) : 0u);
+                    TIMING_MARK(h, "k_map_accumulate");
+                    hipLaunchKernelGGL(k_map_accumulate, dim3(p.n_acc * m.n_chunks), dim3(1024), n_words * sizeof(unsigned long long),
+                                       h->stream, h->d_map_rec, pass == 0 ? h->d_runs : h->d_ua_runs,
+                                       pass == 0 ? h->d_run_begin : h->d_ua_run_begin, p.n_acc, nf, e.rec_stride, m.frames_per_chunk,
+                                       pass == 0 ? 1u : 3u, n_words, ntm, h->d_map_packed, p.n_acc);
                 }
                 HIP_TRY(h, hipGetLastError());
             }
         }
     }
-    if (!p.direct.empty()) {
-        const uint32_t n_items = (uint32_t)p.direct.size();
-        const uint32_t bpc = (n_items + kBlock - 1) / kBlock;
-        const uint32_t target = h->wg_target ? h->wg_target : 256u * 8u;
-        uint32_t n_chunks = std::max(1u, (target + bpc - 1) / bpc);
-        n_chunks = std::min(n_chunks, a.n_frames);
-        const uint32_t fpc = (a.n_frames + n_chunks - 1) / n_chunks;
-        n_chunks = (a.n_frames + fpc - 1) / fpc;
+    if (route.direct) {
+        const uint32_t n_items = (uint32_t)p.direct.size(), bpc = (n_items + kBlock - 1) / kBlock;
+        const FrameChunks c = gorder::direct_chunks(a.n_frames, bpc, h->wg_target);
         FrameArgs b = a;
-        b.frames_per_chunk = fpc;
-        name("k_bonds_direct");
-        if (h->tables.flags & GORDER_FLAG_TRIG_ACOS_COS)
-            hipLaunchKernelGGL(k_bonds_direct<true>, dim3(bpc * n_chunks), dim3(kBlock), 0, h->stream, b, h->d_direct,
-                               n_items, bpc);
-        else
-            hipLaunchKernelGGL(k_bonds_direct<false>, dim3(bpc * n_chunks), dim3(kBlock), 0, h->stream, b, h->d_direct,
-                               n_items, bpc);
+        b.frames_per_chunk = c.frames_per_chunk;
+        TIMING_MARK(h, "k_bonds_direct");
+        with_bool(ac, [&](auto AC) { hipLaunchKernelGGL(k_bonds_direct<AC()>, dim3(bpc * c.n_chunks), dim3(kBlock), 0, h->stream, b, h->d_direct, n_items, bpc); });
         HIP_TRY(h, hipGetLastError());
     }
-#undef name
     return GORDER_OK;       // (the frames are counted by k_batch_end, which also closes the batch's timing chain)
 }
 
@@ -1957,7 +1828,16 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
     // batches (AssignedLeaflets::local, leaflets.rs:1371-1380), rows 1.. = assignment frames here
     const bool leaflets = lf.method != GORDER_LEAFLETS_NONE;
     size_t n_new_rows = 0;
-    bool spec = false;
+    // what the order pass of this batch will run (order_route.h), decided here, before the first kernel is queued
+    gorder::OrderRouteIn ri;
+    ri.acos = (h->tables.flags & GORDER_FLAG_TRIG_ACOS_COS) != 0; ri.pbc = pbc; ri.leaflets = leaflets; ri.axis = h->axis;
+    ri.maps = h->extra.maps != 0; ri.map_staged = h->map_staged; ri.tw = h->extra.tw != 0; ri.geom = h->extra.geom_kind != 0;
+    ri.manual_frames = h->manual_frames != 0; ri.normal_table = h->d_ntable != nullptr;
+    ri.dyn_or_manual = h->dyn || ri.manual_frames || ri.normal_table;       // (manual_active is set further down)
+    ri.use_gather = h->use_gather; ri.item_run = h->d_item_run != nullptr; ri.frames_per_stage = h->frames_per_stage; ri.max_window = p.max_window;
+    ri.bond_tiles = !p.tiles.empty(); ri.ua_tiles = !p.ua_tiles.empty(); ri.direct_items = !p.direct.empty(); ri.ua_fast_flag = (h->tables.flags & GORDER_FLAG_UA_FAST_NORMALISE) != 0;
+    ri.global_leaflets = lf.method == GORDER_LEAFLETS_GLOBAL; ri.spec_enabled = h->spec_enabled; ri.have_assignment = h->have_assignment;
+    ri.npf5 = env_flag("GORDER_HIP_NPF5"); ri.tw_gather = env_flag("GORDER_HIP_TW_GATHER"); ri.maps_gather = env_flag("GORDER_HIP_MAPS_GATHER");
     std::vector<uint32_t> spec_aframes;
     std::vector<uint64_t> collect_frames;       // collected leaflets: the assignment frames of this batch = rows 1.. of d_aflags
     // argument errors come before the first kernel of the batch is queued (a batch that fails later leaves through
@@ -1994,11 +1874,12 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
         (void)timing_mark(h, nullptr);
         return status;
     };
+    std::vector<uint32_t> arow, aframes;
+    uint64_t last_assign_frame = h->assignment_frame;
     if (leaflets) {
-        std::vector<uint32_t> arow(n_frames), aframes;
+        arow.resize(n_frames);
         uint32_t cur = 0;
         bool have = h->have_assignment;
-        uint64_t last_assign_frame = h->assignment_frame;
         if (ltable) {
             arow = replay.arow;
             last_assign_frame = replay.carry_index * lf.frequency;       // the assignment frame of the newest row
@@ -2019,20 +1900,19 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
             if (!have) return fail(h, GORDER_ERR_LEAFLETS_NOT_PRIMED, "no leaflet assignment for the first frame");
             arow[f] = cur;
         }
-        // One read for global leaflets + order parameters: every frame of the batch is an assignment frame, an earlier
-        // assignment exists (row 0), nothing but the plain order kernel runs.  The order kernel then routes by row 0.
-        // (per-frame rows too where they come out of the tiled kernel: k_bonds_tiled_tw, the default cosine)
-        const bool tw_tiled = h->extra.tw && !(h->tables.flags & GORDER_FLAG_TRIG_ACOS_COS) && h->d_item_run &&
-                              h->frames_per_stage == (int)kRecFrames && !env_flag("GORDER_HIP_TW_GATHER");
-        spec = h->spec_enabled && lf.method == GORDER_LEAFLETS_GLOBAL && h->have_assignment && aframes.size() == n_frames &&
-               !h->extra.maps && (!h->extra.tw || tw_tiled) && !h->extra.geom_kind && !h->dyn && !h->manual_frames && !h->d_ntable &&
-               !h->use_gather && !p.tiles.empty();
-        if (spec) {
-            spec_poll(h, false);
-            const uint32_t slot = (uint32_t)(h->spec_batches % gorder_hip_handle::kSpecRing);
-            if (h->spec_ring_frames[slot]) (void)hipEventSynchronize(h->spec_counters_copied[slot]), spec_poll(h, false);
-            spec = h->spec_enabled;
-        }
+    }
+    // One read for global leaflets + order parameters (route.speculative): the order kernel then routes by row 0.
+    ri.every_frame_assigns = aframes.size() == n_frames;
+    gorder::OrderRoute route = gorder::choose_order_route(ri);
+    if (route.speculative) {
+        spec_poll(h, false);
+        const uint32_t slot = (uint32_t)(h->spec_batches % gorder_hip_handle::kSpecRing);
+        if (h->spec_ring_frames[slot]) (void)hipEventSynchronize(h->spec_counters_copied[slot]), spec_poll(h, false);
+        ri.spec_enabled = h->spec_enabled;
+        if (!ri.spec_enabled) route = gorder::choose_order_route(ri);      // the counters of an earlier batch turned it off
+    }
+    const bool spec = route.speculative;
+    if (leaflets) {
         if (spec) std::fill(arow.begin(), arow.end(), 0u);
         const size_t rows = (ltable ? replay.expand.size() : aframes.size()) + 1;   // (a speculative batch: row 0 and every frame's exact sides)
         if (rows > h->aflags_rows) {
@@ -2111,7 +1991,6 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
         if ((st = ensure(h, &h->d_head_z, &h->head_z_cap, (size_t)n_frames * p.n_mol_total)) != GORDER_OK) return abort_batch(st);
         a.own = h->d_own; a.mom = h->d_mom; a.mom_dim = (int)lf.normal_dim;
         a.own_head_begin = h->d_own_head_begin; a.own_heads = h->d_own_heads; a.head_z = h->d_head_z;
-        h->spec_now = true;
     }
     h->extra.touched = nullptr;
     if ((h->collect & GORDER_COLLECT_NORMALS) && h->extra.geom_kind && !p.tiles.empty() && p.ua_tiles.empty()) {
@@ -2121,8 +2000,7 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
         if (hipMemsetAsync(h->d_touched, 0, nt, h->stream) != hipSuccess) return abort_batch(fail(h, GORDER_ERR_DEVICE, "collect: hipMemsetAsync"));
         h->extra.touched = h->d_touched;
     }
-    st = launch_orders(h, a);
-    h->spec_now = false;
+    st = launch_orders(h, a, route);
     h->manual_active = false;
     if (st != GORDER_OK) return abort_batch(st);
     h->rep_dirty = true;
@@ -2147,15 +2025,12 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
         if ((st = run_leaflets(h, d_xyz, d_box, spec_aframes, 1, h->d_spec_ok)) != GORDER_OK) return abort_batch(st);
         (void)timing_mark(h, "k_spec_check + k_spec_fixup");
         const uint32_t fix_grid = (uint32_t)std::min<uint64_t>(((uint64_t)n_frames * p.n_mol_total + 63u) / 64u, 4096u);
-        if (h->extra.tw)
-            hipLaunchKernelGGL((k_spec_fixup<false, true>), dim3(fix_grid), dim3(64), 0, h->stream, a, sa, h->d_spec_mol_begin,
-                               h->d_spec_samples, h->d_tw_sums, h->d_tw_cnts, (uint64_t)h->n_frames);
-        else if (h->tables.flags & GORDER_FLAG_TRIG_ACOS_COS)
-            hipLaunchKernelGGL((k_spec_fixup<true, false>), dim3(fix_grid), dim3(64), 0, h->stream, a, sa, h->d_spec_mol_begin,
-                               h->d_spec_samples, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (uint64_t)0);
-        else
-            hipLaunchKernelGGL((k_spec_fixup<false, false>), dim3(fix_grid), dim3(64), 0, h->stream, a, sa, h->d_spec_mol_begin,
-                               h->d_spec_samples, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (uint64_t)0);
+        with_bool(route.fixup_ac, [&](auto AC) { with_bool(route.fixup_tw, [&](auto TW) {
+            if constexpr (!AC() || !TW())      // (per-frame rows come out of the tiled kernel with the default cosine only)
+                hipLaunchKernelGGL((k_spec_fixup<AC(), TW()>), dim3(fix_grid), dim3(64), 0, h->stream, a, sa, h->d_spec_mol_begin,
+                                   h->d_spec_samples, TW() ? h->d_tw_sums : nullptr, TW() ? h->d_tw_cnts : nullptr,
+                                   TW() ? (uint64_t)h->n_frames : (uint64_t)0);
+        }); });
         hipLaunchKernelGGL(k_spec_finish, dim3(1), dim3(256), 0, h->stream, sa);
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipEventRecord(h->spec_counters_copied[ring_slot], h->stream));
