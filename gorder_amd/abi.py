@@ -326,6 +326,7 @@ _EXPORTS = [
     "gorder_hip_set_manual_leaflet_table", "gorder_hip_set_manual_normal_table",
     "gorder_hip_timewise_chunk_frames", "gorder_hip_timewise_rows", "gorder_hip_timewise_blocks", "gorder_hip_error_estimate",
     "gorder_hip_convergence", "gorder_hip_ordermaps",
+    "gorder_hip_set_radial_shells", "gorder_hip_radial_shells", "gorder_hip_radial_thresholds",
 ]
 
 _lib = None
@@ -426,8 +427,25 @@ def load_library() -> C.CDLL:
     lib.gorder_hip_error_estimate.argtypes = [vp, u32, vp, vp, u32, vp, vp, vp]
     lib.gorder_hip_convergence.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp]
     lib.gorder_hip_ordermaps.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, u64, vp]
+    lib.gorder_hip_set_radial_shells.argtypes = [vp, vp, u32]
+    lib.gorder_hip_radial_shells.argtypes = [vp, vp, vp, C.POINTER(u32)]
+    lib.gorder_hip_radial_thresholds.argtypes = [vp, u32, vp]
     _lib = lib
     return lib
+
+
+RADIAL_MAX_SHELLS = 32       # GORDER_RADIAL_MAX_SHELLS
+
+
+def radial_thresholds(radii) -> np.ndarray:
+    """thr[k]: the smallest float32 whose correctly rounded square root reaches radii[k], so that `d2 < thr[k]` is exactly
+    `sqrt(d2) < radii[k]` — what k_bonds_shells compares against (gorder_hip_radial_thresholds); needs no device."""
+    r = np.ascontiguousarray(radii, dtype=np.float32)
+    thr = np.empty(r.shape, dtype=np.float32)
+    st = load_library().gorder_hip_radial_thresholds(r.ctypes.data_as(C.c_void_p), r.size, thr.ctypes.data_as(C.c_void_p))
+    if st != OK:
+        raise GorderHipError(st, "gorder_hip_radial_thresholds")
+    return thr
 
 
 def timewise_chunk_frames() -> int:
@@ -548,6 +566,7 @@ class HipEngine:
             raise GorderHipError(st, msg)
         self.n_acc = self.lib.gorder_hip_n_accumulators(self._h)
         self._keep = []
+        self._n_shells = 0
 
     def close(self):
         if getattr(self, "_h", None):
@@ -832,6 +851,27 @@ class HipEngine:
         normals (COLLECT_NORMALS) of the frames submitted from now on (gorder_hip_set_collect): before the first submit
         or right after reset()."""
         self._check(self.lib.gorder_hip_set_collect(self._h, what))
+
+    def set_radial_shells(self, radii):
+        """Ascending radii (nm) around the reference of the tables' cylinder or sphere, the last one geometry.radius: from
+        now on the handle also keeps sums and counts per shell radii[k - 1] <= d < radii[k] (gorder_hip_set_radial_shells).
+        Before the first submit or right after reset(); an empty list switches the shells off."""
+        r = np.ascontiguousarray([] if radii is None else radii, dtype=np.float32).reshape(-1)
+        self._check(self.lib.gorder_hip_set_radial_shells(self._h, r.ctypes.data_as(C.c_void_p) if r.size else None, r.size))
+        self._n_shells = int(r.size)
+
+    def radial_shells(self) -> List[Results]:
+        """One Results per shell (sums, counts [3, n_acc] as finish() gives them, n_frames the frames analysed so far): raw
+        integers, the shells of several shards add up element by element (gorder_hip_radial_shells).  Waits like finish()."""
+        n = C.c_uint32()
+        k = self._n_shells
+        sums = np.zeros((max(k, 1), 3, self.n_acc), dtype=np.int64)
+        counts = np.zeros((max(k, 1), 3, self.n_acc), dtype=np.uint64)
+        self._check(self.lib.gorder_hip_radial_shells(self._h, sums.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p), C.byref(n)))
+        assert n.value == k
+        nf = C.c_uint64()
+        self._check(self.lib.gorder_hip_finish(self._h, None, None, None, None, C.byref(nf)))
+        return [Results(sums[q], counts[q], int(nf.value)) for q in range(k)]
 
     def collected_counts(self):
         """(leaflet rows, normal rows) collected so far; does not wait."""

@@ -53,6 +53,7 @@ using gorder::Tile;
 #include "kernels_common.h"
 #include "kernels_bonds.h"
 #include "kernels_extras.h"
+#include "kernels_radial.h"
 #include "kernels_leaflets.h"
 #include "kernels_cluster.h"
 #include "kernels_cluster_cutoff.h"
@@ -280,6 +281,14 @@ struct gorder_hip_handle {
     uint32_t ntable_step = 1;
     uint32_t *d_nrow = nullptr;                 // per frame of the batch: its row of d_ntable
     size_t nrow_cap = 0;
+    // radial shells (gorder_hip_set_radial_shells; kernels_radial.h): the accumulators [n_shells][4][n_acc] laid out like d_acc,
+    // their replicas [shell_rep][n_shells][4][n_acc] (k_bonds_shells adds into them, k_fold_replicas folds them)
+    uint32_t n_shells = 0, shell_rep = 1;
+    float shell_thr[GORDER_RADIAL_MAX_SHELLS] = {};          // local_radius_threshold of the radii
+    unsigned long long *d_shell_acc = nullptr, *d_shell_rep = nullptr;
+    size_t shell_lds_bytes = 0;                 // the LDS table of the widest tile
+    bool shell_direct = false;                  // per-sample global atomics: the table does not fit, or ...
+    bool shell_force_direct = false;            // ... GORDER_HIP_RADIAL_DIRECT, read once at gorder_hip_create
 };
 
 namespace {
@@ -600,7 +609,9 @@ int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &
             for (int pass = 0; pass < 2; pass++) {      // the bond tiles, then the united-atom tiles
                 const uint32_t nt = pass == 0 ? (route.extras ? n_tiles : 0u) : (uint32_t)p.ua_tiles.size();
                 if (!nt) continue;
-                const FrameChunks c = gorder::extras_chunks(nf, nt, h->wg_target, h->wg_capacity, staged, pass == 0 && route.family == BondFamily::TiledTw);
+                const FrameChunks c = pass == 0 && route.family == BondFamily::Shells
+                                          ? gorder::shells_chunks(nf, nt, h->wg_target, h->wg_capacity, kShellChunkMax)
+                                          : gorder::extras_chunks(nf, nt, h->wg_target, h->wg_capacity, staged, pass == 0 && route.family == BondFamily::TiledTw);
                 FrameArgs b = a;
                 b.frame0 = lo; b.n_frames = hi; b.frames_per_chunk = c.frames_per_chunk;
                 e.map_rec = staged ? h->d_map_rec : nullptr;
@@ -610,7 +621,17 @@ int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &
                 if (pass == 0) {
                     const Item *items = route.items_by_slot ? h->d_items_by_slot : h->d_items;
                     TIMING_MARK(h, route.label);
-                    if (route.family == BondFamily::Extras)
+                    if (route.family == BondFamily::Shells) {
+                        ShellArgs sa{};
+                        sa.n = h->n_shells; sa.rep = h->d_shell_rep; sa.n_rep = h->shell_rep;
+                        for (uint32_t k = 0; k < GORDER_RADIAL_MAX_SHELLS; k++) sa.thr[k] = k < h->n_shells ? h->shell_thr[k] : INFINITY;
+                        // the table of the widest tile, or the [2][256] u64 + [2][256] u32 of the direct route's reduction
+                        const size_t lds = h->shell_direct ? (size_t)kBlock * 24u : h->shell_lds_bytes;
+                        with_bool(ac, [&](auto AC) { with_bool(h->shell_direct, [&](auto DIRECT) {
+                            hipLaunchKernelGGL((k_bonds_shells<AC(), DIRECT()>), g, blk, lds, h->stream, b, e, sa, b.xyz, b.box9, b.aflags, b.arow,
+                                               h->d_tiles, items, h->d_tile_slots, nt);
+                        }); });
+                    } else if (route.family == BondFamily::Extras)
                         with_bool(ac, [&](auto AC) { with_bool(route.maps_only, [&](auto MO) {
                             hipLaunchKernelGGL((k_bonds_extras<AC(), MO()>), g, blk, 0, h->stream, b, e, b.xyz, b.box9, b.aflags, b.arow,
                                                h->d_tiles, items, h->d_tile_slots, nt);
@@ -1173,6 +1194,7 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
         h->extra.axis = h->axis;
     }
     if (const char *e = getenv("GORDER_HIP_KERNEL")) h->use_gather = strcmp(e, "gather") == 0;
+    h->shell_force_direct = env_flag("GORDER_HIP_RADIAL_DIRECT");
     if (const char *e = getenv("GORDER_HIP_WG_TARGET")) {
         const int w = atoi(e);
         if (w > 0) h->wg_target = (uint32_t)w;
@@ -1427,6 +1449,7 @@ void gorder_hip_destroy(gorder_hip_handle *h) {
     (void)hipFree(h->d_dyn_rec); (void)hipFree(h->d_dyn_normals); (void)hipFree(h->d_dyn_cov);
     if (!h->acc_external) (void)hipFree(h->d_acc);
     (void)hipFree(h->d_rep);
+    (void)hipFree(h->d_shell_acc); (void)hipFree(h->d_shell_rep);
     (void)hipFree(h->d_heads); (void)hipFree(h->d_membrane); (void)hipFree(h->d_methyl_begin);
     (void)hipFree(h->d_methyl_atoms); (void)hipFree(h->d_aflags); (void)hipFree(h->d_adist);
     (void)hipFree(h->d_sph_spill); (void)hipFree(h->d_sph_stats);
@@ -1837,6 +1860,7 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
     ri.use_gather = h->use_gather; ri.item_run = h->d_item_run != nullptr; ri.frames_per_stage = h->frames_per_stage; ri.max_window = p.max_window;
     ri.bond_tiles = !p.tiles.empty(); ri.ua_tiles = !p.ua_tiles.empty(); ri.direct_items = !p.direct.empty(); ri.ua_fast_flag = (h->tables.flags & GORDER_FLAG_UA_FAST_NORMALISE) != 0;
     ri.global_leaflets = lf.method == GORDER_LEAFLETS_GLOBAL; ri.spec_enabled = h->spec_enabled; ri.have_assignment = h->have_assignment;
+    ri.shells = h->n_shells != 0;
     ri.npf5 = env_flag("GORDER_HIP_NPF5"); ri.tw_gather = env_flag("GORDER_HIP_TW_GATHER"); ri.maps_gather = env_flag("GORDER_HIP_MAPS_GATHER");
     std::vector<uint32_t> spec_aframes;
     std::vector<uint64_t> collect_frames;       // collected leaflets: the assignment frames of this batch = rows 1.. of d_aflags
@@ -2217,6 +2241,7 @@ int gorder_hip_finish(gorder_hip_handle *h, int64_t *sums, uint64_t *counts, int
 int gorder_hip_set_normals(gorder_hip_handle *h, const float *normals, uint32_t n_frames) {
     if (!h || !normals || n_frames == 0) return GORDER_ERR_INVALID_ARGUMENT;
     if (h->d_ntable) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_normals: a manual normal table is set");
+    if (h->n_shells) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_normals: the handle has radial shells (static normals only)");
     const size_t n = (size_t)n_frames * h->plan.n_mol_total;
     h->manual_normals.resize(4 * n);
     for (size_t i = 0; i < n; i++) {
@@ -2267,6 +2292,7 @@ int gorder_hip_set_manual_leaflet_table(gorder_hip_handle *h, const uint8_t *fla
 
 int gorder_hip_set_manual_normal_table(gorder_hip_handle *h, const float *normals, uint32_t step, uint64_t first_row, uint64_t n_rows) {
     if (!h || (n_rows && !normals)) return GORDER_ERR_INVALID_ARGUMENT;
+    if (h->n_shells) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_normal_table: the handle has radial shells (static normals only)");
     const uint32_t n_mol = h->plan.n_mol_total;
     if (n_rows) {
         if (step == 0) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_normal_table: step 0");
@@ -2563,6 +2589,103 @@ int gorder_hip_set_collect(gorder_hip_handle *h, uint32_t what) {
     return GORDER_OK;
 }
 
+// ---- radial shells (kernels_radial.h) -----------------------------------------------------------------------------------
+int gorder_hip_radial_thresholds(const float *radii, uint32_t n, float *thr) {
+    if ((n && !radii) || (n && !thr)) return GORDER_ERR_INVALID_ARGUMENT;
+    for (uint32_t k = 0; k < n; k++) thr[k] = local_radius_threshold(radii[k]);
+    return GORDER_OK;
+}
+
+int gorder_hip_set_radial_shells(gorder_hip_handle *h, const float *radii, uint32_t n_radii) {
+    if (!h || (n_radii && !radii)) return GORDER_ERR_INVALID_ARGUMENT;
+    const char *who = "gorder_hip_set_radial_shells: ";
+    auto refuse = [&](const char *why) { return fail(h, GORDER_ERR_INVALID_ARGUMENT, std::string(who) + why); };
+    if (h->collect_locked) return refuse("only before the first submit or prime, or right after gorder_hip_reset");
+    const Plan &p = h->plan;
+    if (n_radii) {
+        const gorder_tables_t &t = h->tables;
+        if (n_radii > GORDER_RADIAL_MAX_SHELLS) return refuse("more than GORDER_RADIAL_MAX_SHELLS radii");
+        if (t.geometry.kind != GORDER_GEOM_CYLINDER && t.geometry.kind != GORDER_GEOM_SPHERE)
+            return refuse("the tables select no cylinder or sphere");
+        if (t.geometry.invert) return refuse("the selection is inverted");
+        if (!p.ua_tiles.empty()) return refuse("united-atom molecule types");
+        if (h->extra.maps) return refuse("ordermaps are on");
+        if (h->extra.tw) return refuse("timewise is on");
+        if (h->dyn) return refuse("dynamic membrane normals");
+        if (h->d_ntable) return refuse("a manual normal table is set");
+        if (h->manual_frames) return refuse("normals were supplied by gorder_hip_set_normals");
+        // (GORDER_COLLECT_NORMALS needs dynamic normals, gorder_hip_set_collect: refused above with them)
+        if (!p.n_acc || p.tiles.empty()) return refuse("no bond samples");
+        float thr[GORDER_RADIAL_MAX_SHELLS];
+        for (uint32_t k = 0; k < n_radii; k++) {
+            if (!std::isfinite(radii[k]) || !(radii[k] > 0.0f)) return refuse("a radius is not finite and > 0");
+            if (k && !(radii[k] > radii[k - 1])) return refuse("the radii are not strictly ascending");
+            thr[k] = local_radius_threshold(radii[k]);
+            if (k && thr[k] < thr[k - 1]) return refuse("the radii's thresholds do not ascend");       // (sqrt is monotonic: never)
+        }
+        if (memcmp(&radii[n_radii - 1], &t.geometry.radius, sizeof(float)) != 0 || thr[n_radii - 1] != h->extra.geom_thr)
+            return refuse("the last radius is not tables.geometry.radius");
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));       // (a reset still queued may be zeroing the old blocks)
+        (void)hipFree(h->d_shell_acc); (void)hipFree(h->d_shell_rep);
+        h->d_shell_acc = h->d_shell_rep = nullptr;
+        h->n_shells = 0;
+        // replicas against contention on the global shell words, as the ordinary sums have them; fewer where the block would pass 64 MiB
+        const size_t words = (size_t)n_radii * 4u * p.n_acc;
+        uint32_t n_rep = h->n_rep;
+        while (n_rep > 1 && (size_t)n_rep * words * sizeof(unsigned long long) > ((size_t)64 << 20)) n_rep /= 2;
+        HIP_TRY(h, hipMalloc((void **)&h->d_shell_acc, words * sizeof(unsigned long long)));
+        HIP_TRY(h, hipMalloc((void **)&h->d_shell_rep, (size_t)n_rep * words * sizeof(unsigned long long)));
+        HIP_TRY(h, hipMemset(h->d_shell_acc, 0, words * sizeof(unsigned long long)));
+        HIP_TRY(h, hipMemset(h->d_shell_rep, 0, (size_t)n_rep * words * sizeof(unsigned long long)));
+        uint32_t max_slots = 1;
+        for (const Tile &tile : p.tiles) max_slots = std::max(max_slots, tile.n_slots);
+        const uint32_t planes = t.leaflets.method != GORDER_LEAFLETS_NONE ? 2u : 1u;
+        h->shell_lds_bytes = (size_t)planes * n_radii * max_slots * sizeof(unsigned long long);
+        h->shell_direct = h->shell_force_direct || h->shell_lds_bytes > 64u * 1024u;
+        h->shell_rep = n_rep;
+        for (uint32_t k = 0; k < n_radii; k++) h->shell_thr[k] = thr[k];
+        h->n_shells = n_radii;
+        return GORDER_OK;
+    }
+    if (h->n_shells) {
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        (void)hipFree(h->d_shell_acc); (void)hipFree(h->d_shell_rep);
+        h->d_shell_acc = h->d_shell_rep = nullptr;
+        h->n_shells = 0;
+    }
+    return GORDER_OK;
+}
+
+int gorder_hip_radial_shells(gorder_hip_handle *h, int64_t *sums, uint64_t *counts, uint32_t *n_shells) {
+    if (!h) return GORDER_ERR_INVALID_ARGUMENT;
+    if (n_shells) *n_shells = h->n_shells;
+    if (!h->n_shells) return GORDER_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const uint32_t n = h->plan.n_acc;
+    const size_t words = (size_t)h->n_shells * 4u * n;
+    hipLaunchKernelGGL(k_fold_replicas, dim3((uint32_t)((words + 255) / 256)), dim3(256), 0, h->stream, h->d_shell_acc, h->d_shell_rep,
+                       h->shell_rep, (uint32_t)words);
+    HIP_TRY(h, hipGetLastError());
+    const int st = gorder_hip_synchronize(h);
+    if (st != GORDER_OK) return st;
+    std::vector<unsigned long long> raw(words);
+    HIP_TRY(h, hipMemcpy(raw.data(), h->d_shell_acc, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    const bool lf = h->tables.leaflets.method != GORDER_LEAFLETS_NONE;
+    for (uint32_t k = 0; k < h->n_shells; k++) {
+        const unsigned long long *r = raw.data() + (size_t)k * 4u * n;
+        for (uint32_t s = 0; s < n; s++) {
+            const int64_t tot = (int64_t)r[s], up = (int64_t)r[n + s];
+            const uint64_t ctot = r[2 * (size_t)n + s], cup = r[3 * (size_t)n + s];
+            const size_t o = (size_t)k * 3u * n + s;
+            if (sums) { sums[o] = tot; sums[o + n] = lf ? up : 0; sums[o + 2 * (size_t)n] = lf ? tot - up : 0; }
+            if (counts) { counts[o] = ctot; counts[o + n] = lf ? cup : 0; counts[o + 2 * (size_t)n] = lf ? ctot - cup : 0; }
+        }
+    }
+    return GORDER_OK;
+}
+
 int gorder_hip_collected_counts(gorder_hip_handle *h, uint64_t *n_leaflet_rows, uint64_t *n_normal_rows) {
     if (!h) return GORDER_ERR_INVALID_ARGUMENT;
     if (n_leaflet_rows) *n_leaflet_rows = (h->collect & GORDER_COLLECT_LEAFLETS) ? h->collect_flags.n_rows() : 0;
@@ -2678,6 +2801,11 @@ int gorder_hip_reset(gorder_hip_handle *h) {
     HIP_TRY(h, hipMemsetAsync(h->d_acc, 0, h->acc_words * sizeof(unsigned long long), h->stream));
     if (h->d_rep) HIP_TRY(h, hipMemsetAsync(h->d_rep, 0, (size_t)h->n_rep * 4u * p.n_acc * sizeof(unsigned long long), h->stream));
     h->rep_dirty = false;
+    if (h->n_shells) {      // (the radii stay)
+        const size_t words = (size_t)h->n_shells * 4u * p.n_acc;
+        HIP_TRY(h, hipMemsetAsync(h->d_shell_acc, 0, words * sizeof(unsigned long long), h->stream));
+        HIP_TRY(h, hipMemsetAsync(h->d_shell_rep, 0, (size_t)h->shell_rep * words * sizeof(unsigned long long), h->stream));
+    }
     if (h->extra.maps) {
         const size_t nmap = 3 * (size_t)p.n_acc * h->map_nx * h->map_ny;
         const size_t npk = (h->tables.leaflets.method != GORDER_LEAFLETS_NONE ? 2 : 1) * (nmap / 3);

@@ -5,6 +5,7 @@
 //   per-frame rows only, or rows + staged maps; default cosine, LDS staging, item runs   -> TiledTw
 //   staged maps only; default cosine, LDS staging                                         -> TiledMaps
 //   any other extras                                                                      -> Extras
+//   radial shells (gorder_hip_set_radial_shells: a cylinder or sphere selection, no other extra) -> Shells
 //   united-atom tiles                                                                     -> k_ua_extras<mode> (+ _fast)
 // A batch speculates (one read for global leaflets and order parameters) only where Tiled or the unstaged TiledTw runs:
 // those are the kernels with a MOM variant, and k_spec_check / k_spec_fixup read what that variant wrote.
@@ -29,8 +30,10 @@ struct OrderRouteIn {
     bool global_leaflets = false, spec_enabled = false, have_assignment = false, every_frame_assigns = false, manual_frames = false, normal_table = false;
     // switches (GORDER_HIP_NPF5, GORDER_HIP_TW_GATHER, GORDER_HIP_MAPS_GATHER)
     bool npf5 = false, tw_gather = false, maps_gather = false;
+    // radial shells are set on the handle (they come with a geometry selection and exclude every other extra)
+    bool shells = false;
 };
-enum class BondFamily { None, Tiled, Gather, TiledTw, TiledMaps, Extras };
+enum class BondFamily { None, Tiled, Gather, TiledTw, TiledMaps, Extras, Shells };
 
 struct OrderRoute {
     BondFamily family = BondFamily::None;   // what runs over the bond tiles
@@ -55,10 +58,11 @@ inline OrderRoute choose_order_route(const OrderRouteIn &in) {
     r.npf = (3u * in.max_window + 6u) / 4u <= 4u * 64u && !in.npf5 ? 4 : 5;      // enough float4 for the widest window (64 threads stage a frame)
     if (!in.bond_tiles) r.family = BondFamily::None;
     else if (!r.extras) r.family = in.use_gather ? BondFamily::Gather : BondFamily::Tiled;
+    else if (in.shells) r.family = BondFamily::Shells;
     else if (r.maps_only && tiled_out && !in.maps_gather) r.family = BondFamily::TiledMaps;
     else if (in.tw && (!in.maps || staged) && rows_or_maps_only && tiled_out && in.item_run && !in.tw_gather) r.family = BondFamily::TiledTw;
     else r.family = BondFamily::Extras;
-    static const char *const labels[] = {nullptr, "k_bonds_tiled", "k_bonds_gather", "k_bonds_tiled_tw", "k_bonds_tiled_maps", "k_bonds_extras"};
+    static const char *const labels[] = {nullptr, "k_bonds_tiled", "k_bonds_gather", "k_bonds_tiled_tw", "k_bonds_tiled_maps", "k_bonds_extras", "k_bonds_shells"};
     r.label = labels[(int)r.family];
     r.tw_maps = r.family == BondFamily::TiledTw && staged;
     r.items_by_slot = r.family == BondFamily::TiledTw || r.family == BondFamily::TiledMaps || (r.family == BondFamily::Extras && staged);
@@ -94,6 +98,13 @@ inline FrameChunks extras_chunks(uint32_t n_frames, uint32_t n_tiles, uint32_t w
     if (staged) fpc = ceil_div(fpc, 16u) * 16u;
     if (whole_stages) fpc = ceil_div(fpc, kStageFrames) * kStageFrames;
     return {fpc, ceil_div(n_frames, fpc)};
+}
+
+// k_bonds_shells: the extras' chunks, none longer than max_chunk frames (the packed words of a workgroup's shell table)
+inline FrameChunks shells_chunks(uint32_t n_frames, uint32_t n_tiles, uint32_t wg_target, uint32_t wg_capacity, uint32_t max_chunk) {
+    const FrameChunks c = extras_chunks(n_frames, n_tiles, wg_target, wg_capacity, false, false);
+    if (c.frames_per_chunk <= max_chunk) return c;
+    return {max_chunk, ceil_div(n_frames, max_chunk)};
 }
 
 // k_bonds_direct: blocks_per_chunk workgroups cover the items of one chunk of frames

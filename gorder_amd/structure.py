@@ -537,6 +537,37 @@ def estimate_error(sums: np.ndarray, counts: np.ndarray, n_blocks: int = 5) -> f
     return float(np.sqrt(np.float32(var / np.float32(n_blocks - 1)), dtype=np.float32))
 
 
+# ---- radial profiles (HipEngine.radial_shells): this project's own output, the reference has none ----------
+def radial_counts(shells, groups) -> np.ndarray:
+    """Samples uint64 [n_groups, 3, n_shells] of every group (a list of accumulator slots, as error_groups gives them),
+    leaflet and shell of HipEngine.radial_shells()."""
+    out = np.zeros((len(groups), 3, len(shells)), dtype=np.uint64)
+    for k, res in enumerate(shells):
+        counts = np.asarray(res.counts, dtype=np.uint64)
+        for g, slots in enumerate(groups):
+            out[g, :, k] = counts[:, [int(q) for q in slots]].sum(axis=1, dtype=np.uint64)
+    return out
+
+
+def radial_profile(shells, radii, groups, analysis: str, min_samples: int = 1) -> np.ndarray:
+    """Order parameter by distance: float32 [n_groups, 3, n_shells] (total, upper, lower) from the per-shell Results of
+    HipEngine.radial_shells() with its `radii`.  A group's value in a shell comes from the added tick sums and sample counts
+    of its slots by calc_order's truncating division (Results.order, _mean_ticks), negated for "aa" like every all-atom
+    output; NaN below min_samples (and in the upper and lower rows of an analysis without leaflets)."""
+    if len(shells) != len(radii):
+        raise ValueError(f"{len(shells)} shells for {len(radii)} radii")
+    sign = -1.0 if analysis == "aa" else 1.0
+    out = np.full((len(groups), 3, len(shells)), np.nan, dtype=np.float32)
+    for k, res in enumerate(shells):
+        sums, counts = np.asarray(res.sums, dtype=np.int64), np.asarray(res.counts, dtype=np.uint64)
+        for g, slots in enumerate(groups):
+            slots = [int(q) for q in slots]
+            for w in range(3):
+                v = _mean_ticks(int(sums[w, slots].sum(dtype=np.int64)), int(counts[w, slots].sum(dtype=np.uint64)), min_samples)
+                out[g, w, k] = v if v != v else np.float32(sign * v)
+    return out
+
+
 # ---- ordermaps: which maps the reference writes, and their values (presentation layer arithmetic) ----------
 @dataclass
 class OrdermapGroup:

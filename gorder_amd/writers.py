@@ -317,6 +317,34 @@ def normals_export_text(normals, frames, labels, header: Optional[str] = None) -
     return "\n".join(out) + "\n"
 
 
+def radial_profile_text(values, counts, radii, names, header: Optional[str] = None) -> str:
+    """A radial profile as text (this project's own layout: the reference has no such file), from the values
+    [n_groups, 3, n_shells] of structure.radial_profile, the radii given to HipEngine.set_radial_shells and one name per
+    group: one row per shell — `r_inner r_outer` in nm, then per group its full, upper and lower value with four decimals,
+    NaN as `NaN` — under `#` lines that name the columns.  counts [n_groups, 3, n_shells] (structure.radial_counts), or
+    None: with them every group gets a fourth column, the samples behind its full value."""
+    if len(values) != len(names) or any(len(w) != len(radii) for v in values for w in v):
+        raise ValueError("values [n_groups, 3, n_shells], one name per group, one radius per shell")
+    if counts is not None and (len(counts) != len(names) or any(len(c[0]) != len(radii) for c in counts)):
+        raise ValueError("counts [n_groups, 3, n_shells]")
+    out = [header or "# radial profile of order parameters",
+           "# shell k holds the samples at distance r_inner <= d < r_outer [nm] from the reference of the selection",
+           "# column 1: r_inner", "# column 2: r_outer"]
+    col = 3
+    for name in names:
+        for which in ("full", "upper", "lower") + (("samples",) if counts is not None else ()):
+            out.append(f"# column {col}: {name} {which}")
+            col += 1
+    for k, r in enumerate(radii):
+        cells = [_fixed(float(radii[k - 1]) if k else 0.0), _fixed(float(r))]
+        for g in range(len(names)):
+            cells += [f"{_fixed(float(values[g][w][k])):>8s}" for w in range(3)]
+            if counts is not None:
+                cells.append(str(int(counts[g][0][k])))
+        out.append(" ".join(cells))
+    return "\n".join(out) + "\n"
+
+
 _PLANE_LABELS = {0: ("x", "y"), 1: ("x", "z"), 2: ("z", "y")}     # Plane::get_labels (input/ordermap.rs:54-60)
 _LEAFLET_NAMES = ("full", "upper", "lower")
 

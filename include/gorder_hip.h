@@ -515,6 +515,38 @@ int gorder_hip_collected_leaflets(gorder_hip_handle *h, uint8_t *flags, uint64_t
 int gorder_hip_collected_normals(gorder_hip_handle *h, float *normals, uint64_t *frames,
                                  uint64_t capacity_rows, uint64_t *n_rows);
 
+/* ---- radial profiles: order sums by distance from the selection's reference, in the same pass -----------------------------
+ * A handle whose tables select a cylinder or a sphere can be given ascending radii r[0] < ... < r[n - 1], the last one equal to
+ * tables.geometry.radius bit for bit.  Next to everything else it does, it then keeps one (tick sum, sample count) set per shell,
+ * accumulator slot and leaflet: shell k holds the samples that pass the tables' selection and have r[k - 1] <= d < r[k]
+ * (r[-1] = 0), d the distance the selection itself tests — in the cylinder's plane, or from the sphere's centre.  Membership is
+ * the reference's `sqrtf(d2) < r` (groan_rs Cylinder / Sphere ::inside), so selections of increasing radius around one reference
+ * are nested exactly, shell k is the integer difference of the selections of radius r[k] and r[k - 1], and the shells add up to
+ * what gorder_hip_finish returns.  The kernel is k_bonds_shells (its name in gorder_hip_kernel_time_names / _group); a handle
+ * that never calls gorder_hip_set_radial_shells queues exactly what it queued before.
+ * gorder_hip_set_radial_shells: accepted before the first submit / prime or right after gorder_hip_reset (the rule of
+ *   gorder_hip_set_collect); n_radii = 0 switches the shells off.  GORDER_ERR_INVALID_ARGUMENT, with the reason in
+ *   gorder_hip_last_error_message, for radii that are not finite, not > 0, not strictly ascending, more than
+ *   GORDER_RADIAL_MAX_SHELLS, or whose last differs from tables.geometry.radius; for a geometry kind other than cylinder or
+ *   sphere; for geometry.invert; united-atom molecule types; ordermaps; timewise; dynamic membrane normals; a manual normal table
+ *   or normals supplied by gorder_hip_set_normals; GORDER_COLLECT_NORMALS.  A handle with shells in turn refuses
+ *   gorder_hip_set_normals and gorder_hip_set_manual_normal_table.  Everything else combines: every leaflet method (manual
+ *   tables and GORDER_COLLECT_LEAFLETS included), flip, any frequency, a static normal on an axis or general, both cosine modes,
+ *   periodic boundaries or none, all three reference kinds, a cylinder with a finite span and any orientation.
+ * gorder_hip_radial_shells: sums / counts [n_shells][3][n_acc], the leading index of a shell total / upper / lower as in
+ *   gorder_hip_finish (upper and lower are 0 without leaflets).  Raw integers that add element-wise: shards add them on the host —
+ *   gorder_hip_allreduce does NOT carry them.  Waits for the queued batches like gorder_hip_finish (a device error of the run is
+ *   returned).  Either array may be NULL; *n_shells is set when the pointer is given (0: shells are off, nothing is written).
+ * gorder_hip_reset zeroes the shells; the radii stay.
+ * Not covered: united atoms, cuboid selections, per-shell error estimates and convergence.
+ * gorder_hip_radial_thresholds (host only, no device): thr[k] = the smallest float whose correctly rounded square root reaches
+ *   radii[k], so that `d2 < thr[k]` is exactly `sqrtf(d2) < radii[k]` — what the kernel compares against (0 for a radius that
+ *   is not > 0). */
+#define GORDER_RADIAL_MAX_SHELLS 32
+int gorder_hip_set_radial_shells(gorder_hip_handle *h, const float *radii, uint32_t n_radii);
+int gorder_hip_radial_shells(gorder_hip_handle *h, int64_t *sums, uint64_t *counts, uint32_t *n_shells);
+int gorder_hip_radial_thresholds(const float *radii, uint32_t n, float *thr);
+
 /* Signed distances (nm) behind those flags, [n_molecules_total] (leaflets.rs:725, 796).  GORDER_LEAFLETS_SPHERICAL: each
  * molecule's head-centre distance (nm, non-negative) in the last assignment frame. */
 int gorder_hip_leaflet_distances(gorder_hip_handle *h, float *distances);
