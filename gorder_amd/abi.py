@@ -327,6 +327,7 @@ _EXPORTS = [
     "gorder_hip_timewise_chunk_frames", "gorder_hip_timewise_rows", "gorder_hip_timewise_blocks", "gorder_hip_error_estimate",
     "gorder_hip_convergence", "gorder_hip_ordermaps",
     "gorder_hip_set_radial_shells", "gorder_hip_radial_shells", "gorder_hip_radial_thresholds",
+    "gorder_hip_set_molecule_rows", "gorder_hip_molecule_rows_count", "gorder_hip_molecule_rows", "gorder_hip_molecule_rows_stats",
 ]
 
 _lib = None
@@ -430,6 +431,10 @@ def load_library() -> C.CDLL:
     lib.gorder_hip_set_radial_shells.argtypes = [vp, vp, u32]
     lib.gorder_hip_radial_shells.argtypes = [vp, vp, vp, C.POINTER(u32)]
     lib.gorder_hip_radial_thresholds.argtypes = [vp, u32, vp]
+    lib.gorder_hip_set_molecule_rows.argtypes = [vp, vp, vp, u32]
+    lib.gorder_hip_molecule_rows_count.argtypes = [vp, C.POINTER(u64)]
+    lib.gorder_hip_molecule_rows.argtypes = [vp, vp, vp, vp, u64]
+    lib.gorder_hip_molecule_rows_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u32), C.POINTER(u32)]
     _lib = lib
     return lib
 
@@ -567,6 +572,7 @@ class HipEngine:
         self.n_acc = self.lib.gorder_hip_n_accumulators(self._h)
         self._keep = []
         self._n_shells = 0
+        self._n_mol_groups = 0
 
     def close(self):
         if getattr(self, "_h", None):
@@ -872,6 +878,42 @@ class HipEngine:
         nf = C.c_uint64()
         self._check(self.lib.gorder_hip_finish(self._h, None, None, None, None, C.byref(nf)))
         return [Results(sums[q], counts[q], int(nf.value)) for q in range(k)]
+
+    def set_molecule_rows(self, groups):
+        """Keep, from now on, every molecule's own tick sum and sample count per analysed frame and group — a group is a list
+        of accumulator slots, the groups are disjoint (gorder_hip_set_molecule_rows; structure.molecule_groups makes one per
+        molecule type).  Before the first submit or right after reset(); an empty list switches the rows off."""
+        groups = [] if groups is None else list(groups)
+        begin, slots = _pack_groups(groups)
+        self._check(self.lib.gorder_hip_set_molecule_rows(self._h, begin.ctypes.data_as(C.c_void_p), slots.ctypes.data_as(C.c_void_p),
+                                                          len(groups)))
+        self._n_mol_groups = len(groups)
+
+    def molecule_rows_count(self) -> int:
+        """Per-molecule rows kept so far (one per analysed frame); does not wait."""
+        n = C.c_uint64()
+        self._check(self.lib.gorder_hip_molecule_rows_count(self._h, C.byref(n)))
+        return int(n.value)
+
+    def molecule_rows_stats(self) -> dict:
+        """Facts of the lane order built by set_molecule_rows (gorder_hip_molecule_rows_stats): n_runs = global atomics per
+        frame, max_runs_per_tile, max_tiles_per_word = tiles that add into one (group, molecule) word."""
+        a, b, c = C.c_uint64(), C.c_uint32(), C.c_uint32()
+        self._check(self.lib.gorder_hip_molecule_rows_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"n_runs": int(a.value), "max_runs_per_tile": int(b.value), "max_tiles_per_word": int(c.value)}
+
+    def molecule_rows(self):
+        """Every analysed frame since set_molecule_rows / reset -> (sums int32 [rows, n_groups, n_molecules_total]: tick sums
+        of each molecule's samples in each group, counts uint32 likewise, frames uint64 [rows]: the frames' global indices).
+        Waits like finish().  structure.molecule_order turns them into order parameters."""
+        rows = self.molecule_rows_count()
+        shape = (rows, self._n_mol_groups, self.tables.n_molecules_total)
+        sums, counts = np.zeros(shape, dtype=np.int32), np.zeros(shape, dtype=np.uint32)
+        frames = np.zeros(rows, dtype=np.uint64)
+        self._check(self.lib.gorder_hip_molecule_rows(self._h, sums.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
+                                                      frames.ctypes.data_as(C.c_void_p), rows))
+        rows_now = self.molecule_rows_count()      # (a device error that surfaced while waiting drops the failed batch's rows)
+        return sums[:rows_now], counts[:rows_now], frames[:rows_now]
 
     def collected_counts(self):
         """(leaflet rows, normal rows) collected so far; does not wait."""

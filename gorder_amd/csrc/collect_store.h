@@ -106,6 +106,20 @@ public:
             for (size_t k = 0; k < c.used; k++) f(r++, static_cast<const void *>(c.p + k * row_bytes_));
     }
 
+    // forget the rows from row `n_rows` on (a batch that failed after it had reserved); the chunks stay
+    void truncate(uint64_t n_rows) {
+        if (n_rows >= frames_.size()) return;
+        frames_.resize((size_t)n_rows);
+        size_t left = (size_t)n_rows;
+        cur_ = 0;
+        for (size_t k = 0; k < chunks_.size(); k++) {
+            Chunk &c = chunks_[k];
+            c.used = left < c.used ? left : c.used;
+            left -= c.used;
+            if (c.used) cur_ = k;
+        }
+    }
+
     void clear() {
         for (Chunk &c : chunks_) c.used = 0;
         cur_ = 0;

@@ -41,6 +41,7 @@
 #include "timewise_blocks.h"
 #include "ordermap_final.h"
 #include "order_route.h"
+#include "molecule_rows.h"
 
 #pragma clang fp contract(off)
 
@@ -53,6 +54,7 @@ using gorder::Tile;
 #include "kernels_common.h"
 #include "kernels_bonds.h"
 #include "kernels_extras.h"
+#include "kernels_molrows.h"
 #include "kernels_radial.h"
 #include "kernels_leaflets.h"
 #include "kernels_cluster.h"
@@ -289,6 +291,19 @@ struct gorder_hip_handle {
     size_t shell_lds_bytes = 0;                 // the LDS table of the widest tile
     bool shell_direct = false;                  // per-sample global atomics: the table does not fit, or ...
     bool shell_force_direct = false;            // ... GORDER_HIP_RADIAL_DIRECT, read once at gorder_hip_create
+    // per-molecule rows (gorder_hip_set_molecule_rows; molecule_rows.h, kernels_molrows.h): the lane order and the run tables,
+    // the staging block of one frame sub-range [frames][n_groups][n_mol_total] packed words, and the rows in pinned chunks
+    gorder::MolRows mol;                        // mol.n_groups != 0: the rows are on
+    Item *d_mol_items = nullptr;
+    gorder::MolRun *d_mol_runs = nullptr;
+    uint32_t *d_mol_run_begin = nullptr;
+    unsigned long long *d_mol_stage = nullptr;
+    size_t mol_stage_cap = 0;
+    size_t mol_stage_bytes = (size_t)1 << 30;   // GORDER_HIP_MOL_ROWS_STAGING, read once at gorder_hip_create
+    gorder::CollectStore mol_store;             // rows of n_groups x n_mol_total u64
+    const uint64_t *mol_frame_index = nullptr;  // the batch being submitted: its frames' labels
+    bool mol_failed = false;                    // a device error ended the run: its batch and the later ones append nothing
+    std::deque<std::pair<uint64_t, uint64_t>> mol_batch_log;   // (batch ordinal, rows before it), as batch_log
 };
 
 namespace {
@@ -355,7 +370,18 @@ int check_device_error(gorder_hip_handle *h) {
     // [1]: latched at the end of a batch; [0]: raised outside a batch (priming frame, stand-alone decode) and not committed yet
     const bool latched = rec[1] != kErrNone;
     const unsigned long long key = latched ? rec[1] : rec[0];
-    if (key == kErrNone) { h->batch_log.clear(); return GORDER_OK; }
+    if (key == kErrNone) { h->batch_log.clear(); h->mol_batch_log.clear(); return GORDER_OK; }
+    if (latched && !h->mol_failed)      // per-molecule rows: the batch that raised it and the later ones leave no rows (the stream is idle here)
+        if (h->mol.n_groups && !h->mol_batch_log.empty()) {
+            // (a batch older than the log keeps kBatchLog entries of: the rows are cut at the oldest batch still known, which
+            // is later than the failed one — rows are lost, none of a failed batch is kept)
+            uint64_t keep = h->mol_batch_log.front().second;
+            for (const auto &b : h->mol_batch_log)
+                if (b.first <= rec[2]) keep = b.second;
+            if (rec[2] > h->mol_batch_log.back().first) keep = h->mol_store.n_rows();      // (raised by a batch without rows)
+            h->mol_store.truncate(keep);
+            h->mol_failed = true;
+        }
     const uint32_t code = (uint32_t)(key & 15u), detail = (uint32_t)(key >> 4) & 3u, mol = (uint32_t)(key >> 6) & 0x1ffffu;
     const uint32_t sample = (uint32_t)(key >> 23) & 1u, slot = (uint32_t)(key >> 24) & 0x3fffu;
     const uint32_t stage = (uint32_t)(key >> 38) & 3u, frame = (uint32_t)(key >> 40) & 0x7fffffu;
@@ -532,6 +558,44 @@ template <class F> void with_axis(int axis, F &&f) { with_int<2, 1, 0, -1>(axis,
 template <class F> void with_npf(int npf, F &&f) { with_int<4, 5>(npf, f); }
 static_assert(gorder::kStageFrames == kRecFrames && gorder::kStageFrames == (uint32_t)kFramesPerStage, "order_route.h: frames of a stage");
 
+// k_bonds_tiled_mol over the frames of the batch, in sub-ranges the staging block holds: zero the block, run the order pass,
+// queue the copy of the sub-range's rows into the pinned chunks — stream-ordered, nothing waits
+int collect_copy_out(gorder_hip_handle *h, gorder::CollectStore &store, const void *d_block, const uint64_t *frames, size_t n_rows);
+int launch_molecule_rows(gorder_hip_handle *h, const FrameArgs &a, const gorder::OrderRoute &route) {
+    const Plan &p = h->plan;
+    const uint32_t n_tiles = (uint32_t)p.tiles.size();
+    const bool ac = (h->tables.flags & GORDER_FLAG_TRIG_ACOS_COS) != 0;
+    const size_t wpf = (size_t)h->mol.n_groups * p.n_mol_total;
+    const uint32_t sub = gorder::molecule_rows_subrange(a.n_frames, wpf, h->mol_stage_bytes);
+    int st;
+    if ((st = ensure(h, &h->d_mol_stage, &h->mol_stage_cap, wpf * sub)) != GORDER_OK) return st;
+    MolRowArgs mr{};
+    mr.runs = h->d_mol_runs; mr.run_begin = h->d_mol_run_begin; mr.stage = h->d_mol_stage; mr.words_per_frame = (uint32_t)wpf;
+    for (uint32_t lo = 0; lo < a.n_frames; lo += sub) {
+        const uint32_t hi = std::min(a.n_frames, lo + sub), nf = hi - lo;
+        const gorder::FrameChunks c = gorder::extras_chunks(nf, n_tiles, h->wg_target, h->wg_capacity, false, true);
+        const uint64_t grid = (uint64_t)n_tiles * c.n_chunks;
+        if (grid > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "batch too large");
+        FrameArgs b = a;
+        b.frame0 = lo; b.n_frames = hi; b.frames_per_chunk = c.frames_per_chunk;
+        TIMING_MARK(h, route.label);
+        HIP_TRY(h, hipMemsetAsync(h->d_mol_stage, 0, wpf * nf * sizeof(unsigned long long), h->stream));
+        const dim3 g((uint32_t)grid), blk(kBlock);
+        with_npf(route.npf, [&](auto NPF) { with_bool(b.pbc, [&](auto PBC) { with_bool(b.leaflets, [&](auto LF) {
+            if (ac)     // (the literal cosine: the general normal's code for every axis)
+                hipLaunchKernelGGL((k_bonds_tiled_mol<NPF(), true, PBC(), LF(), -1>), g, blk, h->lds_bytes, h->stream, b, mr, b.xyz, b.box9,
+                                   b.aflags, b.arow, h->d_tiles, h->d_mol_items, h->d_tile_slots, n_tiles, h->lw);
+            else with_int<2, -1>(h->axis, [&](auto AX) {      // (a normal along z, or the general code: exact for x and y as well)
+                hipLaunchKernelGGL((k_bonds_tiled_mol<NPF(), false, PBC(), LF(), AX()>), g, blk, h->lds_bytes, h->stream, b, mr, b.xyz, b.box9,
+                                   b.aflags, b.arow, h->d_tiles, h->d_mol_items, h->d_tile_slots, n_tiles, h->lw);
+            });
+        }); }); });
+        HIP_TRY(h, hipGetLastError());
+        if ((st = collect_copy_out(h, h->mol_store, h->d_mol_stage, h->mol_frame_index + lo, nf)) != GORDER_OK) return st;
+    }
+    return GORDER_OK;
+}
+
 // The order kernels of one batch, as `route` has them (every kernel group opens a timing segment of its own).  A combination
 // of template arguments without a kernel (`if constexpr`) is one the route never asks for: tests/test_order_route_cpu.py.
 int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &route) {
@@ -576,6 +640,10 @@ int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &
             }); }); });
         }); }); });
         HIP_TRY(h, hipGetLastError());
+    }
+    if (route.family == BondFamily::TiledMol) {
+        const int st2 = launch_molecule_rows(h, a, route);
+        if (st2 != GORDER_OK) return st2;
     }
     if (route.extras || route.ua_mode >= 0) {
         // scatter-bound modes: plain per-sample kernels (see "Extras" above)
@@ -1195,6 +1263,10 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
     }
     if (const char *e = getenv("GORDER_HIP_KERNEL")) h->use_gather = strcmp(e, "gather") == 0;
     h->shell_force_direct = env_flag("GORDER_HIP_RADIAL_DIRECT");
+    if (const char *e = getenv("GORDER_HIP_MOL_ROWS_STAGING")) {      // bytes of the per-molecule rows' device staging (tests set it small)
+        const long long v = atoll(e);
+        if (v > 0) h->mol_stage_bytes = (size_t)v;
+    }
     if (const char *e = getenv("GORDER_HIP_WG_TARGET")) {
         const int w = atoi(e);
         if (w > 0) h->wg_target = (uint32_t)w;
@@ -1450,6 +1522,8 @@ void gorder_hip_destroy(gorder_hip_handle *h) {
     if (!h->acc_external) (void)hipFree(h->d_acc);
     (void)hipFree(h->d_rep);
     (void)hipFree(h->d_shell_acc); (void)hipFree(h->d_shell_rep);
+    (void)hipFree(h->d_mol_items); (void)hipFree(h->d_mol_runs); (void)hipFree(h->d_mol_run_begin); (void)hipFree(h->d_mol_stage);
+    h->mol_store.release();
     (void)hipFree(h->d_heads); (void)hipFree(h->d_membrane); (void)hipFree(h->d_methyl_begin);
     (void)hipFree(h->d_methyl_atoms); (void)hipFree(h->d_aflags); (void)hipFree(h->d_adist);
     (void)hipFree(h->d_sph_spill); (void)hipFree(h->d_sph_stats);
@@ -1861,6 +1935,7 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
     ri.bond_tiles = !p.tiles.empty(); ri.ua_tiles = !p.ua_tiles.empty(); ri.direct_items = !p.direct.empty(); ri.ua_fast_flag = (h->tables.flags & GORDER_FLAG_UA_FAST_NORMALISE) != 0;
     ri.global_leaflets = lf.method == GORDER_LEAFLETS_GLOBAL; ri.spec_enabled = h->spec_enabled; ri.have_assignment = h->have_assignment;
     ri.shells = h->n_shells != 0;
+    ri.mol_rows = h->mol.n_groups != 0 && !h->mol_failed;
     ri.npf5 = env_flag("GORDER_HIP_NPF5"); ri.tw_gather = env_flag("GORDER_HIP_TW_GATHER"); ri.maps_gather = env_flag("GORDER_HIP_MAPS_GATHER");
     std::vector<uint32_t> spec_aframes;
     std::vector<uint64_t> collect_frames;       // collected leaflets: the assignment frames of this batch = rows 1.. of d_aflags
@@ -1892,7 +1967,9 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
             return fail(h, GORDER_ERR_MANUAL_NORMAL_FRAME, "manual normal table: no row for frame " + std::to_string(bad));
         }
     }
+    const uint64_t mol_rows_before = h->mol_store.n_rows();
     auto abort_batch = [&](int status) {
+        h->mol_store.truncate(mol_rows_before);         // a batch that ends in an error appends no per-molecule rows
         hipLaunchKernelGGL(k_batch_abort, dim3(1), dim3(1), 0, h->stream, h->d_err);
         (void)hipGetLastError();
         (void)timing_mark(h, nullptr);
@@ -2024,7 +2101,9 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
         if (hipMemsetAsync(h->d_touched, 0, nt, h->stream) != hipSuccess) return abort_batch(fail(h, GORDER_ERR_DEVICE, "collect: hipMemsetAsync"));
         h->extra.touched = h->d_touched;
     }
+    h->mol_frame_index = frame_index;
     st = launch_orders(h, a, route);
+    h->mol_frame_index = nullptr;
     h->manual_active = false;
     if (st != GORDER_OK) return abort_batch(st);
     h->rep_dirty = true;
@@ -2088,6 +2167,10 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
             if (frame_index[f] != rec.first + (uint64_t)f * rec.stride) { rec.list.assign(frame_index, frame_index + n_frames); break; }
         if (h->batch_log.size() >= gorder_hip_handle::kBatchLog) h->batch_log.pop_front();
         h->batch_log.push_back(std::move(rec));
+        if (ri.mol_rows) {
+            if (h->mol_batch_log.size() >= gorder_hip_handle::kBatchLog) h->mol_batch_log.pop_front();
+            h->mol_batch_log.push_back({h->n_submits, mol_rows_before});
+        }
         // check_box, total_frames and the batch's error key in one launch behind the batch's kernels
         TIMING_MARK(h, "k_batch_end");
         hipLaunchKernelGGL(k_batch_end, dim3(pbc ? std::min<uint32_t>((n_frames + 255u) / 256u, 256u) : 1u), dim3(256), 0, h->stream,
@@ -2242,6 +2325,7 @@ int gorder_hip_set_normals(gorder_hip_handle *h, const float *normals, uint32_t 
     if (!h || !normals || n_frames == 0) return GORDER_ERR_INVALID_ARGUMENT;
     if (h->d_ntable) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_normals: a manual normal table is set");
     if (h->n_shells) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_normals: the handle has radial shells (static normals only)");
+    if (h->mol.n_groups) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_normals: the handle has molecule rows (static normals only)");
     const size_t n = (size_t)n_frames * h->plan.n_mol_total;
     h->manual_normals.resize(4 * n);
     for (size_t i = 0; i < n; i++) {
@@ -2293,6 +2377,7 @@ int gorder_hip_set_manual_leaflet_table(gorder_hip_handle *h, const uint8_t *fla
 int gorder_hip_set_manual_normal_table(gorder_hip_handle *h, const float *normals, uint32_t step, uint64_t first_row, uint64_t n_rows) {
     if (!h || (n_rows && !normals)) return GORDER_ERR_INVALID_ARGUMENT;
     if (h->n_shells) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_normal_table: the handle has radial shells (static normals only)");
+    if (h->mol.n_groups) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_normal_table: the handle has molecule rows (static normals only)");
     const uint32_t n_mol = h->plan.n_mol_total;
     if (n_rows) {
         if (step == 0) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_normal_table: step 0");
@@ -2604,6 +2689,7 @@ int gorder_hip_set_radial_shells(gorder_hip_handle *h, const float *radii, uint3
     const Plan &p = h->plan;
     if (n_radii) {
         const gorder_tables_t &t = h->tables;
+        if (h->mol.n_groups) return refuse("the handle has molecule rows");
         if (n_radii > GORDER_RADIAL_MAX_SHELLS) return refuse("more than GORDER_RADIAL_MAX_SHELLS radii");
         if (t.geometry.kind != GORDER_GEOM_CYLINDER && t.geometry.kind != GORDER_GEOM_SPHERE)
             return refuse("the tables select no cylinder or sphere");
@@ -2683,6 +2769,87 @@ int gorder_hip_radial_shells(gorder_hip_handle *h, int64_t *sums, uint64_t *coun
             if (counts) { counts[o] = ctot; counts[o + n] = lf ? cup : 0; counts[o + 2 * (size_t)n] = lf ? ctot - cup : 0; }
         }
     }
+    return GORDER_OK;
+}
+
+// ---- per-molecule rows (molecule_rows.h, kernels_molrows.h) -------------------------------------------------------------
+int gorder_hip_set_molecule_rows(gorder_hip_handle *h, const uint32_t *group_begin, const uint32_t *slots, uint32_t n_groups) {
+    if (!h || (n_groups && (!group_begin || !slots))) return GORDER_ERR_INVALID_ARGUMENT;
+    const char *who = "gorder_hip_set_molecule_rows: ";
+    auto refuse = [&](const char *why) { return fail(h, GORDER_ERR_INVALID_ARGUMENT, std::string(who) + why); };
+    if (h->collect_locked) return refuse("only before the first submit or prime, or right after gorder_hip_reset");
+    const Plan &p = h->plan;
+    gorder::MolRows mol;
+    if (n_groups) {
+        if (!p.ua_tiles.empty()) return refuse("united-atom molecule types");
+        if (h->extra.maps) return refuse("ordermaps are on");
+        if (h->extra.tw) return refuse("timewise is on");
+        if (h->n_shells) return refuse("the handle has radial shells");
+        if (h->extra.geom_kind) return refuse("a geometry selection");
+        if (h->dyn) return refuse("dynamic membrane normals");
+        if (h->d_ntable) return refuse("a manual normal table is set");
+        if (h->manual_frames) return refuse("normals were supplied by gorder_hip_set_normals");
+        if (!p.direct.empty()) return refuse("a bond spans more than the LDS window");
+        if (!p.n_acc || p.tiles.empty() || !p.n_mol_total) return refuse("no bond samples");
+        std::vector<uint32_t> group_of_slot;
+        if (const char *why = gorder::molecule_groups_check(group_begin, slots, n_groups, p.n_acc, group_of_slot)) return refuse(why);
+        if ((uint64_t)n_groups * p.n_mol_total > 0xffffffffull) return refuse("groups x molecules exceed 2^32 words a frame");
+        gorder::build_molecule_rows(p.tiles, p.items, p.tile_slots, group_of_slot, n_groups, p.n_mol_total, mol);
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // (copies of a run before the reset may still be writing the chunks)
+    (void)hipFree(h->d_mol_items); (void)hipFree(h->d_mol_runs); (void)hipFree(h->d_mol_run_begin);
+    h->d_mol_items = nullptr; h->d_mol_runs = nullptr; h->d_mol_run_begin = nullptr;
+    h->mol = gorder::MolRows();
+    h->mol_store.release();
+    h->mol_failed = false;
+    h->mol_batch_log.clear();
+    if (!n_groups) return GORDER_OK;
+    int st;
+    if ((st = upload(h, &h->d_mol_items, mol.items)) != GORDER_OK) return st;
+    if ((st = upload(h, &h->d_mol_runs, mol.runs)) != GORDER_OK) return st;
+    if ((st = upload(h, &h->d_mol_run_begin, mol.run_begin)) != GORDER_OK) return st;
+    h->mol_store.configure((size_t)n_groups * p.n_mol_total * sizeof(uint64_t), gorder::CollectAlloc{collect_host_alloc, collect_host_free});
+    h->mol = std::move(mol);
+    return GORDER_OK;
+}
+
+int gorder_hip_molecule_rows_count(gorder_hip_handle *h, uint64_t *n_rows) {
+    if (!h || !n_rows) return GORDER_ERR_INVALID_ARGUMENT;
+    *n_rows = h->mol.n_groups ? h->mol_store.n_rows() : 0;
+    return GORDER_OK;
+}
+
+int gorder_hip_molecule_rows_stats(gorder_hip_handle *h, uint64_t *n_runs, uint32_t *max_runs_per_tile, uint32_t *max_tiles_per_word) {
+    if (!h) return GORDER_ERR_INVALID_ARGUMENT;
+    if (!h->mol.n_groups) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_molecule_rows_stats: molecule rows are off");
+    if (n_runs) *n_runs = h->mol.n_runs;
+    if (max_runs_per_tile) *max_runs_per_tile = h->mol.max_runs_per_tile;
+    if (max_tiles_per_word) *max_tiles_per_word = h->mol.max_tiles_per_word;
+    return GORDER_OK;
+}
+
+int gorder_hip_molecule_rows(gorder_hip_handle *h, int32_t *sums, uint32_t *counts, uint64_t *frames, uint64_t capacity_rows) {
+    if (!h) return GORDER_ERR_INVALID_ARGUMENT;
+    if (!h->mol.n_groups) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_molecule_rows: molecule rows are off");
+    const int st = gorder_hip_synchronize(h);           // (a device error of the run also drops the failed batch's rows)
+    if (st != GORDER_OK) return st;
+    const gorder::CollectStore &store = h->mol_store;
+    if ((sums || counts || frames) && capacity_rows < store.n_rows())
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_molecule_rows: capacity_rows is too small");
+    if (frames) std::copy(store.frames().begin(), store.frames().end(), frames);
+    const size_t wpf = (size_t)h->mol.n_groups * h->plan.n_mol_total;
+    if (sums || counts)
+        store.for_each_row([&](uint64_t r, const void *row) {
+            const uint64_t *w = static_cast<const uint64_t *>(row);
+            for (size_t q = 0; q < wpf; q++) {
+                int64_t s;
+                uint64_t c;
+                gorder::molecule_word_unpack(w[q], s, c);
+                if (sums) sums[r * wpf + q] = (int32_t)s;
+                if (counts) counts[r * wpf + q] = (uint32_t)c;
+            }
+        });
     return GORDER_OK;
 }
 
@@ -2826,6 +2993,9 @@ int gorder_hip_reset(gorder_hip_handle *h) {
     // switch stays and may be set anew
     h->collect_flags.clear();
     h->collect_normals.clear();
+    h->mol_store.clear();                  // (the groups stay)
+    h->mol_failed = false;
+    h->mol_batch_log.clear();
     h->collect_locked = false;
     h->have_assignment = false;
     h->cl_have_carry = false;

@@ -7,8 +7,12 @@
 //   any other extras                                                                      -> Extras
 //   radial shells (gorder_hip_set_radial_shells: a cylinder or sphere selection, no other extra) -> Shells
 //   united-atom tiles                                                                     -> k_ua_extras<mode> (+ _fast)
+//   per-molecule rows (gorder_hip_set_molecule_rows: bond tiles, no other extra, either cosine)  -> TiledMol
 // A batch speculates (one read for global leaflets and order parameters) only where Tiled or the unstaged TiledTw runs:
-// those are the kernels with a MOM variant, and k_spec_check / k_spec_fixup read what that variant wrote.
+// those are the kernels with a MOM variant, and k_spec_check / k_spec_fixup read what that variant wrote.  TiledMol has
+// none, and no gather variant either: GORDER_HIP_KERNEL=gather does not apply to a handle with rows (the rows need the lanes'
+// ticks in LDS).  With per-molecule rows global leaflets take the two-kernel path (k_leaflets_global, then the order kernel), no
+// one-read speculation.
 #ifndef GORDER_ORDER_ROUTE_H
 #define GORDER_ORDER_ROUTE_H
 #include <stddef.h>
@@ -32,8 +36,10 @@ struct OrderRouteIn {
     bool npf5 = false, tw_gather = false, maps_gather = false;
     // radial shells are set on the handle (they come with a geometry selection and exclude every other extra)
     bool shells = false;
+    // per-molecule rows are set on the handle (they exclude every extra, united atoms and direct items)
+    bool mol_rows = false;
 };
-enum class BondFamily { None, Tiled, Gather, TiledTw, TiledMaps, Extras, Shells };
+enum class BondFamily { None, Tiled, Gather, TiledTw, TiledMaps, Extras, Shells, TiledMol };
 
 struct OrderRoute {
     BondFamily family = BondFamily::None;   // what runs over the bond tiles
@@ -57,12 +63,14 @@ inline OrderRoute choose_order_route(const OrderRouteIn &in) {
     r.maps_only = staged && !in.tw && rows_or_maps_only;
     r.npf = (3u * in.max_window + 6u) / 4u <= 4u * 64u && !in.npf5 ? 4 : 5;      // enough float4 for the widest window (64 threads stage a frame)
     if (!in.bond_tiles) r.family = BondFamily::None;
+    else if (in.mol_rows) r.family = BondFamily::TiledMol;
     else if (!r.extras) r.family = in.use_gather ? BondFamily::Gather : BondFamily::Tiled;
     else if (in.shells) r.family = BondFamily::Shells;
     else if (r.maps_only && tiled_out && !in.maps_gather) r.family = BondFamily::TiledMaps;
     else if (in.tw && (!in.maps || staged) && rows_or_maps_only && tiled_out && in.item_run && !in.tw_gather) r.family = BondFamily::TiledTw;
     else r.family = BondFamily::Extras;
-    static const char *const labels[] = {nullptr, "k_bonds_tiled", "k_bonds_gather", "k_bonds_tiled_tw", "k_bonds_tiled_maps", "k_bonds_extras", "k_bonds_shells"};
+    static const char *const labels[] = {nullptr, "k_bonds_tiled", "k_bonds_gather", "k_bonds_tiled_tw", "k_bonds_tiled_maps", "k_bonds_extras", "k_bonds_shells",
+                                         "k_bonds_tiled_mol"};
     r.label = labels[(int)r.family];
     r.tw_maps = r.family == BondFamily::TiledTw && staged;
     r.items_by_slot = r.family == BondFamily::TiledTw || r.family == BondFamily::TiledMaps || (r.family == BondFamily::Extras && staged);
@@ -122,6 +130,9 @@ inline FrameChunks map_chunks(uint32_t n_frames, uint32_t n_acc, uint32_t forced
     const uint32_t fpc = ceil_div(ceil_div(n_frames, n_chunks), 16u) * 16u;
     return {fpc, ceil_div(n_frames, fpc)};
 }
+
+// (k_bonds_tiled_mol: the chunks of extras_chunks(..., staged = false, whole_stages = true) per staging sub-range,
+// molecule_rows.h: molecule_rows_subrange)
 
 // frames of one ordermap sub-range: short enough for the packed map words (k_fold_maps: fold_limit samples per word, at
 // most max_mol a frame) and, staged, for 1 GiB of staging (words_per_frame 64-bit words a frame); everything without maps

@@ -568,6 +568,36 @@ def radial_profile(shells, radii, groups, analysis: str, min_samples: int = 1) -
     return out
 
 
+# ---- per-molecule order rows (HipEngine.molecule_rows): this project's own output, the reference has none ----------
+def molecule_groups(labels, analysis: str):
+    """One group per molecule type — all its bonds — for HipEngine.set_molecule_rows: (groups: lists of accumulator slots,
+    names: the molecule types' names).  (`analysis` as elsewhere: "aa" or "cg"; united-atom labels have no molecule rows.)"""
+    if labels and hasattr(labels[0], "carbons"):
+        raise ValueError("molecule rows cover all-atom and coarse-grained analyses only")
+    if analysis not in ("aa", "cg"):
+        raise ValueError(f"analysis {analysis!r}")
+    groups = [list(range(ml.slot0, ml.slot0 + len(ml.bonds))) for ml in labels if len(ml.bonds)]
+    names = [ml.name for ml in labels if len(ml.bonds)]
+    return groups, names
+
+
+def molecule_order(sums, counts, analysis: str, min_samples: int = 1) -> np.ndarray:
+    """Order parameter of every (frame, group, molecule): float32 of the shape of `sums` / `counts` as
+    HipEngine.molecule_rows() gives them, each entry by calc_order's truncating division (_mean_ticks), negated for "aa"
+    like every all-atom output; NaN below min_samples (a molecule whose type has no slot in the group: always)."""
+    s, n = np.asarray(sums, dtype=np.int64), np.asarray(counts, dtype=np.int64)
+    if s.shape != n.shape:
+        raise ValueError("sums and counts differ in shape")
+    ok = n >= max(1, min_samples)
+    q = np.zeros(s.shape, dtype=np.int64)
+    q[ok] = (np.abs(s[ok]) // n[ok]) * np.sign(s[ok])          # Rust i64 `/` truncates toward zero
+    out = np.full(s.shape, np.nan, dtype=np.float32)
+    out[ok] = (q[ok].astype(np.float64) / 1e6).astype(np.float32)
+    if analysis == "aa":
+        out[ok] = -out[ok]
+    return out
+
+
 # ---- ordermaps: which maps the reference writes, and their values (presentation layer arithmetic) ----------
 @dataclass
 class OrdermapGroup:

@@ -345,6 +345,22 @@ def radial_profile_text(values, counts, radii, names, header: Optional[str] = No
     return "\n".join(out) + "\n"
 
 
+def molecule_order_text(values, frames, names, header: Optional[str] = None) -> str:
+    """Per-molecule order parameters as text (this project's own layout: the reference has no such file), from the values
+    [rows, n_groups, n_molecules] of structure.molecule_order, the frames of HipEngine.molecule_rows and one name per group:
+    one line per frame — the frame's global index, then group by group every molecule's value with four decimals, NaN as
+    `NaN` (a molecule that is not of the group's type, or below min_samples) — under `#` lines that name the columns."""
+    if len(values) != len(frames) or any(len(v) != len(names) for v in values):
+        raise ValueError("values [rows, n_groups, n_molecules], one frame index per row, one name per group")
+    n_mol = len(values[0][0]) if len(values) and len(names) else 0
+    out = [header or "# order parameters of single molecules, frame by frame", "# column 1: frame index"]
+    for g, name in enumerate(names):
+        out.append(f"# columns {2 + g * n_mol}-{1 + (g + 1) * n_mol}: {name}, molecules 0-{n_mol - 1}")
+    for row, f in zip(values, frames):
+        out.append(" ".join([str(int(f))] + [_fixed(float(x)) for grp in row for x in grp]))
+    return "\n".join(out) + "\n"
+
+
 _PLANE_LABELS = {0: ("x", "y"), 1: ("x", "z"), 2: ("z", "y")}     # Plane::get_labels (input/ordermap.rs:54-60)
 _LEAFLET_NAMES = ("full", "upper", "lower")
 

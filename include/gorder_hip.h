@@ -547,6 +547,55 @@ int gorder_hip_set_radial_shells(gorder_hip_handle *h, const float *radii, uint3
 int gorder_hip_radial_shells(gorder_hip_handle *h, int64_t *sums, uint64_t *counts, uint32_t *n_shells);
 int gorder_hip_radial_thresholds(const float *radii, uint32_t n, float *thr);
 
+/* ---- per-molecule order rows: every molecule's own tick sum and sample count, frame by frame ------------------------------
+ * Everything above is summed over the molecules of a type.  With molecule rows the handle also keeps, for every analysed frame,
+ * every group g of accumulator slots and every molecule m, the sum of the ticks (the x 10^6 fixed point of the order sums) of
+ * m's samples whose slot belongs to g, and their number — what Lo/Ld domain detection, annular shells around a protein or a
+ * lipid's flip-flop history start from.  The reference has no counterpart.  The rows do not depend on leaflets (a molecule is
+ * on one side in a frame: GORDER_COLLECT_LEAFLETS says which); a molecule whose type has no slot in g has count 0; a group may
+ * span molecule types; "whole lipid" is the host adding the chain groups — integers add.
+ * The order pass then runs as k_bonds_tiled_mol (its name in gorder_hip_kernel_time_names / _group): the tiled kernel with a
+ * second output, one 64-bit atomic per (tile, group, molecule) and frame into a device staging block of the batch
+ * [frames][n_groups][n_molecules_total] packed words, copied behind the kernel into pinned host memory the handle owns (the
+ * chunks of the collected history: 8 MiB or one batch, never moved, reused after gorder_hip_reset) — a submit stays
+ * asynchronous.  gorder_hip_finish returns exactly what it returns without the rows.  A handle that never calls
+ * gorder_hip_set_molecule_rows queues exactly what it queued before.
+ * Memory: 8 bytes per group, molecule and frame of pinned host memory — 256 lipids x 2 groups = 4 KB a frame; 83 333 lipids of
+ *   a 1M-bead system x 1 group = 667 KB a frame.  On the device only the staging block of one batch, bounded at 1 GiB: a batch
+ *   beyond the bound is walked in frame sub-ranges.  The bound is the environment variable GORDER_HIP_MOL_ROWS_STAGING (bytes),
+ *   read once at gorder_hip_create.  No pinned memory: GORDER_ERR_DEVICE.
+ * gorder_hip_set_molecule_rows: groups in CSR form over accumulator slots as gorder_hip_error_estimate takes them, disjoint;
+ *   n_groups = 0 switches the rows off.  Accepted before the first submit / prime or right after gorder_hip_reset (the rule of
+ *   gorder_hip_set_collect).  GORDER_ERR_INVALID_ARGUMENT, with the reason in gorder_hip_last_error_message, for united-atom
+ *   molecule types; ordermaps; timewise; a geometry selection; dynamic membrane normals; a manual normal table or normals
+ *   supplied by gorder_hip_set_normals; radial shells; a bond that spans more than the LDS window; an empty group; a slot
+ *   >= n_acc; a slot in two groups; group_begin not ascending; a group of more than 2047 slots (the int32 sum:
+ *   2047 x 10^6 < 2^31).  A handle with rows in turn refuses gorder_hip_set_normals, gorder_hip_set_manual_normal_table and
+ *   gorder_hip_set_radial_shells.  Everything else combines: both cosine modes, periodic boundaries or none, a static normal
+ *   on an axis or general, every leaflet method, flip, any frequency, GORDER_COLLECT_LEAFLETS, any cut into batches,
+ *   gorder_hip_submit_host / _device and gorder_hip_run_trajectory (device decoding included).  Global leaflets are assigned
+ *   by their own kernel on this route (no one-read speculation).
+ * gorder_hip_molecule_rows_count: rows kept so far; does not wait.
+ * gorder_hip_molecule_rows: waits for the handle's stream like gorder_hip_finish (a device error of the run is returned);
+ *   sums [n_rows][n_groups][n_molecules_total] int32, counts likewise uint32 (molecule-type-major ids, as the leaflet flags),
+ *   frames [n_rows] the global frame indices.  Any pointer may be NULL; capacity_rows < rows: GORDER_ERR_INVALID_ARGUMENT.
+ *   Shards concatenate their rows by frames[] on the host, as collected rows; gorder_hip_allreduce does NOT carry them.
+ * A batch that ends in an error appends no rows: a submit that fails on the host takes back what it had appended, and once a
+ *   device error of the run has surfaced (gorder_hip_synchronize, gorder_hip_finish, gorder_hip_molecule_rows, ...) the rows
+ *   of the batch that raised it and of every later batch are gone: the rows end where the run ended.  (Where more than 4096
+ *   batches were queued without a synchronisation and the failed one is older than that, the rows are cut at the oldest batch
+ *   still known: good rows are lost, none of a failed batch is kept.)  GORDER_HIP_KERNEL=gather does not apply to a handle with
+ *   rows.
+ * gorder_hip_reset clears the rows and keeps the groups.
+ * gorder_hip_molecule_rows_stats: facts of the lane order built at set time — n_runs: (tile, group, molecule) runs = global
+ *   atomics per frame; max_runs_per_tile; max_tiles_per_word: how many tiles add into one (group, molecule) word.
+ * Not covered: united atoms; rows together with ordermaps, timewise, geometry selections, dynamic or manual normals or radial
+ *   shells; per-molecule error estimates and time averages on the device. */
+int gorder_hip_set_molecule_rows(gorder_hip_handle *h, const uint32_t *group_begin, const uint32_t *slots, uint32_t n_groups);
+int gorder_hip_molecule_rows_count(gorder_hip_handle *h, uint64_t *n_rows);
+int gorder_hip_molecule_rows(gorder_hip_handle *h, int32_t *sums, uint32_t *counts, uint64_t *frames, uint64_t capacity_rows);
+int gorder_hip_molecule_rows_stats(gorder_hip_handle *h, uint64_t *n_runs, uint32_t *max_runs_per_tile, uint32_t *max_tiles_per_word);
+
 /* Signed distances (nm) behind those flags, [n_molecules_total] (leaflets.rs:725, 796).  GORDER_LEAFLETS_SPHERICAL: each
  * molecule's head-centre distance (nm, non-negative) in the last assignment frame. */
 int gorder_hip_leaflet_distances(gorder_hip_handle *h, float *distances);
