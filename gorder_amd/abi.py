@@ -328,6 +328,7 @@ _EXPORTS = [
     "gorder_hip_convergence", "gorder_hip_ordermaps",
     "gorder_hip_set_radial_shells", "gorder_hip_radial_shells", "gorder_hip_radial_thresholds",
     "gorder_hip_set_molecule_rows", "gorder_hip_molecule_rows_count", "gorder_hip_molecule_rows", "gorder_hip_molecule_rows_stats",
+    "gorder_hip_set_order_histogram", "gorder_hip_order_histogram",
 ]
 
 _lib = None
@@ -435,11 +436,14 @@ def load_library() -> C.CDLL:
     lib.gorder_hip_molecule_rows_count.argtypes = [vp, C.POINTER(u64)]
     lib.gorder_hip_molecule_rows.argtypes = [vp, vp, vp, vp, u64]
     lib.gorder_hip_molecule_rows_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u32), C.POINTER(u32)]
+    lib.gorder_hip_set_order_histogram.argtypes = [vp, vp, u32]
+    lib.gorder_hip_order_histogram.argtypes = [vp, vp, C.POINTER(u32)]
     _lib = lib
     return lib
 
 
 RADIAL_MAX_SHELLS = 32       # GORDER_RADIAL_MAX_SHELLS
+HIST_MAX_BINS = 256          # GORDER_HIST_MAX_BINS
 
 
 def radial_thresholds(radii) -> np.ndarray:
@@ -888,6 +892,27 @@ class HipEngine:
         self._check(self.lib.gorder_hip_set_molecule_rows(self._h, begin.ctypes.data_as(C.c_void_p), slots.ctypes.data_as(C.c_void_p),
                                                           len(groups)))
         self._n_mol_groups = len(groups)
+
+    def set_order_histogram(self, edges):
+        """Ascending integer tick edges (structure.order_edges, structure.tilt_edges): from now on the handle also counts the
+        samples per bin edges[k] <= tick < edges[k + 1], accumulator slot and leaflet (gorder_hip_set_order_histogram).  Before
+        the first submit or right after reset(); an empty list switches the histogram off."""
+        e = np.asarray([] if edges is None else edges).reshape(-1)
+        if e.size and (not np.issubdtype(e.dtype, np.integer) or e.min() < -2**31 or e.max() >= 2**31):
+            raise ValueError("the edges are int32 ticks")
+        e = np.ascontiguousarray(e, dtype=np.int32)
+        self._check(self.lib.gorder_hip_set_order_histogram(self._h, e.ctypes.data_as(C.c_void_p) if e.size else None, e.size))
+
+    def order_histogram(self) -> np.ndarray:
+        """Sample counts uint64 [n_bins, 3, n_acc] (total, upper, lower) of the frames analysed so far: raw integers, the
+        arrays of several shards add up (gorder_hip_order_histogram).  Waits like finish(); [0, 3, n_acc] with the
+        histogram off."""
+        n = C.c_uint32()
+        self._check(self.lib.gorder_hip_order_histogram(self._h, None, C.byref(n)))
+        counts = np.zeros((n.value, 3, self.n_acc), dtype=np.uint64)
+        if n.value:
+            self._check(self.lib.gorder_hip_order_histogram(self._h, counts.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return counts
 
     def molecule_rows_count(self) -> int:
         """Per-molecule rows kept so far (one per analysed frame); does not wait."""

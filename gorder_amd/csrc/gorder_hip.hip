@@ -42,6 +42,7 @@
 #include "ordermap_final.h"
 #include "order_route.h"
 #include "molecule_rows.h"
+#include "order_hist.h"
 
 #pragma clang fp contract(off)
 
@@ -56,6 +57,7 @@ using gorder::Tile;
 #include "kernels_extras.h"
 #include "kernels_molrows.h"
 #include "kernels_radial.h"
+#include "kernels_hist.h"
 #include "kernels_leaflets.h"
 #include "kernels_cluster.h"
 #include "kernels_cluster_cutoff.h"
@@ -291,6 +293,15 @@ struct gorder_hip_handle {
     size_t shell_lds_bytes = 0;                 // the LDS table of the widest tile
     bool shell_direct = false;                  // per-sample global atomics: the table does not fit, or ...
     bool shell_force_direct = false;            // ... GORDER_HIP_RADIAL_DIRECT, read once at gorder_hip_create
+    // order distributions (gorder_hip_set_order_histogram; kernels_hist.h): the counts [n_bins][2][n_acc] (total, upper), their
+    // replicas [hist_rep][n_bins][2][n_acc] (k_bonds_dist adds into them, k_fold_replicas folds them), the edges on the device
+    uint32_t hist_edges = 0, hist_rep = 1;      // hist_edges: n_edges, 0 = off
+    int32_t *d_hist_edges = nullptr;
+    unsigned long long *d_hist_acc = nullptr, *d_hist_rep = nullptr;
+    size_t hist_table_words = 0;                // the LDS table of the widest tile, in u32 words
+    bool hist_direct = false;                   // per-sample global atomics: the table does not fit, or ...
+    bool hist_force_direct = false;             // ... GORDER_HIP_DIST_DIRECT, read once at gorder_hip_create
+    uint32_t hist_samples_per_word = gorder::kDistSamplesPerWord;       // dist_chunks; GORDER_HIP_DIST_SAMPLES_PER_WORD, read once likewise
     // per-molecule rows (gorder_hip_set_molecule_rows; molecule_rows.h, kernels_molrows.h): the lane order and the run tables,
     // the staging block of one frame sub-range [frames][n_groups][n_mol_total] packed words, and the rows in pinned chunks
     gorder::MolRows mol;                        // mol.n_groups != 0: the rows are on
@@ -679,6 +690,8 @@ int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &
                 if (!nt) continue;
                 const FrameChunks c = pass == 0 && route.family == BondFamily::Shells
                                           ? gorder::shells_chunks(nf, nt, h->wg_target, h->wg_capacity, kShellChunkMax)
+                                      : pass == 0 && route.family == BondFamily::Dist
+                                          ? gorder::dist_chunks(nf, nt, h->wg_target, h->wg_capacity, h->hist_direct ? 0u : (uint32_t)h->hist_table_words, h->hist_samples_per_word, kDistChunkMax)
                                           : gorder::extras_chunks(nf, nt, h->wg_target, h->wg_capacity, staged, pass == 0 && route.family == BondFamily::TiledTw);
                 FrameArgs b = a;
                 b.frame0 = lo; b.n_frames = hi; b.frames_per_chunk = c.frames_per_chunk;
@@ -697,6 +710,15 @@ int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &
                         const size_t lds = h->shell_direct ? (size_t)kBlock * 24u : h->shell_lds_bytes;
                         with_bool(ac, [&](auto AC) { with_bool(h->shell_direct, [&](auto DIRECT) {
                             hipLaunchKernelGGL((k_bonds_shells<AC(), DIRECT()>), g, blk, lds, h->stream, b, e, sa, b.xyz, b.box9, b.aflags, b.arow,
+                                               h->d_tiles, items, h->d_tile_slots, nt);
+                        }); });
+                    } else if (route.family == BondFamily::Dist) {
+                        DistArgs da{};
+                        da.n_edges = h->hist_edges; da.edges = h->d_hist_edges; da.rep = h->d_hist_rep; da.n_rep = h->hist_rep;
+                        // the edges, then the table of the widest tile or the ordinary sums' reduction, whichever is larger
+                        const size_t lds = kDistEdgeBytes + std::max<size_t>(kDistReduceBytes, h->hist_direct ? 0u : h->hist_table_words * sizeof(uint32_t));
+                        with_bool(ac, [&](auto AC) { with_bool(h->hist_direct, [&](auto DIRECT) {
+                            hipLaunchKernelGGL((k_bonds_dist<AC(), DIRECT()>), g, blk, lds, h->stream, b, e, da, b.xyz, b.box9, b.aflags, b.arow,
                                                h->d_tiles, items, h->d_tile_slots, nt);
                         }); });
                     } else if (route.family == BondFamily::Extras)
@@ -1263,6 +1285,8 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
     }
     if (const char *e = getenv("GORDER_HIP_KERNEL")) h->use_gather = strcmp(e, "gather") == 0;
     h->shell_force_direct = env_flag("GORDER_HIP_RADIAL_DIRECT");
+    h->hist_force_direct = env_flag("GORDER_HIP_DIST_DIRECT");
+    if (const char *ev = getenv("GORDER_HIP_DIST_SAMPLES_PER_WORD")) h->hist_samples_per_word = (uint32_t)std::min(std::max(0, atoi(ev)), 1 << 16);
     if (const char *e = getenv("GORDER_HIP_MOL_ROWS_STAGING")) {      // bytes of the per-molecule rows' device staging (tests set it small)
         const long long v = atoll(e);
         if (v > 0) h->mol_stage_bytes = (size_t)v;
@@ -1522,6 +1546,7 @@ void gorder_hip_destroy(gorder_hip_handle *h) {
     if (!h->acc_external) (void)hipFree(h->d_acc);
     (void)hipFree(h->d_rep);
     (void)hipFree(h->d_shell_acc); (void)hipFree(h->d_shell_rep);
+    (void)hipFree(h->d_hist_acc); (void)hipFree(h->d_hist_rep); (void)hipFree(h->d_hist_edges);
     (void)hipFree(h->d_mol_items); (void)hipFree(h->d_mol_runs); (void)hipFree(h->d_mol_run_begin); (void)hipFree(h->d_mol_stage);
     h->mol_store.release();
     (void)hipFree(h->d_heads); (void)hipFree(h->d_membrane); (void)hipFree(h->d_methyl_begin);
@@ -1935,6 +1960,7 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
     ri.bond_tiles = !p.tiles.empty(); ri.ua_tiles = !p.ua_tiles.empty(); ri.direct_items = !p.direct.empty(); ri.ua_fast_flag = (h->tables.flags & GORDER_FLAG_UA_FAST_NORMALISE) != 0;
     ri.global_leaflets = lf.method == GORDER_LEAFLETS_GLOBAL; ri.spec_enabled = h->spec_enabled; ri.have_assignment = h->have_assignment;
     ri.shells = h->n_shells != 0;
+    ri.dist = h->hist_edges != 0;
     ri.mol_rows = h->mol.n_groups != 0 && !h->mol_failed;
     ri.npf5 = env_flag("GORDER_HIP_NPF5"); ri.tw_gather = env_flag("GORDER_HIP_TW_GATHER"); ri.maps_gather = env_flag("GORDER_HIP_MAPS_GATHER");
     std::vector<uint32_t> spec_aframes;
@@ -2326,6 +2352,7 @@ int gorder_hip_set_normals(gorder_hip_handle *h, const float *normals, uint32_t 
     if (h->d_ntable) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_normals: a manual normal table is set");
     if (h->n_shells) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_normals: the handle has radial shells (static normals only)");
     if (h->mol.n_groups) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_normals: the handle has molecule rows (static normals only)");
+    if (h->hist_edges) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_normals: the handle has an order histogram (static normals only)");
     const size_t n = (size_t)n_frames * h->plan.n_mol_total;
     h->manual_normals.resize(4 * n);
     for (size_t i = 0; i < n; i++) {
@@ -2378,6 +2405,7 @@ int gorder_hip_set_manual_normal_table(gorder_hip_handle *h, const float *normal
     if (!h || (n_rows && !normals)) return GORDER_ERR_INVALID_ARGUMENT;
     if (h->n_shells) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_normal_table: the handle has radial shells (static normals only)");
     if (h->mol.n_groups) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_normal_table: the handle has molecule rows (static normals only)");
+    if (h->hist_edges) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_normal_table: the handle has an order histogram (static normals only)");
     const uint32_t n_mol = h->plan.n_mol_total;
     if (n_rows) {
         if (step == 0) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_normal_table: step 0");
@@ -2690,6 +2718,7 @@ int gorder_hip_set_radial_shells(gorder_hip_handle *h, const float *radii, uint3
     if (n_radii) {
         const gorder_tables_t &t = h->tables;
         if (h->mol.n_groups) return refuse("the handle has molecule rows");
+        if (h->hist_edges) return refuse("the handle has an order histogram");
         if (n_radii > GORDER_RADIAL_MAX_SHELLS) return refuse("more than GORDER_RADIAL_MAX_SHELLS radii");
         if (t.geometry.kind != GORDER_GEOM_CYLINDER && t.geometry.kind != GORDER_GEOM_SPHERE)
             return refuse("the tables select no cylinder or sphere");
@@ -2772,6 +2801,81 @@ int gorder_hip_radial_shells(gorder_hip_handle *h, int64_t *sums, uint64_t *coun
     return GORDER_OK;
 }
 
+// ---- order distributions (order_hist.h, kernels_hist.h) ------------------------------------------------------------------
+int gorder_hip_set_order_histogram(gorder_hip_handle *h, const int32_t *edges, uint32_t n_edges) {
+    if (!h || (n_edges && !edges)) return GORDER_ERR_INVALID_ARGUMENT;
+    const char *who = "gorder_hip_set_order_histogram: ";
+    auto refuse = [&](const char *why) { return fail(h, GORDER_ERR_INVALID_ARGUMENT, std::string(who) + why); };
+    if (h->collect_locked) return refuse("only before the first submit or prime, or right after gorder_hip_reset");
+    const Plan &p = h->plan;
+    if (n_edges) {
+        if (!p.ua_tiles.empty()) return refuse("united-atom molecule types");
+        if (h->extra.maps) return refuse("ordermaps are on");
+        if (h->extra.tw) return refuse("timewise is on");
+        if (h->dyn) return refuse("dynamic membrane normals");
+        if (h->d_ntable) return refuse("a manual normal table is set");
+        if (h->manual_frames) return refuse("normals were supplied by gorder_hip_set_normals");
+        if (h->n_shells) return refuse("the handle has radial shells");
+        if (h->mol.n_groups) return refuse("the handle has molecule rows");
+        if (!p.direct.empty()) return refuse("a bond spans more than the LDS window");
+        if (!p.n_acc || p.tiles.empty()) return refuse("no bond samples");
+        if (const char *why = gorder::hist_edges_check(edges, n_edges)) return refuse(why);
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // (a reset still queued may be zeroing the old blocks)
+    (void)hipFree(h->d_hist_acc); (void)hipFree(h->d_hist_rep); (void)hipFree(h->d_hist_edges);
+    h->d_hist_acc = h->d_hist_rep = nullptr; h->d_hist_edges = nullptr;
+    h->hist_edges = 0;
+    if (!n_edges) return GORDER_OK;
+    // replicas against contention on the global words, as the ordinary sums have them; fewer where the block would pass 64 MiB
+    const uint32_t n_bins = n_edges - 1u;
+    const size_t words = (size_t)n_bins * 2u * p.n_acc;
+    uint32_t n_rep = h->n_rep;
+    while (n_rep > 1 && (size_t)n_rep * words * sizeof(unsigned long long) > ((size_t)64 << 20)) n_rep /= 2;
+    HIP_TRY(h, hipMalloc((void **)&h->d_hist_edges, n_edges * sizeof(int32_t)));
+    HIP_TRY(h, hipMalloc((void **)&h->d_hist_acc, words * sizeof(unsigned long long)));
+    HIP_TRY(h, hipMalloc((void **)&h->d_hist_rep, (size_t)n_rep * words * sizeof(unsigned long long)));
+    HIP_TRY(h, hipMemcpy(h->d_hist_edges, edges, n_edges * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemset(h->d_hist_acc, 0, words * sizeof(unsigned long long)));
+    HIP_TRY(h, hipMemset(h->d_hist_rep, 0, (size_t)n_rep * words * sizeof(unsigned long long)));
+    uint32_t max_slots = 1;
+    for (const Tile &tile : p.tiles) max_slots = std::max(max_slots, tile.n_slots);
+    const uint32_t planes = h->tables.leaflets.method != GORDER_LEAFLETS_NONE ? 2u : 1u;
+    h->hist_table_words = (size_t)planes * n_bins * max_slots;
+    h->hist_direct = h->hist_force_direct || kDistEdgeBytes + h->hist_table_words * sizeof(uint32_t) > 64u * 1024u;
+    h->hist_rep = n_rep;
+    h->hist_edges = n_edges;
+    return GORDER_OK;
+}
+
+int gorder_hip_order_histogram(gorder_hip_handle *h, uint64_t *counts, uint32_t *n_bins) {
+    if (!h) return GORDER_ERR_INVALID_ARGUMENT;
+    const uint32_t nb = h->hist_edges ? h->hist_edges - 1u : 0u;
+    if (n_bins) *n_bins = nb;
+    if (!nb) return GORDER_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const uint32_t n = h->plan.n_acc;
+    const size_t words = (size_t)nb * 2u * n;
+    hipLaunchKernelGGL(k_fold_replicas, dim3((uint32_t)((words + 255) / 256)), dim3(256), 0, h->stream, h->d_hist_acc, h->d_hist_rep,
+                       h->hist_rep, (uint32_t)words);
+    HIP_TRY(h, hipGetLastError());
+    const int st = gorder_hip_synchronize(h);
+    if (st != GORDER_OK) return st;
+    if (!counts) return GORDER_OK;
+    std::vector<unsigned long long> raw(words);
+    HIP_TRY(h, hipMemcpy(raw.data(), h->d_hist_acc, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    const bool lf = h->tables.leaflets.method != GORDER_LEAFLETS_NONE;
+    for (uint32_t k = 0; k < nb; k++) {
+        const unsigned long long *r = raw.data() + (size_t)k * 2u * n;
+        for (uint32_t s = 0; s < n; s++) {
+            const uint64_t ctot = r[s], cup = r[n + s];
+            const size_t o = (size_t)k * 3u * n + s;
+            counts[o] = ctot; counts[o + n] = lf ? cup : 0; counts[o + 2 * (size_t)n] = lf ? ctot - cup : 0;
+        }
+    }
+    return GORDER_OK;
+}
+
 // ---- per-molecule rows (molecule_rows.h, kernels_molrows.h) -------------------------------------------------------------
 int gorder_hip_set_molecule_rows(gorder_hip_handle *h, const uint32_t *group_begin, const uint32_t *slots, uint32_t n_groups) {
     if (!h || (n_groups && (!group_begin || !slots))) return GORDER_ERR_INVALID_ARGUMENT;
@@ -2785,6 +2889,7 @@ int gorder_hip_set_molecule_rows(gorder_hip_handle *h, const uint32_t *group_beg
         if (h->extra.maps) return refuse("ordermaps are on");
         if (h->extra.tw) return refuse("timewise is on");
         if (h->n_shells) return refuse("the handle has radial shells");
+        if (h->hist_edges) return refuse("the handle has an order histogram");
         if (h->extra.geom_kind) return refuse("a geometry selection");
         if (h->dyn) return refuse("dynamic membrane normals");
         if (h->d_ntable) return refuse("a manual normal table is set");
@@ -2972,6 +3077,11 @@ int gorder_hip_reset(gorder_hip_handle *h) {
         const size_t words = (size_t)h->n_shells * 4u * p.n_acc;
         HIP_TRY(h, hipMemsetAsync(h->d_shell_acc, 0, words * sizeof(unsigned long long), h->stream));
         HIP_TRY(h, hipMemsetAsync(h->d_shell_rep, 0, (size_t)h->shell_rep * words * sizeof(unsigned long long), h->stream));
+    }
+    if (h->hist_edges) {    // (the edges stay)
+        const size_t words = (size_t)(h->hist_edges - 1u) * 2u * p.n_acc;
+        HIP_TRY(h, hipMemsetAsync(h->d_hist_acc, 0, words * sizeof(unsigned long long), h->stream));
+        HIP_TRY(h, hipMemsetAsync(h->d_hist_rep, 0, (size_t)h->hist_rep * words * sizeof(unsigned long long), h->stream));
     }
     if (h->extra.maps) {
         const size_t nmap = 3 * (size_t)p.n_acc * h->map_nx * h->map_ny;

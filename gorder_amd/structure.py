@@ -598,6 +598,70 @@ def molecule_order(sums, counts, analysis: str, min_samples: int = 1) -> np.ndar
     return out
 
 
+# ---- order distributions (HipEngine.order_histogram): this project's own output, the reference has none ----------
+TICK_MIN, TICK_MAX = -500_000, 1_000_000      # gm_tick of S = -0.5 and S = 1
+
+
+def order_edges(n_bins: int) -> np.ndarray:
+    """int32 [n_bins + 1] tick edges for HipEngine.set_order_histogram, uniform in S from -0.5 (tick -500 000); the last edge
+    is 1 000 001, so that S = 1 is in the last bin."""
+    if not 1 <= n_bins <= 256:
+        raise ValueError("1 to 256 bins")
+    edges = TICK_MIN + (np.arange(n_bins + 1, dtype=np.int64) * (TICK_MAX - TICK_MIN)) // n_bins
+    edges[-1] = TICK_MAX + 1
+    return edges.astype(np.int32)
+
+
+def tilt_edges(n_bins: int):
+    """Tick edges of a tilt-angle histogram, theta uniform on [0, 90] degrees between the bond vector and the normal ->
+    (edges int32 [n_bins + 1], angles float64 [n_bins + 1] in degrees).  An edge is round(1e6 (1.5 cos^2 theta - 0.5)) in
+    float64; the edges ascend in ticks, so the angles descend from 90 to 0 and bin k holds angles[k + 1] < theta <=
+    angles[k] up to the rounding of the tick; the last edge is 1 000 001, so that theta = 0 is in the last bin.  Raises where
+    two edges coincide (the bins near 0 and 90 degrees are narrow in S)."""
+    if not 1 <= n_bins <= 256:
+        raise ValueError("1 to 256 bins")
+    angles = (90.0 * np.arange(n_bins, -1, -1, dtype=np.float64)) / n_bins
+    c = np.cos(np.deg2rad(angles))
+    edges = np.rint(1e6 * (1.5 * c * c - 0.5)).astype(np.int64)
+    edges[0], edges[-1] = TICK_MIN, TICK_MAX + 1
+    if (np.diff(edges) <= 0).any():
+        raise ValueError(f"{n_bins} tilt bins: two edges coincide in ticks")
+    return edges.astype(np.int32), angles
+
+
+def histogram_groups(hist, groups) -> np.ndarray:
+    """Samples uint64 [n_groups, 3, n_bins] of every group (a list of accumulator slots, as error_groups gives them),
+    leaflet and bin from the counts [n_bins, 3, n_acc] of HipEngine.order_histogram()."""
+    h = np.asarray(hist, dtype=np.uint64)
+    if h.ndim != 3 or h.shape[1] != 3:
+        raise ValueError("hist [n_bins, 3, n_acc]")
+    out = np.zeros((len(groups), 3, h.shape[0]), dtype=np.uint64)
+    for g, slots in enumerate(groups):
+        out[g] = h[:, :, [int(q) for q in slots]].sum(axis=2, dtype=np.uint64).T
+    return out
+
+
+def order_density(hist, edges, analysis: str):
+    """Probability density of the order parameter from counts whose last axis is the bins of `edges` (histogram_groups) ->
+    (density float64 of the counts' shape, s_low, s_high float64 [n_bins]): each count divided by the samples in all bins
+    and by the bin's width in S, so that sum(density * (s_high - s_low)) is 1 (NaN where no sample is in any bin).  For
+    "aa" and "ua" the axis is -S as in every atomistic output of calc_order's users: the bins come reversed, bin
+    (-edge[k + 1], -edge[k]] first for the largest k, and s_low ascends either way."""
+    if analysis not in ("aa", "ua", "cg"):
+        raise ValueError(f"analysis {analysis!r}")
+    e = np.asarray(edges, dtype=np.int64)
+    n = np.asarray(hist, dtype=np.float64)
+    if e.ndim != 1 or e.size < 2 or n.shape[-1] != e.size - 1:
+        raise ValueError("the counts' last axis is the bins of the edges")
+    lo, hi = e[:-1] / 1e6, e[1:] / 1e6
+    total = n.sum(axis=-1, keepdims=True)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        density = n / total / (hi - lo)
+    if analysis in ("aa", "ua"):
+        density, lo, hi = density[..., ::-1], -hi[::-1], -lo[::-1]
+    return density, lo, hi
+
+
 # ---- ordermaps: which maps the reference writes, and their values (presentation layer arithmetic) ----------
 @dataclass
 class OrdermapGroup:

@@ -361,6 +361,38 @@ def molecule_order_text(values, frames, names, header: Optional[str] = None) -> 
     return "\n".join(out) + "\n"
 
 
+def order_histogram_text(counts, edges, names, angles=None, header: Optional[str] = None) -> str:
+    """An order distribution as text (this project's own layout: the reference has no such file), from the counts
+    [n_groups, 3, n_bins] of structure.histogram_groups, the tick edges given to HipEngine.set_order_histogram and one name
+    per group: one row per bin — `tick_low tick_high`, the bin edges[k] <= 1e6 S < edges[k + 1] of the raw S =
+    1.5 cos^2 - 0.5 as integers, with `angles` (structure.tilt_edges) the bin's two tilt angles in degrees with four
+    decimals behind them — then per group its full, upper and lower sample count, under `#` lines that name the columns."""
+    n_bins = len(edges) - 1
+    if len(counts) != len(names) or any(len(w) != n_bins for c in counts for w in c):
+        raise ValueError("counts [n_groups, 3, n_bins], one name per group, n_bins + 1 edges")
+    if angles is not None and len(angles) != len(edges):
+        raise ValueError("one angle per edge")
+    out = [header or "# distribution of order parameters: samples per bin",
+           "# bin k holds the samples with tick_low <= 1e6 * S < tick_high, S = 1.5 cos^2(theta) - 0.5 of the bond vector",
+           "# column 1: tick_low", "# column 2: tick_high"]
+    col = 3
+    if angles is not None:
+        out += ["# column 3: theta at tick_low [deg]", "# column 4: theta at tick_high [deg]"]
+        col = 5
+    for name in names:
+        for which in ("full", "upper", "lower"):
+            out.append(f"# column {col}: {name} {which}")
+            col += 1
+    for k in range(n_bins):
+        cells = [str(int(edges[k])), str(int(edges[k + 1]))]
+        if angles is not None:
+            cells += [_fixed(float(angles[k])), _fixed(float(angles[k + 1]))]
+        for g in range(len(names)):
+            cells += [str(int(counts[g][w][k])) for w in range(3)]
+        out.append(" ".join(cells))
+    return "\n".join(out) + "\n"
+
+
 _PLANE_LABELS = {0: ("x", "y"), 1: ("x", "z"), 2: ("z", "y")}     # Plane::get_labels (input/ordermap.rs:54-60)
 _LEAFLET_NAMES = ("full", "upper", "lower")
 

@@ -596,6 +596,43 @@ int gorder_hip_molecule_rows_count(gorder_hip_handle *h, uint64_t *n_rows);
 int gorder_hip_molecule_rows(gorder_hip_handle *h, int32_t *sums, uint32_t *counts, uint64_t *frames, uint64_t capacity_rows);
 int gorder_hip_molecule_rows_stats(gorder_hip_handle *h, uint64_t *n_runs, uint32_t *max_runs_per_tile, uint32_t *max_tiles_per_word);
 
+/* ---- order distributions: sample counts per bin of S, accumulator slot and leaflet, for the whole run ----------------------
+ * Everything above reports means.  With an order histogram the handle also counts, in the same pass over the frames, how many
+ * samples of every accumulator slot fell into each bin of ascending integer tick edges: bin k holds the samples with
+ * edges[k] <= tick < edges[k + 1], tick being the x 10^6 fixed point of the sample's raw S = 1.5 cos^2 - 0.5 (before the
+ * sign flip an all-atom report applies).  A sample below edges[0] or at or above the last edge is in no bin.  Edges uniform
+ * in S give the distribution of S; edges at 10^6 (1.5 cos^2 theta - 0.5) of uniform angles give the tilt-angle distribution
+ * of the bond vectors.  The reference has no counterpart.  The counts are pure integer work: exact, and independent of the
+ * launch geometry and the cut into batches.
+ * The order pass then runs as k_bonds_dist (its name in gorder_hip_kernel_time_names / _group).  gorder_hip_finish returns
+ * exactly what it returns without a histogram.  A handle that never calls gorder_hip_set_order_histogram queues exactly what
+ * it queued before.  The counts live on the device: 16 bytes per bin and slot, times up to 256 replicas (at most 64 MiB).
+ * The environment variable GORDER_HIP_DIST_DIRECT=1 (read once at gorder_hip_create) takes the kernel's per-sample global
+ * atomics where its LDS table would fit.
+ * gorder_hip_set_order_histogram: n_edges = 0 switches the histogram off; otherwise 2 <= n_edges <= GORDER_HIST_MAX_BINS + 1
+ *   strictly ascending edges.  Accepted before the first submit / prime or right after gorder_hip_reset (the rule of
+ *   gorder_hip_set_collect).  GORDER_ERR_INVALID_ARGUMENT, with the reason in gorder_hip_last_error_message, for united-atom
+ *   molecule types; ordermaps; timewise; dynamic membrane normals; a manual normal table or normals supplied by
+ *   gorder_hip_set_normals; radial shells; molecule rows; a bond that spans more than the LDS window; a plan without bond
+ *   samples; bad edges.  A handle with a histogram in turn refuses gorder_hip_set_normals, gorder_hip_set_manual_normal_table,
+ *   gorder_hip_set_radial_shells and gorder_hip_set_molecule_rows.  Everything else combines: both cosine modes, periodic
+ *   boundaries or none, a static normal on an axis or general, every leaflet method, flip, any frequency,
+ *   GORDER_COLLECT_LEAFLETS, any cut into batches, gorder_hip_submit_host / _device and gorder_hip_run_trajectory (device
+ *   decoding included), and a geometry selection of any kind, inverted or not: a sample outside the selection is in no bin,
+ *   as it is in no sum.  Global leaflets are assigned by their own kernel on this route (no one-read speculation), and
+ *   GORDER_HIP_KERNEL=gather does not apply.
+ * gorder_hip_order_histogram: waits for the handle's stream like gorder_hip_finish (a device error of the run is returned);
+ *   counts [n_bins][3][n_acc], the planes total / upper / lower as in gorder_hip_finish (lower = total - upper; without
+ *   leaflets upper and lower are 0); n_bins = n_edges - 1, or 0 with the histogram off (counts is then not written).  Either
+ *   pointer may be NULL.  After a batch that ended in an error the counts have the standing of the ordinary accumulators.
+ *   Shards add their arrays on the host; gorder_hip_allreduce does NOT carry them.
+ * gorder_hip_reset zeroes the counts and keeps the edges.
+ * Not covered: united atoms; a histogram per frame or per molecule; sums per bin; histograms together with ordermaps, timewise
+ *   rows, radial shells, molecule rows, or dynamic or manual normals. */
+#define GORDER_HIST_MAX_BINS 256
+int gorder_hip_set_order_histogram(gorder_hip_handle *h, const int32_t *edges, uint32_t n_edges);
+int gorder_hip_order_histogram(gorder_hip_handle *h, uint64_t *counts, uint32_t *n_bins);
+
 /* Signed distances (nm) behind those flags, [n_molecules_total] (leaflets.rs:725, 796).  GORDER_LEAFLETS_SPHERICAL: each
  * molecule's head-centre distance (nm, non-negative) in the last assignment frame. */
 int gorder_hip_leaflet_distances(gorder_hip_handle *h, float *distances);
