@@ -53,6 +53,7 @@ using gorder::Plan;
 using gorder::Tile;
 
 #include "kernels_common.h"
+#include "kernels_tile.h"
 #include "kernels_bonds.h"
 #include "kernels_extras.h"
 #include "kernels_molrows.h"

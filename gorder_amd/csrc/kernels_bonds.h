@@ -1,5 +1,5 @@
 // kernels_bonds.h — K1 k_bonds_tiled (+ gather / direct variants): BondType::analyze_frame, bond.rs:396-446.
-// Part of the single translation unit gorder_hip.hip (included there, in this order: common, bonds, extras,
+// Part of the single translation unit gorder_hip.hip (included there, in this order: common, tile, bonds, extras,
 // leaflets, normals); device code for gfx950 only.
 #pragma once
 
@@ -50,12 +50,6 @@ __device__ __forceinline__ unsigned long long map_sample_word(const TiledMapOut 
 }
 
 // ---- one bond sample (bond.rs:407-443) -----------------------------------------------------
-constexpr uint32_t kNoNan = 0xffffffffu;   // "this sample has met no undefined position yet"
-struct SampleAcc {
-    long long s_tot = 0, s_up = 0;
-    uint32_t n_tot = 0, n_up = 0;
-};
-
 // returns true when S came out NaN (undefined position or a non-finite coordinate)
 template <bool ACOS_COS>
 __device__ __forceinline__ bool bond_sample(const FrameArgs &a, uint32_t f, float p1x, float p1y, float p1z,
@@ -249,10 +243,7 @@ struct TiledStage {
                 const float sch = gm_calc_sch<ACOS_COS>(vx, vy, vz, a.nx, a.ny, a.nz, a.n2, a.n2sq);
                 tick[k] = gm_tick(sch);
                 if (MAPS) stage_word(k, vx, vy, vz);
-                if (sch != sch && nan_frame == kNoNan) {   // the FIRST undefined position this sample meets (bond.rs:410-416)
-                    if (P[k][0] != P[k][0]) { nan_which = 0; nan_frame = f0 + k; }
-                    else if (P[k][3] != P[k][3]) { nan_which = 1; nan_frame = f0 + k; }
-                }
+                if (sch != sch && nan_frame == kNoNan) note_undefined(P[k][0], P[k][3], f0 + k, nan_which, nan_frame);
             }
         }
         int st = 0, su = 0;
@@ -307,10 +298,8 @@ struct TiledStage {
                 const float p1x = w[3u * it.li], p1y = w[3u * it.li + 1], p1z = w[3u * it.li + 2];
                 const float p2x = w[3u * it.lj], p2y = w[3u * it.lj + 1], p2z = w[3u * it.lj + 2];
                 if (bond_sample<ACOS_COS>(a, f, p1x, p1y, p1z, p2x, p2y, p2z, it.mol, acc, bad, mo, mo->words + k, OUT == 3 ? mo->ticks + k : nullptr) &&
-                    nan_frame == kNoNan) {
-                    if (p1x != p1x) { nan_which = 0; nan_frame = f; }
-                    else if (p2x != p2x) { nan_which = 1; nan_frame = f; }
-                }
+                    nan_frame == kNoNan)
+                    note_undefined(p1x, p2x, f, nan_which, nan_frame);
             }
             return;
         }
@@ -320,10 +309,8 @@ struct TiledStage {
             const float *w = lds + (size_t)(f - f0) * lw + sh;
             const float p1x = w[3u * it.li], p1y = w[3u * it.li + 1], p1z = w[3u * it.li + 2];
             const float p2x = w[3u * it.lj], p2y = w[3u * it.lj + 1], p2z = w[3u * it.lj + 2];
-            if (bond_sample<ACOS_COS>(a, f, p1x, p1y, p1z, p2x, p2y, p2z, it.mol, acc, bad) && nan_frame == kNoNan) {
-                if (p1x != p1x) { nan_which = 0; nan_frame = f; }
-                else if (p2x != p2x) { nan_which = 1; nan_frame = f; }
-            }
+            if (bond_sample<ACOS_COS>(a, f, p1x, p1y, p1z, p2x, p2y, p2z, it.mol, acc, bad) && nan_frame == kNoNan)
+                note_undefined(p1x, p2x, f, nan_which, nan_frame);
         }
     }
 };
@@ -402,17 +389,10 @@ __global__ __launch_bounds__(kBlock, GORDER_TILED_MIN_WAVES) void k_bonds_tiled(
     // that the accumulator / error stores never clobber them (uniform loads become scalar loads)
     FrameArgs a = a_in;
     a.xyz = xyz; a.box9 = box9; a.aflags = aflags; a.arow = arow;
-    const uint32_t tile_id = blockIdx.x % n_tiles;
-    const uint32_t chunk = blockIdx.x / n_tiles;
-    const Tile t = tiles[tile_id];
-    const uint32_t tid = threadIdx.x;
+    const TileCtx tc = tile_prologue(tiles, items, n_tiles, 0u, a.frames_per_chunk, a.n_frames);   // (always from frame 0: FrameArgs::frame0 is not added)
+    // (the names below are references into tc; a lambda cannot capture them in C++17, so the ones further down say tc.t, tc.tid)
+    const auto &[t, it, tile_id, chunk, tid, active, f_begin, f_end] = tc;
     const uint32_t sk = tid / S::TPF, si = tid % S::TPF;   // staging role: frame slot, first float4
-    const bool active = tid < t.n_items;
-    Item it{0, 0, 0, 0, 0};
-    if (active) it = items[t.item0 + tid];
-
-    const uint32_t f_begin = chunk * a.frames_per_chunk;
-    const uint32_t f_end = min(a.n_frames, f_begin + a.frames_per_chunk);
     const uint32_t f_full = f_begin + ((f_end - f_begin) / G) * G;   // end of the whole stages
 
     SampleAcc acc;
@@ -447,40 +427,9 @@ __global__ __launch_bounds__(kBlock, GORDER_TILED_MIN_WAVES) void k_bonds_tiled(
         __syncthreads();
     }
 
-    if (nan_frame != kNoNan)
-        raise_error(a.err, GORDER_ERR_UNDEFINED_POSITION, nan_frame, kStageTypes, tile_slots[t.slot0 + it.lslot], 1, it.mol, nan_which);
-    if (bad) raise_box_range(a.err, f_begin);
-
-    // ---- epilogue: fold the block's samples per accumulator slot in LDS, then one global atomic
-    // per (slot, field).  Integer sums: the result does not depend on the order (order.rs:44-60).
-    unsigned long long *l_s = reinterpret_cast<unsigned long long *>(lds);   // [2][256]
-    uint32_t *l_n = reinterpret_cast<uint32_t *>(l_s + 2 * kBlock);          // [2][256]
-    l_s[tid] = 0; l_s[kBlock + tid] = 0; l_n[tid] = 0; l_n[kBlock + tid] = 0;
-    __syncthreads();
-    if (active && acc.n_tot) {
-        atomicAdd(&l_s[it.lslot], (unsigned long long)acc.s_tot);
-        atomicAdd(&l_n[it.lslot], acc.n_tot);
-        if (acc.n_up) {
-            atomicAdd(&l_s[kBlock + it.lslot], (unsigned long long)acc.s_up);
-            atomicAdd(&l_n[kBlock + it.lslot], acc.n_up);
-        }
-    }
-    __syncthreads();
-#ifdef GORDER_DEBUG_NOEPILOGUE   // timing experiment only
-    if (a.n_frames == 0xffffffffu)
-#endif
-    if (tid < t.n_slots && l_n[tid]) {
-        // spread the blocks over n_rep replicas of the accumulator block: same-address atomics of
-        // thousands of blocks would otherwise serialise in L2
-        unsigned long long *acc = a.rep + (size_t)(blockIdx.x % a.n_rep) * 4u * a.n_acc;
-        const uint32_t slot = tile_slots[t.slot0 + tid];
-        atomicAdd(&acc[slot], l_s[tid]);
-        atomicAdd(&acc[2u * a.n_acc + slot], (unsigned long long)l_n[tid]);
-        if (l_n[kBlock + tid]) {
-            atomicAdd(&acc[a.n_acc + slot], l_s[kBlock + tid]);
-            atomicAdd(&acc[3u * a.n_acc + slot], (unsigned long long)l_n[kBlock + tid]);
-        }
-    }
+    raise_tile_errors(a.err, tc, tile_slots, nan_which, nan_frame, bad);
+    // the head of the staging LDS: the barrier that ends the last stage (whole or partial) above ended its reads
+    fold_tile_sums(a.rep, a.n_rep, a.n_acc, tc, acc, lds, [&] { return tile_slots[tc.t.slot0 + tc.tid]; });
 }
 
 // ---- K1g: same tiles, but every lane gathers its two atoms straight from global memory (through the
@@ -501,15 +450,8 @@ __global__ __launch_bounds__(kBlock) void k_bonds_gather(FrameArgs a_in, const f
     using S = TiledStage<G, 1, ACOS_COS, PBC, LEAF>;
     FrameArgs a = a_in;
     a.xyz = xyz; a.box9 = box9; a.aflags = aflags; a.arow = arow;
-    const uint32_t tile_id = blockIdx.x % n_tiles;
-    const uint32_t chunk = blockIdx.x / n_tiles;
-    const Tile t = tiles[tile_id];
-    const uint32_t tid = threadIdx.x;
-    const bool active = tid < t.n_items;
-    Item it{0, 0, 0, 0, 0};
-    if (active) it = items[t.item0 + tid];
-    const uint32_t f_begin = chunk * a.frames_per_chunk;
-    const uint32_t f_end = min(a.n_frames, f_begin + a.frames_per_chunk);
+    const TileCtx tc = tile_prologue(tiles, items, n_tiles, 0u, a.frames_per_chunk, a.n_frames);   // (always from frame 0, like k_bonds_tiled)
+    const auto &[t, it, tile_id, chunk, tid, active, f_begin, f_end] = tc;
     const uint32_t f_full = f_begin + ((f_end - f_begin) / G) * G;
     const size_t fstride = (size_t)a.n_atoms * 3u;
     const float *pi = xyz + ((size_t)t.atom0 + it.li) * 3u;
@@ -543,42 +485,13 @@ __global__ __launch_bounds__(kBlock) void k_bonds_gather(FrameArgs a_in, const f
         for (uint32_t f = f_full; f < f_end; f++) {
             const float *q1 = pi + (size_t)f * fstride, *q2 = pj + (size_t)f * fstride;
             const float p1x = q1[0], p1y = q1[1], p1z = q1[2], p2x = q2[0], p2y = q2[1], p2z = q2[2];
-            if (bond_sample<ACOS_COS>(a, f, p1x, p1y, p1z, p2x, p2y, p2z, it.mol, acc, bad) && nan_frame == kNoNan) {
-                if (p1x != p1x) { nan_which = 0; nan_frame = f; }
-                else if (p2x != p2x) { nan_which = 1; nan_frame = f; }
-            }
+            if (bond_sample<ACOS_COS>(a, f, p1x, p1y, p1z, p2x, p2y, p2z, it.mol, acc, bad) && nan_frame == kNoNan)
+                note_undefined(p1x, p2x, f, nan_which, nan_frame);
         }
     }
-    if (nan_frame != kNoNan)
-        raise_error(a.err, GORDER_ERR_UNDEFINED_POSITION, nan_frame, kStageTypes, tile_slots[t.slot0 + it.lslot], 1, it.mol, nan_which);
-    if (bad) raise_box_range(a.err, f_begin);
-
-    l_s[tid] = 0; l_s[kBlock + tid] = 0; l_n[tid] = 0; l_n[kBlock + tid] = 0;
-    __syncthreads();
-    if (active && acc.n_tot) {
-        atomicAdd(&l_s[it.lslot], (unsigned long long)acc.s_tot);
-        atomicAdd(&l_n[it.lslot], acc.n_tot);
-        if (acc.n_up) {
-            atomicAdd(&l_s[kBlock + it.lslot], (unsigned long long)acc.s_up);
-            atomicAdd(&l_n[kBlock + it.lslot], acc.n_up);
-        }
-    }
-    __syncthreads();
-#ifdef GORDER_DEBUG_NOEPILOGUE   // timing experiment only
-    if (a.n_frames == 0xffffffffu)
-#endif
-    if (tid < t.n_slots && l_n[tid]) {
-        // spread the blocks over n_rep replicas of the accumulator block: same-address atomics of
-        // thousands of blocks would otherwise serialise in L2
-        unsigned long long *acc = a.rep + (size_t)(blockIdx.x % a.n_rep) * 4u * a.n_acc;
-        const uint32_t slot = tile_slots[t.slot0 + tid];
-        atomicAdd(&acc[slot], l_s[tid]);
-        atomicAdd(&acc[2u * a.n_acc + slot], (unsigned long long)l_n[tid]);
-        if (l_n[kBlock + tid]) {
-            atomicAdd(&acc[a.n_acc + slot], l_s[kBlock + tid]);
-            atomicAdd(&acc[3u * a.n_acc + slot], (unsigned long long)l_n[kBlock + tid]);
-        }
-    }
+    raise_tile_errors(a.err, tc, tile_slots, nan_which, nan_frame, bad);
+    // static arrays of its own, untouched so far: no barrier ahead of the fold
+    fold_tile_sums(a.rep, a.n_rep, a.n_acc, tc, acc, l_s, l_n, [&] { return tile_slots[tc.t.slot0 + tc.tid]; });
 }
 
 // ---- K1b: direct gather (samples whose atoms do not fit one LDS window; also the A/B baseline)

@@ -160,6 +160,13 @@ __device__ __forceinline__ void rec_store(const ExtraArgs &e, uint32_t tile_id, 
     __builtin_nontemporal_store(ull2{v[0], v[1]}, row);               // (written once, read once by k_map_accumulate)
     __builtin_nontemporal_store(ull2{v[2], v[3]}, row + 1);
 }
+// the ordermap's grid for the tiled kernels' staged words, which go to `words` (a thread's kRecFrames of a stage); no tick words
+__device__ __forceinline__ TiledMapOut tiled_map_out(const ExtraArgs &e, unsigned long long *words) {
+    TiledMapOut mo{};
+    mo.plane = e.plane; mo.x0 = e.x0; mo.y0 = e.y0; mo.binx = e.binx; mo.biny = e.biny; mo.nx = e.nx; mo.ny = e.ny;
+    mo.bin_core = e.bin_core; mo.words = words;
+    return mo;
+}
 
 // MAPS_ONLY: staged ordermap samples and nothing else (no geometry selection, timewise rows, per-molecule normals)
 template <bool ACOS_COS, bool MAPS_ONLY>
@@ -185,6 +192,7 @@ __global__ __launch_bounds__(kBlock) void k_bonds_extras(FrameArgs a_in, ExtraAr
     const uint32_t gslot = active ? tile_slots[t.slot0 + it.lslot] : 0;
     const uint32_t f_begin = a.frame0 + chunk * a.frames_per_chunk;
     const uint32_t f_end = min(a.n_frames, f_begin + a.frames_per_chunk);
+    const TileCtx tc{t, it, tile_id, chunk, tid, active, f_begin, f_end};      // (for fold_tile_sums; kernels_tile.h says why not tile_prologue)
     const size_t fstride = (size_t)a.n_atoms * 3u;
     const float *pi = xyz + ((size_t)t.atom0 + it.li) * 3u;
     const float *pj = xyz + ((size_t)t.atom0 + it.lj) * 3u;
@@ -279,27 +287,8 @@ __global__ __launch_bounds__(kBlock) void k_bonds_extras(FrameArgs a_in, ExtraAr
         }
     }
     if (bad) raise_box_range(a.err, f_begin);
-    l_s[tid] = 0; l_s[kBlock + tid] = 0; l_n[tid] = 0; l_n[kBlock + tid] = 0;
-    __syncthreads();
-    if (active && acc.n_tot) {
-        atomicAdd(&l_s[it.lslot], (unsigned long long)acc.s_tot);
-        atomicAdd(&l_n[it.lslot], acc.n_tot);
-        if (acc.n_up) {
-            atomicAdd(&l_s[kBlock + it.lslot], (unsigned long long)acc.s_up);
-            atomicAdd(&l_n[kBlock + it.lslot], acc.n_up);
-        }
-    }
-    __syncthreads();
-    if (tid < t.n_slots && l_n[tid]) {
-        unsigned long long *accp = a.rep + (size_t)(blockIdx.x % a.n_rep) * 4u * a.n_acc;
-        const uint32_t slot = tile_slots[t.slot0 + tid];
-        atomicAdd(&accp[slot], l_s[tid]);
-        atomicAdd(&accp[2u * a.n_acc + slot], (unsigned long long)l_n[tid]);
-        if (l_n[kBlock + tid]) {
-            atomicAdd(&accp[a.n_acc + slot], l_s[kBlock + tid]);
-            atomicAdd(&accp[3u * a.n_acc + slot], (unsigned long long)l_n[kBlock + tid]);
-        }
-    }
+    // static arrays of its own, untouched so far: no barrier ahead of the fold
+    fold_tile_sums(a.rep, a.n_rep, a.n_acc, tc, acc, l_s, l_n, [&] { return tile_slots[tc.t.slot0 + tc.tid]; });
 }
 
 // ---- ordermaps and nothing else, bonds: K1's staging (kernels_bonds.h: a tile's atom window of G = kRecFrames frames
@@ -319,20 +308,12 @@ __global__ __launch_bounds__(kBlock, 4) void k_bonds_tiled_maps(FrameArgs a_in, 
     using S = TiledStage<G, NPF, false, PBC, LEAF, AXIS>;
     FrameArgs a = a_in;
     a.xyz = xyz; a.box9 = box9; a.aflags = aflags; a.arow = arow;
-    const uint32_t tile_id = blockIdx.x % n_tiles, chunk = blockIdx.x / n_tiles;
-    const Tile t = tiles[tile_id];
-    const uint32_t tid = threadIdx.x;
+    const TileCtx tc = tile_prologue(tiles, items, n_tiles, a.frame0, a.frames_per_chunk, a.n_frames);
+    const auto &[t, it, tile_id, chunk, tid, active, f_begin, f_end] = tc;
     const uint32_t sk = tid / S::TPF, si = tid % S::TPF;
-    const bool active = tid < t.n_items;
-    Item it{0, 0, 0, 0, 0};
-    if (active) it = items[t.item0 + tid];
-    const uint32_t f_begin = a.frame0 + chunk * a.frames_per_chunk;
-    const uint32_t f_end = min(a.n_frames, f_begin + a.frames_per_chunk);
     const uint32_t f_full = f_begin + ((f_end - f_begin) / G) * G;
     unsigned long long words[kRecFrames] = {kMapNoSample, kMapNoSample, kMapNoSample, kMapNoSample};       // (padding lanes: none)
-    TiledMapOut mo;
-    mo.plane = e.plane; mo.x0 = e.x0; mo.y0 = e.y0; mo.binx = e.binx; mo.biny = e.biny; mo.nx = e.nx; mo.ny = e.ny;
-    mo.bin_core = e.bin_core; mo.words = words;
+    const TiledMapOut mo = tiled_map_out(e, words);
     SampleAcc acc;
     int bad = 0;
     uint32_t nan_which = 0, nan_frame = kNoNan;
@@ -356,33 +337,11 @@ __global__ __launch_bounds__(kBlock, 4) void k_bonds_tiled_maps(FrameArgs a_in, 
         rec_store(e, tile_id, f_full, tid, words);
         __syncthreads();
     }
-    if (nan_frame != kNoNan)
-        raise_error(a.err, GORDER_ERR_UNDEFINED_POSITION, nan_frame, kStageTypes, tile_slots[t.slot0 + it.lslot], 1, it.mol, nan_which);
-    if (bad) raise_box_range(a.err, f_begin);
+    raise_tile_errors(a.err, tc, tile_slots, nan_which, nan_frame, bad);
+    // the head of the staging LDS: this barrier ends its reads (so does the one that closes every stage: this one is kept
+    // so that the kernel's code stays what it was)
     __syncthreads();
-    unsigned long long *l_s = reinterpret_cast<unsigned long long *>(lds);   // [2][256]
-    uint32_t *l_n = reinterpret_cast<uint32_t *>(l_s + 2 * kBlock);          // [2][256]
-    l_s[tid] = 0; l_s[kBlock + tid] = 0; l_n[tid] = 0; l_n[kBlock + tid] = 0;
-    __syncthreads();
-    if (active && acc.n_tot) {
-        atomicAdd(&l_s[it.lslot], (unsigned long long)acc.s_tot);
-        atomicAdd(&l_n[it.lslot], acc.n_tot);
-        if (acc.n_up) {
-            atomicAdd(&l_s[kBlock + it.lslot], (unsigned long long)acc.s_up);
-            atomicAdd(&l_n[kBlock + it.lslot], acc.n_up);
-        }
-    }
-    __syncthreads();
-    if (tid < t.n_slots && l_n[tid]) {
-        unsigned long long *accp = a.rep + (size_t)(blockIdx.x % a.n_rep) * 4u * a.n_acc;
-        const uint32_t slot = tile_slots[t.slot0 + tid];
-        atomicAdd(&accp[slot], l_s[tid]);
-        atomicAdd(&accp[2u * a.n_acc + slot], (unsigned long long)l_n[tid]);
-        if (l_n[kBlock + tid]) {
-            atomicAdd(&accp[a.n_acc + slot], l_s[kBlock + tid]);
-            atomicAdd(&accp[3u * a.n_acc + slot], (unsigned long long)l_n[kBlock + tid]);
-        }
-    }
+    fold_tile_sums(a.rep, a.n_rep, a.n_acc, tc, acc, lds, [&] { return tile_slots[tc.t.slot0 + tc.tid]; });
 }
 
 // ---- per-frame rows (timewise sums, timewise.rs:130-186), alone or (MAPS) with staged ordermaps, bonds: K1's staging
@@ -415,18 +374,19 @@ __global__ __launch_bounds__(kBlock, 4) void k_bonds_tiled_tw(FrameArgs a_in, Ex
     const uint32_t sk = tid / S::TPF, si = tid % S::TPF;
     const bool active = tid < t.n_items;
     Item it{0, 0, 0, 0, 0};
-    if (active) {
+    if (active) {       // (its own prologue, not tile_prologue: the item and its run come in under ONE test of `active`)
         it = items[t.item0 + tid];
         const uint32_t run = e.item_run[t.item0 + tid];
         if ((run >> 16) == tid) l_slot_run[it.lslot] = run;          // the first lane of a run writes it down
     }
     const uint32_t f_begin = a.frame0 + chunk * a.frames_per_chunk;
     const uint32_t f_end = min(a.n_frames, f_begin + a.frames_per_chunk);
+    const TileCtx tc{t, it, tile_id, chunk, tid, active, f_begin, f_end};      // (for raise_tile_errors and fold_tile_sums)
     unsigned long long words[kRecFrames], mwords[MAPS ? kRecFrames : 1];
     TiledMapOut mo{};
     if (MAPS) {                     // the ordermap words as well (staged like k_bonds_tiled_maps')
-        mo.plane = e.plane; mo.x0 = e.x0; mo.y0 = e.y0; mo.binx = e.binx; mo.biny = e.biny; mo.nx = e.nx; mo.ny = e.ny;
-        mo.bin_core = e.bin_core; mo.words = mwords; mo.ticks = words;
+        mo = tiled_map_out(e, mwords);
+        mo.ticks = words;
     } else {
         mo.nx = 0;                  // ticks only: word = (lower << 32) | tick
         mo.words = words;
@@ -503,32 +463,11 @@ __global__ __launch_bounds__(kBlock, 4) void k_bonds_tiled_tw(FrameArgs a_in, Ex
             }
         }
     }
+    // the head of the staging LDS: its last reads, the last stage's samples, ended at that stage's second barrier (the run
+    // sums behind it read other LDS); this barrier is kept so that the kernel's code stays what it was
     __syncthreads();
-    if (nan_frame != kNoNan)
-        raise_error(a.err, GORDER_ERR_UNDEFINED_POSITION, nan_frame, kStageTypes, tile_slots[t.slot0 + it.lslot], 1, it.mol, nan_which);
-    if (bad) raise_box_range(a.err, f_begin);
-    unsigned long long *l_s = reinterpret_cast<unsigned long long *>(lds);   // [2][256]
-    uint32_t *l_n = reinterpret_cast<uint32_t *>(l_s + 2 * kBlock);          // [2][256]
-    l_s[tid] = 0; l_s[kBlock + tid] = 0; l_n[tid] = 0; l_n[kBlock + tid] = 0;
-    __syncthreads();
-    if (active && acc.n_tot) {
-        atomicAdd(&l_s[it.lslot], (unsigned long long)acc.s_tot);
-        atomicAdd(&l_n[it.lslot], acc.n_tot);
-        if (acc.n_up) {
-            atomicAdd(&l_s[kBlock + it.lslot], (unsigned long long)acc.s_up);
-            atomicAdd(&l_n[kBlock + it.lslot], acc.n_up);
-        }
-    }
-    __syncthreads();
-    if (tid < t.n_slots && l_n[tid]) {
-        unsigned long long *accp = a.rep + (size_t)(blockIdx.x % a.n_rep) * 4u * a.n_acc;
-        atomicAdd(&accp[my_slot], l_s[tid]);
-        atomicAdd(&accp[2u * a.n_acc + my_slot], (unsigned long long)l_n[tid]);
-        if (l_n[kBlock + tid]) {
-            atomicAdd(&accp[a.n_acc + my_slot], l_s[kBlock + tid]);
-            atomicAdd(&accp[3u * a.n_acc + my_slot], (unsigned long long)l_n[kBlock + tid]);
-        }
-    }
+    raise_tile_errors(a.err, tc, tile_slots, nan_which, nan_frame, bad);
+    fold_tile_sums(a.rep, a.n_rep, a.n_acc, tc, acc, lds, [&] { return my_slot; });      // (the slot came in with l_slot_id: no second load)
 }
 
 // ---- united atoms: hydrogen construction, restating uaorder.rs:947-1104 with the operation order of

@@ -32,8 +32,8 @@ struct DistArgs {
 //     are 64 consecutive lanes, so the 32 lanes of a half wave sit on 32 distinct banks whatever their bins.
 //     The epilogue strides the table and adds the non-zero words to the global replicas.
 //   DIRECT: the table does not fit (or GORDER_HIP_DIST_DIRECT): one or two global atomics per sample on the replicas.
-// The ordinary sums stay in registers on both routes and are reduced as in k_bonds_extras: gorder_hip_finish sees what
-// that kernel would have left.
+// The ordinary sums stay in registers on both routes and are reduced by fold_tile_sums (kernels_tile.h): gorder_hip_finish
+// sees what k_bonds_extras would have left.
 template <bool ACOS_COS, bool DIRECT>
 __global__ __launch_bounds__(kBlock) void k_bonds_dist(FrameArgs a_in, ExtraArgs e, DistArgs s, const float *__restrict__ xyz,
                                                         const float *__restrict__ box9,
@@ -56,6 +56,7 @@ __global__ __launch_bounds__(kBlock) void k_bonds_dist(FrameArgs a_in, ExtraArgs
     const uint32_t gslot = active ? tile_slots[t.slot0 + it.lslot] : 0;
     const uint32_t f_begin = a.frame0 + chunk * a.frames_per_chunk;
     const uint32_t f_end = min(a.n_frames, f_begin + a.frames_per_chunk);
+    const TileCtx tc{t, it, tile_id, chunk, tid, active, f_begin, f_end};      // (for fold_tile_sums; kernels_tile.h says why not tile_prologue)
     const size_t fstride = (size_t)a.n_atoms * 3u;
     const float *pi = xyz + ((size_t)t.atom0 + it.li) * 3u;
     const float *pj = xyz + ((size_t)t.atom0 + it.lj) * 3u;
@@ -146,29 +147,9 @@ __global__ __launch_bounds__(kBlock) void k_bonds_dist(FrameArgs a_in, ExtraArgs
         }
         __syncthreads();        // the table's words are read: its place now serves the reduction below
     }
-    unsigned long long *l_s = reinterpret_cast<unsigned long long *>(l_tab);      // [2][256]
-    uint32_t *l_n = reinterpret_cast<uint32_t *>(l_s + 2 * kBlock);               // [2][256]
-    l_s[tid] = 0; l_s[kBlock + tid] = 0; l_n[tid] = 0; l_n[kBlock + tid] = 0;
-    __syncthreads();
-    if (active && acc.n_tot) {
-        atomicAdd(&l_s[it.lslot], (unsigned long long)acc.s_tot);
-        atomicAdd(&l_n[it.lslot], acc.n_tot);
-        if (acc.n_up) {
-            atomicAdd(&l_s[kBlock + it.lslot], (unsigned long long)acc.s_up);
-            atomicAdd(&l_n[kBlock + it.lslot], acc.n_up);
-        }
-    }
-    __syncthreads();
-    if (tid < ns && l_n[tid]) {
-        unsigned long long *accp = a.rep + (size_t)(blockIdx.x % a.n_rep) * 4u * a.n_acc;
-        const uint32_t slot = tile_slots[t.slot0 + tid];
-        atomicAdd(&accp[slot], l_s[tid]);
-        atomicAdd(&accp[2u * a.n_acc + slot], (unsigned long long)l_n[tid]);
-        if (l_n[kBlock + tid]) {
-            atomicAdd(&accp[a.n_acc + slot], l_s[kBlock + tid]);
-            atomicAdd(&accp[3u * a.n_acc + slot], (unsigned long long)l_n[kBlock + tid]);
-        }
-    }
+    // the place of the table (behind the edges, which stay): the barrier just above ended the table's reads; on the direct
+    // route nothing has been there
+    fold_tile_sums(a.rep, a.n_rep, a.n_acc, tc, acc, l_tab, [&] { return tile_slots[tc.t.slot0 + tc.tid]; });
 }
 
 }  // namespace

@@ -43,20 +43,14 @@ __global__ __launch_bounds__(kBlock, 4) void k_bonds_tiled_mol(FrameArgs a_in, M
     using S = TiledStage<G, NPF, ACOS_COS, PBC, LEAF, AXIS>;
     FrameArgs a = a_in;
     a.xyz = xyz; a.box9 = box9; a.aflags = aflags; a.arow = arow;
-    const uint32_t tile_id = blockIdx.x % n_tiles, chunk = blockIdx.x / n_tiles;
-    const Tile t = tiles[tile_id];
-    const uint32_t tid = threadIdx.x;
+    const TileCtx tc = tile_prologue(tiles, items, n_tiles, a.frame0, a.frames_per_chunk, a.n_frames);
+    const auto &[t, it, tile_id, chunk, tid, active, f_begin, f_end] = tc;
     const uint32_t sk = tid / S::TPF, si = tid % S::TPF;
-    const bool active = tid < t.n_items;
-    Item it{0, 0, 0, 0, 0};
-    if (active) it = items[t.item0 + tid];
     const uint32_t run0 = mr.run_begin[tile_id], n_runs = mr.run_begin[tile_id + 1u] - run0;    // (<= n_items <= kBlock)
     if (tid < n_runs) {
         const gorder::MolRun r = mr.runs[run0 + tid];
         l_run[tid] = make_uint2(((uint32_t)r.lane0 << 16) | (uint32_t)r.n, r.word);
     }
-    const uint32_t f_begin = a.frame0 + chunk * a.frames_per_chunk;
-    const uint32_t f_end = min(a.n_frames, f_begin + a.frames_per_chunk);
     unsigned long long words[kRecFrames];
     TiledMapOut mo{};
     mo.nx = 0;                      // ticks only: word = (lower << 32) | tick
@@ -98,33 +92,11 @@ __global__ __launch_bounds__(kBlock, 4) void k_bonds_tiled_mol(FrameArgs a_in, M
             if (s) atomicAdd(&mr.stage[(size_t)(fs + k - a.frame0) * mr.words_per_frame + run.y], s);
         }
     }
+    // the head of the staging LDS: its last reads, the last stage's samples, ended at that stage's second barrier (the run
+    // sums behind it read other LDS); this barrier is kept so that the kernel's code stays what it was
     __syncthreads();
-    if (nan_frame != kNoNan)
-        raise_error(a.err, GORDER_ERR_UNDEFINED_POSITION, nan_frame, kStageTypes, tile_slots[t.slot0 + it.lslot], 1, it.mol, nan_which);
-    if (bad) raise_box_range(a.err, f_begin);
-    unsigned long long *l_s = reinterpret_cast<unsigned long long *>(lds);   // [2][256]
-    uint32_t *l_n = reinterpret_cast<uint32_t *>(l_s + 2 * kBlock);          // [2][256]
-    l_s[tid] = 0; l_s[kBlock + tid] = 0; l_n[tid] = 0; l_n[kBlock + tid] = 0;
-    __syncthreads();
-    if (active && acc.n_tot) {
-        atomicAdd(&l_s[it.lslot], (unsigned long long)acc.s_tot);
-        atomicAdd(&l_n[it.lslot], acc.n_tot);
-        if (acc.n_up) {
-            atomicAdd(&l_s[kBlock + it.lslot], (unsigned long long)acc.s_up);
-            atomicAdd(&l_n[kBlock + it.lslot], acc.n_up);
-        }
-    }
-    __syncthreads();
-    if (tid < t.n_slots && l_n[tid]) {
-        unsigned long long *accp = a.rep + (size_t)(blockIdx.x % a.n_rep) * 4u * a.n_acc;
-        const uint32_t slot = tile_slots[t.slot0 + tid];
-        atomicAdd(&accp[slot], l_s[tid]);
-        atomicAdd(&accp[2u * a.n_acc + slot], (unsigned long long)l_n[tid]);
-        if (l_n[kBlock + tid]) {
-            atomicAdd(&accp[a.n_acc + slot], l_s[kBlock + tid]);
-            atomicAdd(&accp[3u * a.n_acc + slot], (unsigned long long)l_n[kBlock + tid]);
-        }
-    }
+    raise_tile_errors(a.err, tc, tile_slots, nan_which, nan_frame, bad);
+    fold_tile_sums(a.rep, a.n_rep, a.n_acc, tc, acc, lds, [&] { return tile_slots[tc.t.slot0 + tc.tid]; });
 }
 
 }  // namespace

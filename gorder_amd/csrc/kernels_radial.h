@@ -60,7 +60,7 @@ __device__ __forceinline__ bool shell_geom(const ExtraArgs &e, const float *sh, 
 //     The epilogue, a thread per slot of the tile, adds the non-empty entries to the global shell replicas and their sum
 //     over the shells to the handle's ordinary replica block: gorder_hip_finish sees what k_bonds_extras would have left.
 //   DIRECT: the table does not fit (or GORDER_HIP_RADIAL_DIRECT): two to four global atomics per sample on the shell
-//     replicas, the ordinary sums in registers and reduced as in k_bonds_extras (dynamic LDS: [2][256] u64 + [2][256] u32).
+//     replicas, the ordinary sums in registers and reduced by fold_tile_sums (dynamic LDS: kTileFoldBytes).
 template <bool ACOS_COS, bool DIRECT>
 __global__ __launch_bounds__(kBlock) void k_bonds_shells(FrameArgs a_in, ExtraArgs e, ShellArgs s, const float *__restrict__ xyz,
                                                           const float *__restrict__ box9,
@@ -81,6 +81,7 @@ __global__ __launch_bounds__(kBlock) void k_bonds_shells(FrameArgs a_in, ExtraAr
     const uint32_t gslot = active ? tile_slots[t.slot0 + it.lslot] : 0;
     const uint32_t f_begin = a.frame0 + chunk * a.frames_per_chunk;
     const uint32_t f_end = min(a.n_frames, f_begin + a.frames_per_chunk);
+    const TileCtx tc{t, it, tile_id, chunk, tid, active, f_begin, f_end};      // (for fold_tile_sums; kernels_tile.h says why not tile_prologue)
     const size_t fstride = (size_t)a.n_atoms * 3u;
     const float *pi = xyz + ((size_t)t.atom0 + it.li) * 3u;
     const float *pj = xyz + ((size_t)t.atom0 + it.lj) * 3u;
@@ -170,28 +171,8 @@ __global__ __launch_bounds__(kBlock) void k_bonds_shells(FrameArgs a_in, ExtraAr
     if (bad) raise_box_range(a.err, f_begin);
     unsigned long long *accp = a.rep + (size_t)(blockIdx.x % a.n_rep) * 4u * a.n_acc;
     if (DIRECT) {
-        unsigned long long *l_s = l_tab;                                         // [2][256]
-        uint32_t *l_n = reinterpret_cast<uint32_t *>(l_s + 2 * kBlock);         // [2][256]
-        l_s[tid] = 0; l_s[kBlock + tid] = 0; l_n[tid] = 0; l_n[kBlock + tid] = 0;
-        __syncthreads();
-        if (active && acc.n_tot) {
-            atomicAdd(&l_s[it.lslot], (unsigned long long)acc.s_tot);
-            atomicAdd(&l_n[it.lslot], acc.n_tot);
-            if (acc.n_up) {
-                atomicAdd(&l_s[kBlock + it.lslot], (unsigned long long)acc.s_up);
-                atomicAdd(&l_n[kBlock + it.lslot], acc.n_up);
-            }
-        }
-        __syncthreads();
-        if (tid < ns && l_n[tid]) {
-            const uint32_t slot = tile_slots[t.slot0 + tid];
-            atomicAdd(&accp[slot], l_s[tid]);
-            atomicAdd(&accp[2u * a.n_acc + slot], (unsigned long long)l_n[tid]);
-            if (l_n[kBlock + tid]) {
-                atomicAdd(&accp[a.n_acc + slot], l_s[kBlock + tid]);
-                atomicAdd(&accp[3u * a.n_acc + slot], (unsigned long long)l_n[kBlock + tid]);
-            }
-        }
+        // the dynamic LDS, which this route has not touched so far: no barrier ahead of the fold
+        fold_tile_sums(a.rep, a.n_rep, a.n_acc, tc, acc, l_tab, [&] { return tile_slots[tc.t.slot0 + tc.tid]; });
         return;
     }
     if (open_word) atomicAdd(&l_tab[open_at], open_word);

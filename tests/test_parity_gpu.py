@@ -10,7 +10,7 @@ import pytest
 
 from gorder_amd import HipEngine, abi, synthetic
 from gorder_amd.abi import (LEAFLETS_GLOBAL, LEAFLETS_INDIVIDUAL, LEAFLETS_LOCAL, LEAFLETS_MANUAL,
-                            LEAFLETS_NONE, MolType, Tables)
+                            LEAFLETS_NONE, MolType, OrderMap, Tables)
 from oracle import oracle
 from leaflet_check import assert_sums_given_device_flags
 
@@ -360,25 +360,43 @@ def test_errors_mirror_the_reference(built):
     assert e.value.status == abi.ERR_LEAFLETS_NOT_PRIMED
 
 
-@pytest.mark.parametrize("mode", ["tiled", "direct", "timewise", "gather", "ua"])
+@pytest.mark.parametrize("mode", ["tiled", "direct", "timewise", "gather", "ua", "maps", "extras"])
 def test_first_error_in_reference_order(built, monkeypatch, mode):
     """Several undefined atoms in one batch: the status payload is the one the reference's single-threaded walk meets
     first — lowest frame, then bond type, then molecule, first atom before second (bond.rs:406-417; united atoms:
-    uaorder.rs:400-437) — whichever wave of which kernel gets there first (64-bit error key + atomicMin)."""
+    uaorder.rs:400-437) — whichever wave of which kernel gets there first (64-bit error key + atomicMin).
+    `maps` (an ordermap over the box: k_bonds_tiled_maps) and `extras` (per-frame rows out of k_bonds_extras) say on a
+    clean run of the same tables that it is their kernel that ran."""
     torch_cuda()
     if mode == "direct":
         monkeypatch.setenv("GORDER_HIP_FORCE_DIRECT", "1")
     if mode == "gather":
         monkeypatch.setenv("GORDER_HIP_KERNEL", "gather")
+    if mode == "extras":
+        monkeypatch.setenv("GORDER_HIP_TW_GATHER", "1")
     if mode == "ua":
         system = synthetic.ua_membrane(24)
         apl = 52
     else:
-        system = synthetic.cg_membrane(40, n_types=2, timewise=(mode == "timewise"))
+        system = synthetic.cg_membrane(40, n_types=2, timewise=(mode in ("timewise", "extras")))
         apl = 12
+    if mode == "maps":
+        bx = system.box
+        system.tables.ordermap = OrderMap(enabled=True, plane=0, span_x=(0.0, float(bx[0])), span_y=(0.0, float(bx[1])), bin=(0.5, 0.7))
     n = 9
     xyz = system.frames(n, seed=3)
     box = system.box9(n)
+    kernel = {"maps": "k_bonds_tiled_maps", "extras": "k_bonds_extras"}.get(mode)
+    if kernel:
+        for batches in (1, 3):
+            eng = HipEngine(system.tables)
+            eng.kernel_time()                   # (switches the event pairs on: the kernels of the batch are then named)
+            edges = np.linspace(0, n, batches + 1).astype(int)
+            for a, b in zip(edges[:-1], edges[1:]):
+                eng.submit_host(xyz[a:b], box[a:b], np.arange(a, b))
+                eng.synchronize()
+                assert kernel in eng.kernel_names().split(" + "), (mode, batches, eng.kernel_names())
+            assert eng.finish().n_frames == n
     rng = np.random.default_rng(5)
     for trial in range(6):
         x = xyz.copy()
