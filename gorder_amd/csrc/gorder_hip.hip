@@ -1409,6 +1409,8 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
             h->sph_spill = lf.n_membrane > resident ? lf.n_membrane - resident : 0u;
             if (h->sph_spill) {
                 h->sph_slab = (uint32_t)std::min<size_t>(std::max<size_t>(((size_t)64 << 20) / (h->sph_spill * sizeof(float)), 1), 4096);
+                if (const char *ev = getenv("GORDER_HIP_SPHERICAL_SLAB"))      // (tests: frames per launch; only lowers the cap)
+                    h->sph_slab = std::min(h->sph_slab, (uint32_t)std::max(1, atoi(ev)));
                 HIP_TRY(h, hipMalloc((void **)&h->d_sph_spill, (size_t)h->sph_slab * h->sph_spill * sizeof(float)));
             }
             HIP_TRY(h, hipMalloc((void **)&h->d_sph_stats, 12 * sizeof(float)));

@@ -790,7 +790,10 @@ int gorder_hip_speculation_stats(gorder_hip_handle *h, uint64_t out[4]);
  * that undulates by more than the water around it allows — sends the next 16 submits down the atom-by-atom pass alone.
  * The sides are the reference's either way.  (Device memory: a handle with local leaflets holds up to 4 GiB of cell-list
  * scratch — 2 048 assignment frames a launch group, fewer for membranes that need more than 2 MB a frame;
- * GORDER_HIP_LOCAL_SLAB=n caps the frames.)  out[0] = submits that ran the bound kernel, out[1] = submits that paused it,
+ * GORDER_HIP_LOCAL_SLAB=n caps the frames, at least 4; it sizes the launch groups of dynamic normals as well.
+ * GORDER_HIP_SPHERICAL_SLAB=n, at least 1, does the same for spherical clustering of a group beyond 16 384 atoms, whose
+ * scratch rows hold at most 64 MiB and 4 096 assignment frames a launch: it only lowers that cap.  Both are read at
+ * gorder_hip_create and change no result.)  out[0] = submits that ran the bound kernel, out[1] = submits that paused it,
  * out[2] / out[3] = frames left open / frames seen in the last report read back.  (GORDER_HIP_LOCAL_NO_DECIDE=1: never.)
  * Waits for the handle's stream. */
 int gorder_hip_local_decide_stats(gorder_hip_handle *h, uint64_t out[4]);

@@ -39,11 +39,12 @@ def trr_frame(step, t, box, x=None, v=None, double=False, x_size=None):
 
 def write_trr(path, xyz, boxes, times, double=False):
     """frames [F, N, 3] (+ boxes [F, 3, 3] or None, times [F]) as one TRR file -> the file offset of every positions block"""
-    data, where = b"", []
+    data, where, at = [], [], 0
     for k in range(len(xyz)):
         box = None if boxes is None else boxes[k]
-        where.append(len(data) + HEADER_BYTES[double] + (0 if box is None else 9 * (8 if double else 4)))
-        data += trr_frame(k, float(times[k]), box, x=xyz[k], double=double)
+        where.append(at + HEADER_BYTES[double] + (0 if box is None else 9 * (8 if double else 4)))
+        data.append(trr_frame(k, float(times[k]), box, x=xyz[k], double=double))      # (a list: 65 540 frames in a second)
+        at += len(data[-1])
     with open(path, "wb") as f:
-        f.write(data)
+        f.write(b"".join(data))
     return where
