@@ -37,6 +37,7 @@
 #include "gm_math.h"
 #include "plan.h"
 #include "collect_store.h"
+#include "device_mem.h"
 #include "replay_rows.h"
 #include "timewise_blocks.h"
 #include "ordermap_final.h"
@@ -74,6 +75,60 @@ using gorder::Tile;
 // host side
 // ============================================================================================
 
+// ---- who owns what (device_mem.h): device and pinned blocks, events and streams that free themselves ----------------------
+struct DeviceMem {
+    static void *alloc(size_t bytes) { void *p = nullptr; return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr; }
+    static void release(void *p) { (void)hipFree(p); }
+};
+struct PinnedMem {
+    static void *alloc(size_t bytes) { void *p = nullptr; return hipHostMalloc(&p, bytes) == hipSuccess ? p : nullptr; }
+    static void release(void *p) { (void)hipHostFree(p); }
+};
+template <typename T> using DBuf = gorder::Buf<T, DeviceMem>;
+template <typename T> using HBuf = gorder::Buf<T, PinnedMem>;
+using u64 = unsigned long long;
+
+struct Event {
+    hipEvent_t ev = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() { if (ev) (void)hipEventDestroy(ev); }
+    hipError_t create(unsigned flags = hipEventDisableTiming) { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, flags); }
+    operator hipEvent_t() const { return ev; }
+};
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    hipError_t create() { return s ? hipSuccess : hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+    operator hipStream_t() const { return s; }
+};
+
+// an accumulator block of `words` u64 and the replicas the kernels add into (k_fold_replicas folds them): radial shells, order
+// distributions
+struct RepAcc {
+    DBuf<u64> acc, rep;      // [words], [n_rep][words]
+    uint32_t n_rep = 1;
+    size_t words = 0;
+    bool alloc(size_t n_words, uint32_t n_rep_wanted) {
+        words = n_words;
+        n_rep = gorder::replica_count(n_rep_wanted, n_words);
+        return acc.alloc(words) && rep.alloc((size_t)n_rep * words);
+    }
+    void reset() { acc.reset(); rep.reset(); words = 0; }
+    hipError_t zero_async(hipStream_t stream) {
+        const hipError_t e = hipMemsetAsync(acc, 0, words * sizeof(u64), stream);
+        return e != hipSuccess ? e : hipMemsetAsync(rep, 0, (size_t)n_rep * words * sizeof(u64), stream);
+    }
+    hipError_t fold(hipStream_t stream) {
+        hipLaunchKernelGGL(k_fold_replicas, dim3((uint32_t)((words + 255) / 256)), dim3(256), 0, stream, acc.get(), rep.get(), n_rep, (uint32_t)words);
+        return hipGetLastError();
+    }
+};
+
 struct gorder_hip_handle {
     // staging buffers of gorder_hip_run_trajectory, kept between calls (trajectory_driver.h: TrajCache)
     void *traj_cache = nullptr;
@@ -81,105 +136,99 @@ struct gorder_hip_handle {
     Plan plan;
     gorder_tables_t tables{};           // scalar copy (pointers inside are NOT kept)
     int device = 0;
-    hipStream_t own_stream = nullptr;
+    Stream own_stream;                  // (declared before every buffer: destroyed after them)
     hipStream_t stream = nullptr;
     // device tables
-    Tile *d_tiles = nullptr;
-    Item *d_items = nullptr;
-    uint32_t *d_tile_slots = nullptr;
-    DirectItem *d_direct = nullptr;
-    Tile *d_ua_tiles = nullptr;
-    gorder::UaItem *d_ua_items = nullptr;
-    uint32_t *d_ua_tile_slots = nullptr;
+    DBuf<Tile> d_tiles;
+    DBuf<Item> d_items;
+    DBuf<uint32_t> d_tile_slots;
+    DBuf<DirectItem> d_direct;
+    DBuf<Tile> d_ua_tiles;
+    DBuf<gorder::UaItem> d_ua_items;
+    DBuf<uint32_t> d_ua_tile_slots;
     // ordermaps [3][n_acc][nx*ny] and timewise rows [cap][3][n_acc]
     uint32_t map_nx = 0, map_ny = 0;
-    unsigned long long *d_map_sums = nullptr, *d_map_cnts = nullptr;   // [3][n_acc][nx*ny], folded
-    unsigned long long *d_map_packed = nullptr;   // [1 or 2][n_acc][nx*ny], what the kernels add into
-    unsigned long long *d_map_rec = nullptr;      // united-atom staging for k_map_accumulate (see ExtraArgs::map_rec)
-    size_t map_rec_cap = 0;
-    gorder::MapRun *d_ua_runs = nullptr, *d_runs = nullptr;
-    uint32_t *d_ua_run_begin = nullptr, *d_run_begin = nullptr;
-    Item *d_items_by_slot = nullptr;
-    uint32_t *d_ua_item_run = nullptr, *d_item_run = nullptr;
-    uint4 *d_lgrid = nullptr;       // per slab frame: the cell grid of the local-leaflet kernels
-    LocalRowPre *d_lrowpre = nullptr;   // per slab frame: prefix sums along the rows of cells (k_local_rowprefix)
-    LocalEdge *d_ledge = nullptr;       // the same cells' 16-byte entries for the bound of k_local_flags_rows
-    float4 *d_lfinfo = nullptr;     // per slab frame: extrema of the membrane's normal coordinate, finite flag
+    DBuf<u64> d_map_sums, d_map_cnts;   // [3][n_acc][nx*ny], folded
+    DBuf<u64> d_map_packed;             // [1 or 2][n_acc][nx*ny], what the kernels add into
+    DBuf<u64> d_map_rec;                // united-atom staging for k_map_accumulate (see ExtraArgs::map_rec)
+    DBuf<gorder::MapRun> d_ua_runs, d_runs;
+    DBuf<uint32_t> d_ua_run_begin, d_run_begin;
+    DBuf<Item> d_items_by_slot;
+    DBuf<uint32_t> d_ua_item_run, d_item_run;
+    DBuf<uint4> d_lgrid;            // per slab frame: the cell grid of the local-leaflet kernels
+    DBuf<LocalRowPre> d_lrowpre;    // per slab frame: prefix sums along the rows of cells (k_local_rowprefix)
+    DBuf<LocalEdge> d_ledge;        // the same cells' 16-byte entries for the bound of k_local_flags_rows
+    DBuf<float4> d_lfinfo;          // per slab frame: extrema of the membrane's normal coordinate, finite flag
     // k_local_decide pays when it decides whole frames; a membrane whose heads it leaves open (one that undulates by more than
     // the water around it allows) is better off without it: every submit that runs it reports {frames left open, frames}
     // to pinned memory, and a submit that finds the majority open sends the next kDecidePause submits down the rows kernel
     // alone.  (Either way the sides are the reference's: the choice is about time only.)
     static constexpr uint32_t kDecidePause = 16;
-    uint32_t *d_lsummary = nullptr, *h_lsummary = nullptr;
-    hipEvent_t lsummary_written = nullptr;
+    DBuf<uint32_t> d_lsummary;
+    HBuf<uint32_t> h_lsummary;
+    Event lsummary_written;
     bool lsummary_pending = false;
     uint32_t decide_pause = 0;
     uint64_t decide_submits = 0, decide_paused_submits = 0;
-    uint32_t *d_lneed = nullptr;    // [local_slab + 1] heads of each slab frame k_local_decide left to k_local_flags_rows; any of the slab
-    uint2 *d_ltodo = nullptr;       // {count}, then the (slab frame, head) pairs left to the general passes
+    DBuf<uint32_t> d_lneed;         // [local_slab + 1] heads of each slab frame k_local_decide left to k_local_flags_rows; any of the slab
+    DBuf<uint2> d_ltodo;            // {count}, then the (slab frame, head) pairs left to the general passes
     size_t map_lds_bytes = 0;
     bool map_staged = false;       // the packed map of one slot fits LDS: stage + accumulate instead of one atomic per sample
     uint64_t map_pending = 0;      // upper bound of the samples one packed word may hold since the last fold
     uint64_t map_fold_limit = kMapFoldLimit;   // GORDER_HIP_MAP_FOLD_LIMIT lowers it (tests)
     uint32_t map_max_mol = 1;      // most molecules of one type = most samples per tile and frame
-    unsigned long long *d_tw_sums = nullptr, *d_tw_cnts = nullptr;
-    uint64_t tw_cap = 0;
+    DBuf<u64> d_tw_sums, d_tw_cnts;
+    uint64_t tw_cap = 0;               // rows (frames) those two hold
     // scratch of the passes over those rows (kernels_timewise.h): block sums then counts [2][n_blocks][3][n_acc], the groups in
     // CSR form, the groups' per-frame rows and their chunk totals [2][..][3][n_groups], carry and end [4][3][n_groups], the columns
-    unsigned long long *d_twx_blocks = nullptr, *d_twx_rows = nullptr, *d_twx_totals = nullptr, *d_twx_edge = nullptr;
-    uint32_t *d_twx_groups = nullptr;
-    float *d_twx_out = nullptr;
-    size_t twx_blocks_cap = 0, twx_rows_cap = 0, twx_totals_cap = 0, twx_edge_cap = 0, twx_groups_cap = 0, twx_out_cap = 0;
+    DBuf<u64> d_twx_blocks, d_twx_rows, d_twx_totals, d_twx_edge;
+    DBuf<uint32_t> d_twx_groups;
+    DBuf<float> d_twx_out;
     // scratch of gorder_hip_ordermaps (kernels_ordermap.h): the groups in CSR form, the finished maps [n_groups][3][nx*ny]
-    uint32_t *d_omx_groups = nullptr;
-    float *d_omx_out = nullptr;
-    size_t omx_groups_cap = 0, omx_out_cap = 0;
+    DBuf<uint32_t> d_omx_groups;
+    DBuf<float> d_omx_out;
     ExtraArgs extra{};
-    uint32_t *d_geom_group = nullptr;
-    float *d_shapes = nullptr;
-    float *d_inv_box = nullptr;      // GORDER_FLAG_UA_FAST_NORMALISE: 1 / box edge per frame of the batch
-    size_t inv_box_cap = 0;
+    DBuf<uint32_t> d_geom_group;
+    DBuf<float> d_shapes;
+    DBuf<float> d_inv_box;             // GORDER_FLAG_UA_FAST_NORMALISE: 1 / box edge per frame of the batch
     // dynamic membrane normals: cloud + per-molecule heads, cell-list scratch (dyn_slab frames), normals of the batch
     uint32_t dyn_slab = 4, local_slab = 4;
     bool local_halo = false;           // local leaflets: rows of cells with a halo + prefix sums (k_local_flags_rows)
     size_t local_rec_stride = 0;       // records per slab frame the local-leaflet record arrays hold
-    XtcCheckpoint *d_xtc_cp = nullptr; // gorder_hip_xtc_decode: where the chunks of the frames start (k_xtc_scan -> k_xtc_chunks)
-    size_t xtc_cp_cap = 0;
+    DBuf<XtcCheckpoint> d_xtc_cp;      // gorder_hip_xtc_decode: where the chunks of the frames start (k_xtc_scan -> k_xtc_chunks)
     bool dyn = false;
-    uint32_t *d_dyn_cloud = nullptr, *d_dyn_heads = nullptr;
-    uint32_t *d_dyn_cell_of = nullptr, *d_dyn_count = nullptr;
-    float *d_dyn_rec = nullptr;
-    float4 *d_dyn_normals = nullptr;
-    DynCov *d_dyn_cov = nullptr;       // per (slab frame, molecule): the sums of k_dyn_cov for k_dyn_eigen
-    size_t dyn_normals_cap = 0;
+    DBuf<uint32_t> d_dyn_cloud, d_dyn_heads;
+    DBuf<uint32_t> d_dyn_cell_of, d_dyn_count;
+    DBuf<float> d_dyn_rec;
+    DBuf<float4> d_dyn_normals;
+    DBuf<DynCov> d_dyn_cov;            // per (slab frame, molecule): the sums of k_dyn_cov for k_dyn_eigen
     std::vector<float> last_normals;   // [n_mol_total][4] of the last submitted frame
     // manual membrane normals (ManualMembraneNormal, normal.rs:266-300): handed over per batch by the host
     std::vector<float> manual_normals; // [frames][n_mol_total][4] (nx, ny, nz, 3) for the NEXT submit
     uint32_t manual_frames = 0;
     bool manual_active = false;        // this batch's samples read d_dyn_normals filled from manual_normals
-    size_t shapes_cap = 0;
-    uint32_t *d_err = nullptr;
-    unsigned long long *d_acc = nullptr;   // [4][n_acc] + total_frames
-    unsigned long long *d_rep = nullptr;   // [n_rep][4][n_acc] (see k_fold_replicas)
+    DBuf<uint32_t> d_err;
+    u64 *d_acc = nullptr;              // [4][n_acc] + total_frames: a view of own_acc, or of the memory gorder_hip_bind_accumulators bound
+    DBuf<u64> own_acc;                 // the block the handle allocated itself (empty once external memory is bound)
+    DBuf<u64> d_rep;                   // [n_rep][4][n_acc] (see k_fold_replicas)
     uint32_t n_rep = 32;
     bool rep_dirty = false;
-    bool acc_external = false;
     size_t acc_words = 0;
     // leaflets
-    uint32_t *d_heads = nullptr, *d_membrane = nullptr, *d_methyl_begin = nullptr, *d_methyl_atoms = nullptr;
-    uint8_t *d_aflags = nullptr;
-    size_t aflags_rows = 0;
-    float *d_adist = nullptr;
+    DBuf<uint32_t> d_heads, d_membrane, d_methyl_begin, d_methyl_atoms;
+    DBuf<uint8_t> d_aflags;
+    size_t aflags_rows = 0;            // rows of n_mol_total flags it holds
+    DBuf<float> d_adist;
     // spherical clustering: distances of the group atoms past the register-resident ones, sph_slab assignment frames a launch;
     // the statistics of the most recent assignment frame (gorder_hip_spherical_stats)
-    float *d_sph_spill = nullptr, *d_sph_stats = nullptr;
+    DBuf<float> d_sph_spill, d_sph_stats;
     uint32_t sph_spill = 0, sph_slab = 1u << 20, sph_threads = 1024;
     // spectral clustering: scratch for cl_slab assignment frames a launch (one allocation, carved in ClArgs), the group slot
     // of every molecule's head, the oriented labels of the previous assignment frame (the carry) and the last frame's statistics
-    void *d_cl_scratch = nullptr;
-    uint32_t *d_cl_head_slot = nullptr;
-    uint8_t *d_cl_carry = nullptr, *d_cl_is0 = nullptr;
-    float *d_cl_stats = nullptr;
+    DBuf<char> d_cl_scratch;
+    DBuf<uint32_t> d_cl_head_slot;
+    DBuf<uint8_t> d_cl_carry, d_cl_is0;
+    DBuf<float> d_cl_stats;
     uint32_t cl_slab = 1, cl_m_max = 0;
     bool cl_stored_w = false;              // GORDER_HIP_CLUSTER_STORED_W: S v reads W stored once a frame instead of recomputing it
     bool cl_have_carry = false;
@@ -187,43 +236,38 @@ struct gorder_hip_handle {
     uint32_t cl_tiles = 0, cl_sort = 0;    // row tiles and counting-sort blocks of a frame (cut-off route)
     std::vector<uint8_t> cl_is0;           // per assignment frame of the call in flight: frame_index == 0
     // Local leaflets scratch (sized for local_slab assignment frames)
-    uint32_t *d_lcell_of = nullptr, *d_lcell_count = nullptr, *d_lcell_fill = nullptr;
-    float *d_ltrig = nullptr;
-    uint32_t *d_arow = nullptr, *d_aframes = nullptr;
+    DBuf<uint32_t> d_lcell_of, d_lcell_count, d_lcell_fill;
+    DBuf<float> d_ltrig;               // LocalRec records, as LocalArgs::trig takes them
+    DBuf<uint32_t> d_arow, d_aframes;
     // what those two hold right now: equal batches (same length, same assignment pattern) skip the upload
     std::vector<uint32_t> up_arow, up_aframes;
-    const uint32_t *up_arow_at = nullptr, *up_aframes_at = nullptr;
-    size_t arow_cap = 0, aframes_cap = 0;
+    bool up_arow_valid = false, up_aframes_valid = false;      // (a new allocation holds nothing yet)
     bool have_assignment = false;
     uint64_t assignment_frame = 0;
     // one read for global leaflets + order parameters (Plan::spec_ok; k_bonds_tiled<..., MOM> + k_spec_*)
     bool spec_enabled = false;         // the plan allows it and GORDER_HIP_NO_SPECULATE is not set
-    uint2 *d_own = nullptr;
-    float4 *d_mom = nullptr;
-    size_t mom_cap = 0;
-    float *d_head_z = nullptr;
-    size_t head_z_cap = 0;
-    uint32_t *d_own_head_begin = nullptr;
-    uint2 *d_own_heads = nullptr;
-    float *d_spec_center = nullptr;
-    uint8_t *d_spec_ok = nullptr;
-    size_t spec_frames_cap = 0;
-    uint32_t *d_spec_counters = nullptr;           // two pairs (batches alternate): [0] mispredicted (frame, molecule) pairs, [1] frames left to the exact kernel
+    DBuf<uint2> d_own;
+    DBuf<float4> d_mom;
+    DBuf<float> d_head_z;
+    DBuf<uint32_t> d_own_head_begin;
+    DBuf<uint2> d_own_heads;
+    DBuf<float> d_spec_center;
+    DBuf<uint8_t> d_spec_ok;
+    DBuf<uint32_t> d_spec_counters;                // two pairs (batches alternate): [0] mispredicted (frame, molecule) pairs, [1] frames left to the exact kernel
     // pinned copies of the last speculative batches' counters, looked at (without waiting) when a later batch is submitted
     static constexpr uint32_t kSpecRing = 8;
-    uint32_t *h_spec_counters = nullptr;           // [kSpecRing][2]
-    hipEvent_t spec_counters_copied[kSpecRing] = {};
+    HBuf<uint32_t> h_spec_counters;                // [kSpecRing][2]
+    Event spec_counters_copied[kSpecRing];
     uint64_t spec_ring_frames[kSpecRing] = {};     // frames of the batch in that slot (0: nothing pending)
-    uint32_t *d_spec_mol_begin = nullptr;
-    SpecSample *d_spec_samples = nullptr;
+    DBuf<uint32_t> d_spec_mol_begin;
+    DBuf<SpecSample> d_spec_samples;
     uint64_t spec_batches = 0, spec_fixed = 0, spec_exact_frames = 0;   // statistics (gorder_hip_speculation_stats)
     // host staging for submit_host: two device buffers, filled on a copy stream while the kernels of the other one run
-    float *d_stage_xyz[2] = {nullptr, nullptr}, *d_stage_box[2] = {nullptr, nullptr};
-    size_t stage_xyz_cap[2] = {0, 0}, stage_box_cap[2] = {0, 0};
-    hipEvent_t stage_copied[2] = {nullptr, nullptr}, stage_computed[2] = {nullptr, nullptr};
+    DBuf<float> d_stage_xyz[2], d_stage_box[2];
+    Event stage_copied[2], stage_computed[2];
     bool stage_used[2] = {false, false};
     int stage_next = 0;
-    hipStream_t copy_stream = nullptr;
+    Stream copy_stream;
     float n2 = 1.0f, n2sq = 1.0f;
     int axis = -1;   // 0/1/2 when the static normal is exactly that unit axis (kernel specialisation)
     int frames_per_stage = kFramesPerStage;   // G = 4 frames staged per pass (8 was measured at 26 % and spilled: removed in round 4)
@@ -243,7 +287,7 @@ struct gorder_hip_handle {
     static constexpr uint32_t kTimingEvents = 1024;
     struct TimingSeg { uint32_t label, ev_a, ev_b; };
     bool timing_on = false;
-    hipEvent_t timing_ev[kTimingEvents] = {};
+    Event timing_ev[kTimingEvents];
     uint32_t timing_next_ev = 0;                  // ring position of the next event to record
     int timing_open_label = -1;                   // the segment being queued (-1: none)
     uint32_t timing_open_ev = 0;
@@ -255,7 +299,7 @@ struct gorder_hip_handle {
     std::string timed_kernels;                    // the labels joined by " + " (gorder_hip_kernel_time_names)
     // host copies behind the payload of gorder_hip_last_error_index
     std::vector<uint32_t> host_heads, host_dyn_heads;
-    uint32_t *d_mol_slot0 = nullptr;
+    DBuf<uint32_t> d_mol_slot0;
     uint64_t err_frame = 0;
     // frame indices of the batches submitted since the last clean synchronisation (ordinal -> SystemTopology::frame of
     // its frames), so that a device error names the frame of the TRAJECTORY; arithmetic progressions are kept as three
@@ -271,34 +315,32 @@ struct gorder_hip_handle {
     bool collect_locked = false;                // something was submitted or primed since create / reset
     gorder::CollectStore collect_flags;         // rows of ceil(n_mol / 64) u64
     gorder::CollectStore collect_normals;       // rows of n_mol x 3 f32
-    unsigned long long *d_collect_words = nullptr;
-    CollectVec3 *d_collect_vec = nullptr;
-    uint8_t *d_touched = nullptr;               // [n_frames][n_mol_total] of the batch (ExtraArgs::touched)
-    size_t collect_words_cap = 0, collect_vec_cap = 0, touched_cap = 0;
+    DBuf<u64> d_collect_words;
+    DBuf<CollectVec3> d_collect_vec;
+    DBuf<uint8_t> d_touched;                    // [n_frames][n_mol_total] of the batch (ExtraArgs::touched)
     // whole-trajectory manual tables (gorder_hip_set_manual_leaflet_table / _normal_table; replay_rows.h): packed on the
     // device, expanded per batch by k_replay_flags / k_replay_normals
-    unsigned long long *d_ltable = nullptr;     // [window rows][ceil(n_mol / 64)] u64, before `flip`
+    DBuf<u64> d_ltable;                         // [window rows][ceil(n_mol / 64)] u64, before `flip`
     gorder::ReplayWindow ltable_win;
     bool replay_have_carry = false;             // row 0 of d_aflags is the table's row replay_carry_index
     uint64_t replay_carry_index = 0;
-    ReplayVec3 *d_ntable = nullptr;             // [window rows][n_mol] x 12 bytes
+    DBuf<ReplayVec3> d_ntable;                  // [window rows][n_mol] x 12 bytes
     gorder::ReplayWindow ntable_win;
     uint32_t ntable_step = 1;
-    uint32_t *d_nrow = nullptr;                 // per frame of the batch: its row of d_ntable
-    size_t nrow_cap = 0;
+    DBuf<uint32_t> d_nrow;                      // per frame of the batch: its row of d_ntable
     // radial shells (gorder_hip_set_radial_shells; kernels_radial.h): the accumulators [n_shells][4][n_acc] laid out like d_acc,
-    // their replicas [shell_rep][n_shells][4][n_acc] (k_bonds_shells adds into them, k_fold_replicas folds them)
-    uint32_t n_shells = 0, shell_rep = 1;
+    // their replicas [shells.n_rep][n_shells][4][n_acc] (k_bonds_shells adds into them)
+    uint32_t n_shells = 0;
     float shell_thr[GORDER_RADIAL_MAX_SHELLS] = {};          // local_radius_threshold of the radii
-    unsigned long long *d_shell_acc = nullptr, *d_shell_rep = nullptr;
+    RepAcc shells;
     size_t shell_lds_bytes = 0;                 // the LDS table of the widest tile
     bool shell_direct = false;                  // per-sample global atomics: the table does not fit, or ...
     bool shell_force_direct = false;            // ... GORDER_HIP_RADIAL_DIRECT, read once at gorder_hip_create
     // order distributions (gorder_hip_set_order_histogram; kernels_hist.h): the counts [n_bins][2][n_acc] (total, upper), their
-    // replicas [hist_rep][n_bins][2][n_acc] (k_bonds_dist adds into them, k_fold_replicas folds them), the edges on the device
-    uint32_t hist_edges = 0, hist_rep = 1;      // hist_edges: n_edges, 0 = off
-    int32_t *d_hist_edges = nullptr;
-    unsigned long long *d_hist_acc = nullptr, *d_hist_rep = nullptr;
+    // replicas [hist.n_rep][n_bins][2][n_acc] (k_bonds_dist adds into them), the edges on the device
+    uint32_t hist_edges = 0;                    // n_edges, 0 = off
+    DBuf<int32_t> d_hist_edges;
+    RepAcc hist;
     size_t hist_table_words = 0;                // the LDS table of the widest tile, in u32 words
     bool hist_direct = false;                   // per-sample global atomics: the table does not fit, or ...
     bool hist_force_direct = false;             // ... GORDER_HIP_DIST_DIRECT, read once at gorder_hip_create
@@ -306,11 +348,10 @@ struct gorder_hip_handle {
     // per-molecule rows (gorder_hip_set_molecule_rows; molecule_rows.h, kernels_molrows.h): the lane order and the run tables,
     // the staging block of one frame sub-range [frames][n_groups][n_mol_total] packed words, and the rows in pinned chunks
     gorder::MolRows mol;                        // mol.n_groups != 0: the rows are on
-    Item *d_mol_items = nullptr;
-    gorder::MolRun *d_mol_runs = nullptr;
-    uint32_t *d_mol_run_begin = nullptr;
-    unsigned long long *d_mol_stage = nullptr;
-    size_t mol_stage_cap = 0;
+    DBuf<Item> d_mol_items;
+    DBuf<gorder::MolRun> d_mol_runs;
+    DBuf<uint32_t> d_mol_run_begin;
+    DBuf<u64> d_mol_stage;
     size_t mol_stage_bytes = (size_t)1 << 30;   // GORDER_HIP_MOL_ROWS_STAGING, read once at gorder_hip_create
     gorder::CollectStore mol_store;             // rows of n_groups x n_mol_total u64
     const uint64_t *mol_frame_index = nullptr;  // the batch being submitted: its frames' labels
@@ -332,24 +373,49 @@ int fail(gorder_hip_handle *h, int status, const std::string &msg) {
             return fail(h, GORDER_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-template <typename T>
-int upload(gorder_hip_handle *h, T **dst, const std::vector<T> &src) {
-    *dst = nullptr;
-    if (src.empty()) return GORDER_OK;
-    HIP_TRY(h, hipMalloc((void **)dst, src.size() * sizeof(T)));
-    HIP_TRY(h, hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+#define ST_TRY(expr)                                \
+    do {                                            \
+        const int st_ = (expr);                     \
+        if (st_ != GORDER_OK) return st_;           \
+    } while (0)
+
+// an allocation a policy of device_mem.h refused, as a status with HIP's words for it (reading the error clears it: the
+// handle stays usable)
+int alloc_failed(gorder_hip_handle *h, const char *call) {
+    return fail(h, GORDER_ERR_DEVICE, std::string(call) + ": " + hipGetErrorString(hipGetLastError()));
+}
+
+// exactly n elements; with `fill` every byte of them set to it (null stream: gorder_hip_create waits for the device at its end)
+template <typename T, typename Mem>
+int allocate(gorder_hip_handle *h, gorder::Buf<T, Mem> &dst, size_t n, int fill = -1) {
+    if (!dst.alloc(n)) return alloc_failed(h, std::is_same<Mem, DeviceMem>::value ? "hipMalloc" : "hipHostMalloc");
+    if (fill >= 0 && n) HIP_TRY(h, hipMemset(dst, fill, n * sizeof(T)));
     return GORDER_OK;
 }
 
 template <typename T>
-int ensure(gorder_hip_handle *h, T **buf, size_t *cap, size_t need) {
-    if (need <= *cap) return GORDER_OK;
-    if (*buf) HIP_TRY(h, hipFree(*buf));
-    *buf = nullptr;
-    *cap = 0;
-    const size_t n = need + need / 2;
-    HIP_TRY(h, hipMalloc((void **)buf, n * sizeof(T)));
-    *cap = n;
+int upload(gorder_hip_handle *h, DBuf<T> &dst, const std::vector<T> &src) {
+    ST_TRY(allocate(h, dst, src.size()));
+    if (!src.empty()) HIP_TRY(h, hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    return GORDER_OK;
+}
+
+// room for `need` elements, contents not kept (Buf::reserve); *grew: the block is a new one and holds nothing yet
+template <typename T>
+int ensure(gorder_hip_handle *h, DBuf<T> &buf, size_t need, bool *grew = nullptr) {
+    const gorder::Reserve r = buf.reserve(need);
+    if (grew) *grew = r == gorder::Reserve::Grew;
+    return r == gorder::Reserve::Failed ? alloc_failed(h, "hipMalloc") : GORDER_OK;
+}
+
+// an accumulator block of `words` words and its replicas (as many as the ordinary sums have, gorder::replica_count), zeroed
+// in the order of the handle's stream
+int alloc_zeroed(gorder_hip_handle *h, RepAcc &r, size_t words) {
+    if (!r.alloc(words, h->n_rep)) {
+        r.reset();
+        return alloc_failed(h, "hipMalloc");
+    }
+    HIP_TRY(h, r.zero_async(h->stream));
     return GORDER_OK;
 }
 
@@ -446,12 +512,11 @@ int timing_mark(gorder_hip_handle *h, const char *label) {
     if (!label && h->timing_open_label < 0) return GORDER_OK;
     // a pending segment holds at most two events of the ring: keep fewer than half of it pending
     while (h->timing_pending.size() >= gorder_hip_handle::kTimingEvents / 2u - 2u) {
-        const int st = timing_drain_oldest(h);
-        if (st != GORDER_OK) return st;
+        ST_TRY(timing_drain_oldest(h));
     }
     const uint32_t ev = h->timing_next_ev;
     h->timing_next_ev = (ev + 1u) % gorder_hip_handle::kTimingEvents;
-    if (!h->timing_ev[ev]) HIP_TRY(h, hipEventCreate(&h->timing_ev[ev]));
+    HIP_TRY(h, h->timing_ev[ev].create(hipEventDefault));
     HIP_TRY(h, hipEventRecord(h->timing_ev[ev], h->stream));
     if (h->timing_open_label >= 0) h->timing_pending.push_back({(uint32_t)h->timing_open_label, h->timing_open_ev, ev});
     h->timing_open_label = -1;
@@ -528,7 +593,7 @@ int launch_cell_list(gorder_hip_handle *h, const LocalArgs &lo, uint32_t ns, uin
 int run_dynamic_normals(gorder_hip_handle *h, const FrameArgs &a) {
     int st;
     const uint32_t n_mol = h->plan.n_mol_total;
-    if ((st = ensure(h, &h->d_dyn_normals, &h->dyn_normals_cap, (size_t)a.n_frames * n_mol)) != GORDER_OK) return st;
+    if ((st = ensure(h, h->d_dyn_normals, (size_t)a.n_frames * n_mol)) != GORDER_OK) return st;
     const gorder_dynamic_normal_t &dn = h->tables.dynamic_normal;
     const size_t ncell = (size_t)kLocalMaxCells1D * kLocalMaxCells1D;
     LocalArgs lo{};
@@ -580,7 +645,7 @@ int launch_molecule_rows(gorder_hip_handle *h, const FrameArgs &a, const gorder:
     const size_t wpf = (size_t)h->mol.n_groups * p.n_mol_total;
     const uint32_t sub = gorder::molecule_rows_subrange(a.n_frames, wpf, h->mol_stage_bytes);
     int st;
-    if ((st = ensure(h, &h->d_mol_stage, &h->mol_stage_cap, wpf * sub)) != GORDER_OK) return st;
+    if ((st = ensure(h, h->d_mol_stage, wpf * sub)) != GORDER_OK) return st;
     MolRowArgs mr{};
     mr.runs = h->d_mol_runs; mr.run_begin = h->d_mol_run_begin; mr.stage = h->d_mol_stage; mr.words_per_frame = (uint32_t)wpf;
     for (uint32_t lo = 0; lo < a.n_frames; lo += sub) {
@@ -616,12 +681,11 @@ int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &
     const uint32_t n_tiles = (uint32_t)p.tiles.size();
     const bool ac = (h->tables.flags & GORDER_FLAG_TRIG_ACOS_COS) != 0;
     if (h->dyn && !h->manual_active) {
-        const int st2 = run_dynamic_normals(h, a);
-        if (st2 != GORDER_OK) return st2;
+        ST_TRY(run_dynamic_normals(h, a));
     }
     if (h->extra.geom_kind) {
         int st2;
-        if ((st2 = ensure(h, &h->d_shapes, &h->shapes_cap, (size_t)a.n_frames * 8)) != GORDER_OK) return st2;
+        if ((st2 = ensure(h, h->d_shapes, (size_t)a.n_frames * 8)) != GORDER_OK) return st2;
         const gorder_geometry_t &ge = h->tables.geometry;
         GeomArgs ga{};
         ga.xyz = a.xyz; ga.box9 = a.box9; ga.n_atoms = a.n_atoms; ga.pbc = a.pbc;
@@ -654,8 +718,7 @@ int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &
         HIP_TRY(h, hipGetLastError());
     }
     if (route.family == BondFamily::TiledMol) {
-        const int st2 = launch_molecule_rows(h, a, route);
-        if (st2 != GORDER_OK) return st2;
+        ST_TRY(launch_molecule_rows(h, a, route));
     }
     if (route.extras || route.ua_mode >= 0) {
         // scatter-bound modes: plain per-sample kernels (see "Extras" above)
@@ -664,7 +727,7 @@ int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &
         e.shapes = h->d_shapes; e.inv_box = nullptr;
         if (route.ua_fast && a.pbc) {      // 1 / box edge per frame, once per frame instead of once per lane and frame
             int st3;
-            if ((st3 = ensure(h, &h->d_inv_box, &h->inv_box_cap, (size_t)a.n_frames * 8)) != GORDER_OK) return st3;
+            if ((st3 = ensure(h, h->d_inv_box, (size_t)a.n_frames * 8)) != GORDER_OK) return st3;
             hipLaunchKernelGGL(k_inv_box, dim3((4u * a.n_frames + 255u) / 256u), dim3(256), 0, h->stream, a.box9, a.n_frames, h->d_inv_box);
             e.inv_box = h->d_inv_box;
         }
@@ -673,16 +736,14 @@ int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &
         const size_t rec_per_frame = std::max(p.ua_tiles.size() * 3u, route.extras ? p.tiles.size() : (size_t)0) * kBlock;   // staged words per frame
         const uint32_t sub = gorder::map_subrange(a.n_frames, e.maps != 0, staged, h->map_fold_limit, h->map_max_mol, rec_per_frame);
         if (staged) {
-            const int st2 = ensure(h, &h->d_map_rec, &h->map_rec_cap, rec_per_frame * (((size_t)sub + 15) / 16 * 16));
-            if (st2 != GORDER_OK) return st2;
+            ST_TRY(ensure(h, h->d_map_rec, rec_per_frame * (((size_t)sub + 15) / 16 * 16)));
         }
         for (uint32_t lo = 0; lo < a.n_frames; lo += sub) {
             const uint32_t hi = std::min(a.n_frames, lo + sub), nf = hi - lo;
             if (e.maps) {
                 const uint64_t cost = (uint64_t)nf * h->map_max_mol;
                 if (h->map_pending + cost >= h->map_fold_limit) {
-                    const int st = fold_maps(h);
-                    if (st != GORDER_OK) return st;
+                    ST_TRY(fold_maps(h));
                 }
                 h->map_pending += cost;
             }
@@ -705,7 +766,7 @@ int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &
                     TIMING_MARK(h, route.label);
                     if (route.family == BondFamily::Shells) {
                         ShellArgs sa{};
-                        sa.n = h->n_shells; sa.rep = h->d_shell_rep; sa.n_rep = h->shell_rep;
+                        sa.n = h->n_shells; sa.rep = h->shells.rep; sa.n_rep = h->shells.n_rep;
                         for (uint32_t k = 0; k < GORDER_RADIAL_MAX_SHELLS; k++) sa.thr[k] = k < h->n_shells ? h->shell_thr[k] : INFINITY;
                         // the table of the widest tile, or the [2][256] u64 + [2][256] u32 of the direct route's reduction
                         const size_t lds = h->shell_direct ? (size_t)kBlock * 24u : h->shell_lds_bytes;
@@ -715,7 +776,7 @@ int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &
                         }); });
                     } else if (route.family == BondFamily::Dist) {
                         DistArgs da{};
-                        da.n_edges = h->hist_edges; da.edges = h->d_hist_edges; da.rep = h->d_hist_rep; da.n_rep = h->hist_rep;
+                        da.n_edges = h->hist_edges; da.edges = h->d_hist_edges; da.rep = h->hist.rep; da.n_rep = h->hist.n_rep;
                         // the edges, then the table of the widest tile or the ordinary sums' reduction, whichever is larger
                         const size_t lds = kDistEdgeBytes + std::max<size_t>(kDistReduceBytes, h->hist_direct ? 0u : h->hist_table_words * sizeof(uint32_t));
                         with_bool(ac, [&](auto AC) { with_bool(h->hist_direct, [&](auto DIRECT) {
@@ -777,12 +838,6 @@ int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &
 }
 
 // ---- collected history (gorder_hip_set_collect): staging block -> pinned chunks ----------------------------------------
-void *collect_host_alloc(size_t bytes) {
-    void *p = nullptr;
-    return hipHostMalloc(&p, bytes) == hipSuccess ? p : nullptr;
-}
-void collect_host_free(void *p) { (void)hipHostFree(p); }
-
 // reserve `n_rows` rows labelled `frames` and queue the copies that fill them from the staging block (a batch that crosses
 // a chunk boundary takes more than one copy); nothing waits
 int collect_copy_out(gorder_hip_handle *h, gorder::CollectStore &store, const void *d_block, const uint64_t *frames, size_t n_rows) {
@@ -804,7 +859,7 @@ int collect_flag_rows(gorder_hip_handle *h, size_t first_row, const std::vector<
     const unsigned long long total = (unsigned long long)frames.size() * wpr;
     if ((total + 3u) / 4u > 0x7fffffffull || frames.size() > 0xffffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "collect: batch too large");
     int st;
-    if ((st = ensure(h, &h->d_collect_words, &h->collect_words_cap, (size_t)total)) != GORDER_OK) return st;
+    if ((st = ensure(h, h->d_collect_words, (size_t)total)) != GORDER_OK) return st;
     TIMING_MARK(h, "k_collect_flags");
     hipLaunchKernelGGL(k_collect_flags, dim3((uint32_t)((total + 3u) / 4u)), dim3(256), 0, h->stream,
                        h->d_aflags + first_row * (size_t)n_mol, n_mol, (uint32_t)frames.size(), wpr, h->d_collect_words);
@@ -817,7 +872,7 @@ int collect_normal_rows(gorder_hip_handle *h, const uint64_t *frame_index, uint3
     const unsigned long long n = (unsigned long long)n_frames * h->plan.n_mol_total;
     if ((n + 255u) / 256u > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "collect: batch too large");
     int st;
-    if ((st = ensure(h, &h->d_collect_vec, &h->collect_vec_cap, (size_t)n)) != GORDER_OK) return st;
+    if ((st = ensure(h, h->d_collect_vec, (size_t)n)) != GORDER_OK) return st;
     TIMING_MARK(h, "k_collect_normals");
     hipLaunchKernelGGL(k_collect_normals, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, h->stream,
                        (const float4 *)h->d_dyn_normals, touched, n, h->d_collect_vec);
@@ -827,10 +882,21 @@ int collect_normal_rows(gorder_hip_handle *h, const uint64_t *frame_index, uint3
 
 // ---- whole-trajectory manual tables: expand what a batch needs (kernels_replay.h) -----------------------------------------
 // a small list of 32-bit rows for this batch, behind everything queued so far
-int upload_rows(gorder_hip_handle *h, uint32_t **buf, size_t *cap, const std::vector<uint32_t> &rows) {
-    const int st = ensure(h, buf, cap, rows.size());
-    if (st != GORDER_OK) return st;
-    HIP_TRY(h, hipMemcpyAsync(*buf, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+int upload_rows(gorder_hip_handle *h, DBuf<uint32_t> &buf, const std::vector<uint32_t> &rows) {
+    ST_TRY(ensure(h, buf, rows.size()));
+    HIP_TRY(h, hipMemcpyAsync(buf, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    return GORDER_OK;
+}
+// ... and one that batches repeat (d_arow, d_aframes): `held` is what the buffer holds while `valid`, and equal batches (same
+// length, same assignment pattern) skip the copy
+int upload_if_changed(gorder_hip_handle *h, DBuf<uint32_t> &buf, std::vector<uint32_t> &held, bool &valid, const std::vector<uint32_t> &rows) {
+    bool grew = false;
+    const int st = ensure(h, buf, rows.size(), &grew);
+    if (grew || st != GORDER_OK) valid = false;      // a new allocation holds nothing yet
+    if (st != GORDER_OK || (valid && held == rows)) return st;
+    ST_TRY(upload_rows(h, buf, rows));
+    held = rows;
+    valid = true;
     return GORDER_OK;
 }
 
@@ -840,15 +906,7 @@ int replay_flag_rows(gorder_hip_handle *h, const gorder::ReplayLeafletBatch &rb)
     const uint32_t n_mol = h->plan.n_mol_total, wpr = (uint32_t)gorder::replay_flag_words(n_mol);
     const unsigned long long total = (unsigned long long)rb.expand.size() * wpr;
     if ((total + 3u) / 4u > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "manual leaflet table: batch too large");
-    int st;
-    const size_t cap_before = h->aframes_cap;
-    if ((st = ensure(h, &h->d_aframes, &h->aframes_cap, rb.expand.size())) != GORDER_OK) return st;
-    if (h->aframes_cap != cap_before) h->up_aframes_at = nullptr;
-    if (h->up_aframes_at != h->d_aframes || h->up_aframes != rb.expand) {      // (equal batches skip the upload, as run_leaflets)
-        HIP_TRY(h, hipMemcpyAsync(h->d_aframes, rb.expand.data(), rb.expand.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-        h->up_aframes = rb.expand;
-        h->up_aframes_at = h->d_aframes;
-    }
+    ST_TRY(upload_if_changed(h, h->d_aframes, h->up_aframes, h->up_aframes_valid, rb.expand));
     TIMING_MARK(h, "k_replay_flags");
     hipLaunchKernelGGL(k_replay_flags, dim3((uint32_t)((total + 3u) / 4u)), dim3(256), 0, h->stream, h->d_ltable, h->d_aframes,
                        (uint32_t)rb.expand.size(), wpr, n_mol, h->tables.leaflets.flip ? 1u : 0u, h->d_aflags + n_mol);
@@ -862,8 +920,8 @@ int replay_normal_rows(gorder_hip_handle *h, const std::vector<uint32_t> &row_of
     const unsigned long long n = (unsigned long long)row_of_frame.size() * n_mol;
     if ((n + 255u) / 256u > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "manual normal table: batch too large");
     int st;
-    if ((st = ensure(h, &h->d_dyn_normals, &h->dyn_normals_cap, (size_t)n)) != GORDER_OK) return st;
-    if ((st = upload_rows(h, &h->d_nrow, &h->nrow_cap, row_of_frame)) != GORDER_OK) return st;
+    if ((st = ensure(h, h->d_dyn_normals, (size_t)n)) != GORDER_OK) return st;
+    if ((st = upload_rows(h, h->d_nrow, row_of_frame)) != GORDER_OK) return st;
     if (!n) return GORDER_OK;
     TIMING_MARK(h, "k_replay_normals");
     hipLaunchKernelGGL(k_replay_normals, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, h->stream, h->d_ntable, h->d_nrow, n_mol, n,
@@ -1001,19 +1059,18 @@ int gorder_hip_selftest_arithmetic(int device, uint64_t n, uint64_t seed, uint64
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return GORDER_ERR_NO_DEVICE;
     if (device < 0 || device >= count || hipSetDevice(device) != hipSuccess) return GORDER_ERR_INVALID_ARGUMENT;
-    unsigned long long *d = nullptr;
-    if (hipMalloc((void **)&d, 2 * sizeof(unsigned long long)) != hipSuccess) return GORDER_ERR_DEVICE;
+    DBuf<u64> d;
+    if (!d.alloc(2)) return GORDER_ERR_DEVICE;
     int st = GORDER_OK;
     if (hipMemset(d, 0, 2 * sizeof(unsigned long long)) != hipSuccess) st = GORDER_ERR_DEVICE;
     if (st == GORDER_OK) {
-        hipLaunchKernelGGL(k_selftest_arithmetic, dim3(4096), dim3(256), 0, 0, n, seed, d);
+        hipLaunchKernelGGL(k_selftest_arithmetic, dim3(4096), dim3(256), 0, 0, n, seed, d.get());
         unsigned long long out[2] = {0, 0};
         if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, d, sizeof(out), hipMemcpyDeviceToHost) != hipSuccess)
             st = GORDER_ERR_DEVICE;
         mismatches[0] = out[0];
         mismatches[1] = out[1];
     }
-    (void)hipFree(d);
     return st;
 }
 
@@ -1034,14 +1091,12 @@ int gorder_hip_selftest_trig(int device, int fn, uint32_t first_bits, uint32_t s
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return GORDER_ERR_NO_DEVICE;
     if (device < 0 || device >= count || hipSetDevice(device) != hipSuccess) return GORDER_ERR_INVALID_ARGUMENT;
     if (n == 0) return GORDER_OK;
-    float *d = nullptr;
-    if (hipMalloc((void **)&d, (size_t)n * sizeof(float)) != hipSuccess) return GORDER_ERR_DEVICE;
-    hipLaunchKernelGGL(k_selftest_trig, dim3((n + 255u) / 256u), dim3(256), 0, 0, fn, first_bits, stride, n, d);
-    int st = GORDER_OK;
+    DBuf<float> d;
+    if (!d.alloc(n)) return GORDER_ERR_DEVICE;
+    hipLaunchKernelGGL(k_selftest_trig, dim3((n + 255u) / 256u), dim3(256), 0, 0, fn, first_bits, stride, n, d.get());
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, d, (size_t)n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
-        st = GORDER_ERR_DEVICE;
-    (void)hipFree(d);
-    return st;
+        return GORDER_ERR_DEVICE;
+    return GORDER_OK;
 }
 
 namespace {
@@ -1100,8 +1155,9 @@ int gorder_hip_selftest_wave_ops(int device, uint32_t block, const double *f64, 
     const size_t n = block, b_fi = 0, b_i64 = 48, b_o64 = b_i64 + 8 * n, b_i32 = b_o64 + 8 * n * GORDER_WAVE_OPS_F64_ROWS,
                  b_iu = b_i32 + 4 * n, b_o32 = b_iu + 4 * n, b_ou = b_o32 + 4 * n * GORDER_WAVE_OPS_F32_ROWS,
                  bytes = b_ou + 4 * n * GORDER_WAVE_OPS_U32_ROWS;
-    char *d = nullptr;
-    if (hipMalloc((void **)&d, bytes) != hipSuccess) return GORDER_ERR_DEVICE;
+    DBuf<char> owned;
+    if (!owned.alloc(bytes)) return GORDER_ERR_DEVICE;
+    char *d = owned;
     int st = GORDER_OK;
     if (hipMemset(d, 0, bytes) != hipSuccess || hipMemcpy(d + b_i64, f64, 8 * n, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d + b_i32, f32, 4 * n, hipMemcpyHostToDevice) != hipSuccess ||
@@ -1118,15 +1174,13 @@ int gorder_hip_selftest_wave_ops(int device, uint32_t block, const double *f64, 
             hipMemcpy(out_finfo, d + b_fi, 4 * GORDER_WAVE_OPS_FINFO_WORDS, hipMemcpyDeviceToHost) != hipSuccess)
             st = GORDER_ERR_DEVICE;
     }
-    (void)hipFree(d);
     return st;
 }
 
 int gorder_hip_plan_tables(const gorder_tables_t *tables, gorder_hip_plan_t *out, int *selfcheck) {
     if (!tables || !out) return GORDER_ERR_INVALID_ARGUMENT;
     Plan p;
-    const int st = gorder::build_plan(*tables, env_flag("GORDER_HIP_FORCE_DIRECT"), p);
-    if (st != GORDER_OK) return st;
+    ST_TRY(gorder::build_plan(*tables, env_flag("GORDER_HIP_FORCE_DIRECT"), p));
     out->n_tiles = (uint32_t)p.tiles.size();
     out->block_threads = kBlock;
     out->max_window_atoms = p.max_window;
@@ -1145,6 +1199,311 @@ int gorder_hip_plan_tables(const gorder_tables_t *tables, gorder_hip_plan_t *out
 
 static size_t cl_frame_bytes(uint32_t n, uint32_t m_max);
 static size_t clcut_frame_bytes(uint32_t n, uint32_t m_max);
+
+// ---- gorder_hip_create, feature by feature: each validates, builds and allocates what its own feature needs ------------------
+static int create_ordermaps(gorder_hip_handle *h, const gorder_tables_t *t) {
+    const gorder_ordermap_t &om = t->ordermap;
+    if (!om.enabled) return GORDER_OK;
+    const Plan &p = h->plan;
+    ExtraArgs &e = h->extra;
+    if (!(om.bin[0] > 0.0f) || !(om.bin[1] > 0.0f) || om.plane > 2)
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "ordermap bin/plane");
+    // groan_rs GridMap::new: n = round(span / bin) + 1 tiles per axis
+    const float fx = roundf((om.span_x[1] - om.span_x[0]) / om.bin[0]);
+    const float fy = roundf((om.span_y[1] - om.span_y[0]) / om.bin[1]);
+    if (!(fx >= 0.0f) || !(fy >= 0.0f) || fx > 65535.0f || fy > 65535.0f)
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "ordermap span");
+    h->map_nx = (uint32_t)fx + 1u;
+    h->map_ny = (uint32_t)fy + 1u;
+    const size_t nmap = 3 * (size_t)p.n_acc * h->map_nx * h->map_ny;
+    const size_t npk = (t->leaflets.method != GORDER_LEAFLETS_NONE ? 2 : 1) * (nmap / 3);
+    ST_TRY(allocate(h, h->d_map_sums, nmap, 0));
+    ST_TRY(allocate(h, h->d_map_cnts, nmap, 0));
+    ST_TRY(allocate(h, h->d_map_packed, npk, 0));
+    // united atoms: stage + accumulate in LDS when one slot's packed map (x2 with leaflets) fits
+    const size_t lds_bytes = npk / p.n_acc * sizeof(u64);
+    h->map_lds_bytes = lds_bytes;
+    if (lds_bytes <= 150u * 1024u && !env_flag("GORDER_HIP_MAP_DIRECT")) {
+        ST_TRY(upload(h, h->d_ua_runs, p.ua_runs));
+        ST_TRY(upload(h, h->d_ua_run_begin, p.ua_run_begin));
+        ST_TRY(upload(h, h->d_runs, p.runs));
+        ST_TRY(upload(h, h->d_run_begin, p.run_begin));
+        ST_TRY(upload(h, h->d_items_by_slot, p.items_by_slot));
+        ST_TRY(upload(h, h->d_ua_item_run, p.ua_item_run));
+        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_map_accumulate),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        h->map_staged = true;
+    }
+    e.maps = 1; e.plane = om.plane; e.x0 = om.span_x[0]; e.y0 = om.span_y[0];
+    e.binx = om.bin[0]; e.biny = om.bin[1]; e.nx = h->map_nx; e.ny = h->map_ny;
+    e.inv_binx = 1.0f / om.bin[0]; e.inv_biny = 1.0f / om.bin[1];
+    e.bin_core = (om.bin[0] >= 0x1p-40f && om.bin[0] <= 0x1p+40f && om.bin[1] >= 0x1p-40f && om.bin[1] <= 0x1p+40f) ? 1 : 0;
+    e.map_packed = h->d_map_packed;
+    return GORDER_OK;
+}
+
+static int create_geometry(gorder_hip_handle *h, const gorder_tables_t *t) {
+    const gorder_geometry_t &ge = t->geometry;
+    if (ge.kind == GORDER_GEOM_NONE) return GORDER_OK;
+    ExtraArgs &e = h->extra;
+    if (ge.kind > GORDER_GEOM_SPHERE || ge.reference > GORDER_GEOMREF_GROUP || ge.orientation > 2)
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "geometry kind/reference/orientation");
+    if (ge.reference == GORDER_GEOMREF_BOX_CENTER && !t->handle_pbc)
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "box-centre reference needs handle_pbc (pbc.rs:243-245)");
+    if (ge.reference == GORDER_GEOMREF_POINT && t->handle_pbc &&
+        !(ge.structure_box[0] > 0.0f && ge.structure_box[1] > 0.0f && ge.structure_box[2] > 0.0f))
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "geometry.structure_box");
+    if (ge.reference == GORDER_GEOMREF_GROUP) {
+        if (!ge.group || ge.n_group == 0) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "geometry.group");
+        std::vector<uint32_t> grp(ge.group, ge.group + ge.n_group);
+        for (uint32_t a : grp)
+            if (a >= t->n_atoms) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "geometry group index out of range");
+        ST_TRY(upload(h, h->d_geom_group, grp));
+    }
+    e.geom_kind = (int)ge.kind; e.geom_invert = ge.invert ? 1 : 0; e.geom_orient = (int)ge.orientation;
+    e.geom_thr = local_radius_threshold(ge.radius);
+    h->tables.geometry.group = nullptr;
+    return GORDER_OK;
+}
+
+// the error words, the accumulator block the handle owns and its replicas
+static int create_accumulators(gorder_hip_handle *h) {
+    const Plan &p = h->plan;
+    ST_TRY(allocate(h, h->d_err, kErrWords + 2u));     // (+ the ticket of k_batch_end)
+    HIP_TRY(h, hipMemset(h->d_err, 0xff, kErrWords * sizeof(uint32_t)));   // kErrNone
+    HIP_TRY(h, hipMemset(h->d_err + kErrWords, 0, 2u * sizeof(uint32_t)));
+    h->acc_words = 4 * (size_t)p.n_acc + 1;
+    ST_TRY(allocate(h, h->own_acc, h->acc_words, 0));
+    h->d_acc = h->own_acc;
+    if (const char *e = getenv("GORDER_HIP_MAP_FOLD_LIMIT")) {
+        const long v = atol(e);
+        if (v >= 2 && (unsigned long long)v <= kMapFoldLimit) h->map_fold_limit = (uint64_t)v;
+    }
+    if (const char *e = getenv("GORDER_HIP_REPLICAS")) {
+        const int r = atoi(e);
+        if (r >= 1 && r <= 1024) h->n_rep = (uint32_t)r;
+    }
+    return p.n_acc ? allocate(h, h->d_rep, (size_t)h->n_rep * 4u * p.n_acc, 0) : GORDER_OK;
+}
+
+// k_local_build (dynamic normals, local leaflets) takes more dynamic LDS than a kernel gets unasked
+static int local_build_attributes(gorder_hip_handle *h) {
+    for (const void *fn : {reinterpret_cast<const void *>(k_local_build<2>), reinterpret_cast<const void *>(k_local_build<5>),
+                           reinterpret_cast<const void *>(k_local_build<kLocalBuildTrips>)})
+        HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLocalBuildLds));
+    return GORDER_OK;
+}
+
+static int create_dynamic_normals(gorder_hip_handle *h, const gorder_tables_t *t) {
+    const gorder_dynamic_normal_t &dn = t->dynamic_normal;
+    if (!dn.enabled) return GORDER_OK;
+    const Plan &p = h->plan;
+    if (!(dn.radius > 0.0f)) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "dynamic normals need a positive radius");
+    if (!dn.cloud || dn.n_cloud == 0) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "dynamic normals need the NormalHeads group");
+    if (!p.direct.empty()) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "dynamic normals: a bond spans more than the LDS window");
+    std::vector<uint32_t> cloud(dn.cloud, dn.cloud + dn.n_cloud), nheads;
+    for (uint32_t a : cloud)
+        if (a >= t->n_atoms) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "NormalHeads index out of range");
+    for (uint32_t m = 0; m < t->n_molecule_types; m++) {
+        const gorder_moltype_t &mt = t->molecule_types[m];
+        if (!mt.normal_heads) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "dynamic normals need normal_heads[] per molecule type");
+        for (uint32_t k = 0; k < mt.n_molecules; k++) {
+            if (mt.normal_heads[k] >= t->n_atoms) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "normal head index out of range");
+            nheads.push_back(mt.normal_heads[k]);
+        }
+    }
+    ST_TRY(upload(h, h->d_dyn_cloud, cloud));
+    ST_TRY(upload(h, h->d_dyn_heads, nheads));
+    h->host_dyn_heads = nheads;
+    const size_t nm = dn.n_cloud, ncell = (size_t)kLocalMaxCells1D * kLocalMaxCells1D;
+    const size_t sl = h->dyn_slab = local_slab_frames(nm);
+    ST_TRY(local_build_attributes(h));
+    ST_TRY(allocate(h, h->d_dyn_cell_of, sl * nm));
+    ST_TRY(allocate(h, h->d_dyn_rec, sl * nm * 4));
+    ST_TRY(allocate(h, h->d_dyn_count, sl * (2 * ncell + 1)));
+    ST_TRY(allocate(h, h->d_dyn_cov, sl * (size_t)(p.n_mol_total ? p.n_mol_total : 1)));
+    h->dyn = true;
+    return GORDER_OK;
+}
+
+// what every leaflet method reads: each molecule's head (`heads`, kept for the methods below), the methyls of the individual
+// method, the membrane group of the global and local ones
+static int create_leaflet_tables(gorder_hip_handle *h, const gorder_tables_t *t, std::vector<uint32_t> &heads) {
+    const gorder_leaflets_t &lf = t->leaflets;
+    const Plan &p = h->plan;
+    if (lf.method > GORDER_LEAFLETS_CLUSTERING) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.method");
+    if (lf.method != GORDER_LEAFLETS_SPHERICAL && lf.method != GORDER_LEAFLETS_CLUSTERING && lf.normal_dim > 2) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.normal_dim");
+    std::vector<uint32_t> mb(1, 0), ma;
+    for (uint32_t m = 0; m < t->n_molecule_types; m++) {
+        const gorder_moltype_t &mt = t->molecule_types[m];
+        if (lf.method != GORDER_LEAFLETS_MANUAL && !mt.heads)
+            return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets need heads[] per molecule type");
+        if (lf.method == GORDER_LEAFLETS_INDIVIDUAL && (!mt.methyls || mt.n_methyls == 0))
+            return fail(h, GORDER_ERR_INVALID_ARGUMENT, "individual leaflets need methyls[]");
+        for (uint32_t k = 0; k < mt.n_molecules; k++) {
+            const uint32_t hd = mt.heads ? mt.heads[k] : 0;
+            if (hd >= t->n_atoms) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "head index out of range");
+            heads.push_back(hd);
+            if (lf.method == GORDER_LEAFLETS_INDIVIDUAL)
+                for (uint32_t q = 0; q < mt.n_methyls; q++) {
+                    const uint32_t a = mt.methyls[(size_t)k * mt.n_methyls + q];
+                    if (a >= t->n_atoms) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "methyl index out of range");
+                    ma.push_back(a);
+                }
+            mb.push_back((uint32_t)ma.size());
+        }
+    }
+    ST_TRY(upload(h, h->d_heads, heads));
+    h->host_heads = heads;
+    if (lf.method == GORDER_LEAFLETS_LOCAL) {   // error key of a failed local centre: first slot of the molecule's type
+        std::vector<uint32_t> ms;
+        for (uint32_t m = 0; m < t->n_molecule_types; m++) ms.insert(ms.end(), t->molecule_types[m].n_molecules, p.slot0[m]);
+        ST_TRY(upload(h, h->d_mol_slot0, ms));
+    }
+    ST_TRY(upload(h, h->d_methyl_begin, mb));
+    ST_TRY(upload(h, h->d_methyl_atoms, ma));
+    if (lf.method == GORDER_LEAFLETS_LOCAL && !(lf.radius > 0.0f))
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "local leaflets need a positive radius");
+    if (lf.method == GORDER_LEAFLETS_GLOBAL || lf.method == GORDER_LEAFLETS_LOCAL) {
+        if (!lf.membrane || lf.n_membrane == 0)
+            return fail(h, GORDER_ERR_INVALID_ARGUMENT, "global/local leaflets need the membrane group");
+        std::vector<uint32_t> mem(lf.membrane, lf.membrane + lf.n_membrane);
+        for (uint32_t a : mem)
+            if (a >= t->n_atoms) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "membrane index out of range");
+        ST_TRY(upload(h, h->d_membrane, mem));
+        h->membrane_is_frame = lf.n_membrane == t->n_atoms && !env_flag("GORDER_HIP_LEAFLETS_GENERIC");
+        for (uint32_t i = 0; i < lf.n_membrane && h->membrane_is_frame; i++) h->membrane_is_frame = mem[i] == i;
+    }
+    return GORDER_OK;
+}
+
+// the clustering methods' group "ClusterHeads" (leaflets.membrane) -> d_membrane, and every head's slot in it: each molecule's
+// head is its own atom of the group (get_reference_head, leaflets.rs:1340-1345; an atom listed twice counts where it is first)
+static int upload_cluster_group(gorder_hip_handle *h, const gorder_tables_t *t, const std::vector<uint32_t> &heads, bool ascending,
+                                std::vector<uint32_t> &head_slot) {
+    const gorder_leaflets_t &lf = t->leaflets;
+    std::vector<uint32_t> grp(lf.membrane, lf.membrane + lf.n_membrane);
+    std::vector<int32_t> slot_of(t->n_atoms, -1);       // atom -> slot in the group
+    for (uint32_t i = 0; i < lf.n_membrane; i++) {
+        if (grp[i] >= t->n_atoms) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.membrane: index out of range");
+        if (ascending && i && grp[i] <= grp[i - 1]) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.membrane: clustering needs ascending, distinct atoms");
+        if (slot_of[grp[i]] < 0) slot_of[grp[i]] = (int32_t)i;
+    }
+    for (uint32_t hd : heads) {
+        if (slot_of[hd] < 0)
+            return fail(h, GORDER_ERR_INVALID_ARGUMENT, "molecule_types[].heads: a head is not a member of leaflets.membrane");
+        head_slot.push_back((uint32_t)slot_of[hd]);
+    }
+    return upload(h, h->d_membrane, grp);
+}
+
+static int create_spherical(gorder_hip_handle *h, const gorder_tables_t *t, const std::vector<uint32_t> &heads) {
+    const gorder_leaflets_t &lf = t->leaflets;
+    // leaflets.membrane is the group "ClusterHeads"; fewer than two atoms: NotEnoughAtomsToCluster (leaflets.rs:106-115)
+    if (!lf.membrane || lf.n_membrane < 2)
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.n_membrane: spherical clustering needs at least two group atoms");
+    // (the kernel needs no molecule -> slot table on the device: it recomputes the head's distance and responsibility from the atom)
+    std::vector<uint32_t> head_slot;
+    ST_TRY(upload_cluster_group(h, t, heads, false, head_slot));
+    // small groups: 256 threads a frame (16 atoms a thread, cheap barriers); larger ones 1024, and past
+    // 16 x 1024 atoms a scratch row per frame of a launch — at most 64 MiB, whatever the batch
+    h->sph_threads = lf.n_membrane <= 256u * (uint32_t)kSphKeep ? 256u : 1024u;
+    const uint32_t resident = h->sph_threads * (uint32_t)kSphKeep;
+    h->sph_spill = lf.n_membrane > resident ? lf.n_membrane - resident : 0u;
+    if (h->sph_spill) {
+        h->sph_slab = (uint32_t)std::min<size_t>(std::max<size_t>(((size_t)64 << 20) / (h->sph_spill * sizeof(float)), 1), 4096);
+        if (const char *ev = getenv("GORDER_HIP_SPHERICAL_SLAB"))      // (tests: frames per launch; only lowers the cap)
+            h->sph_slab = std::min(h->sph_slab, (uint32_t)std::max(1, atoi(ev)));
+        ST_TRY(allocate(h, h->d_sph_spill, (size_t)h->sph_slab * h->sph_spill));
+    }
+    return allocate(h, h->d_sph_stats, 12, 0);
+}
+
+static int create_clustering(gorder_hip_handle *h, const gorder_tables_t *t, const std::vector<uint32_t> &heads) {
+    const gorder_leaflets_t &lf = t->leaflets;
+    // leaflets.membrane is the group "ClusterHeads" (leaflets.rs:96-105: at least two atoms); the dense route holds
+    // n x (steps + 1) basis vectors a frame, hence the bound
+    if (!lf.membrane || lf.n_membrane < kClMinGroup)
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.n_membrane: clustering needs at least two group atoms");
+    h->cl_cut = (t->flags & GORDER_FLAG_CLUSTER_CUTOFF) != 0;
+    if (!h->cl_cut && lf.n_membrane > kClMaxGroup)
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.n_membrane: clustering takes at most 8192 group atoms");
+    if (h->cl_cut && lf.n_membrane > kClCutMaxGroup)
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.n_membrane: clustering with GORDER_FLAG_CLUSTER_CUTOFF takes at most 131072 group atoms");
+    std::vector<uint32_t> head_slot;
+    ST_TRY(upload_cluster_group(h, t, heads, true, head_slot));
+    ST_TRY(upload(h, h->d_cl_head_slot, head_slot));
+    const uint32_t n = lf.n_membrane;
+    h->cl_m_max = std::min<uint32_t>(n - 1u, (uint32_t)kClMaxSteps);
+    // at most 512 MiB of scratch whatever the batch, at most 1024 frames a launch
+    h->cl_stored_w = env_flag("GORDER_HIP_CLUSTER_STORED_W");
+    h->cl_tiles = (n + kClCutTile - 1u) / kClCutTile;
+    h->cl_sort = (n + kClCutSort - 1u) / kClCutSort;
+    const size_t per_frame = h->cl_cut ? clcut_frame_bytes(n, h->cl_m_max)
+                                       : cl_frame_bytes(n, h->cl_m_max) + (h->cl_stored_w ? (size_t)n * n * 4 : 0);
+    h->cl_slab = (uint32_t)std::min<size_t>(std::max<size_t>(((size_t)512 << 20) / per_frame, 1), 1024);
+    ST_TRY(allocate(h, h->d_cl_scratch, (size_t)h->cl_slab * per_frame));
+    ST_TRY(allocate(h, h->d_cl_carry, n));
+    ST_TRY(allocate(h, h->d_cl_is0, h->cl_slab));
+    return allocate(h, h->d_cl_stats, 12, 0);
+}
+
+// one read for global leaflets + order parameters: the tables of k_bonds_tiled<..., MOM> and k_spec_fixup
+static int create_speculation(gorder_hip_handle *h) {
+    const Plan &p = h->plan;
+    std::vector<uint2> own(p.tiles.size());
+    for (size_t i = 0; i < own.size(); i++) own[i] = make_uint2(p.own[2 * i], p.own[2 * i + 1]);
+    ST_TRY(upload(h, h->d_own, own));
+    std::vector<std::vector<SpecSample>> per_mol(p.n_mol_total);
+    for (const Tile &tile : p.tiles)
+        for (uint32_t q = 0; q < tile.n_items; q++) {
+            const Item &it = p.items[tile.item0 + q];
+            per_mol[it.mol].push_back({tile.atom0 + it.li, tile.atom0 + it.lj, p.tile_slots[tile.slot0 + it.lslot]});
+        }
+    std::vector<uint32_t> mbeg(1, 0);
+    std::vector<SpecSample> all;
+    for (const auto &v : per_mol) { all.insert(all.end(), v.begin(), v.end()); mbeg.push_back((uint32_t)all.size()); }
+    ST_TRY(upload(h, h->d_spec_mol_begin, mbeg));
+    ST_TRY(upload(h, h->d_spec_samples, all));
+    std::vector<uint2> oh(p.own_heads.size() / 2);
+    for (size_t i = 0; i < oh.size(); i++) oh[i] = make_uint2(p.own_heads[2 * i], p.own_heads[2 * i + 1]);
+    ST_TRY(upload(h, h->d_own_head_begin, p.own_head_begin));
+    ST_TRY(upload(h, h->d_own_heads, oh));
+    ST_TRY(allocate(h, h->d_spec_counters, 4, 0));
+    ST_TRY(allocate(h, h->h_spec_counters, 2 * gorder_hip_handle::kSpecRing));
+    for (Event &ev : h->spec_counters_copied) HIP_TRY(h, ev.create());
+    h->spec_enabled = true;
+    return GORDER_OK;
+}
+
+static int create_local_leaflets(gorder_hip_handle *h, const gorder_tables_t *t) {
+    const Plan &p = h->plan;
+    const size_t nm = t->leaflets.n_membrane, ncell = (size_t)kLocalMaxCells1D * kLocalMaxCells1D;
+    const size_t sl = h->local_slab = local_slab_frames(nm);
+    ST_TRY(local_build_attributes(h));
+    // rows of cells with a halo (periodic boxes, k_local_flags_rows): the first cells of a row are there twice,
+    // records included — room for twice the membrane
+    h->local_halo = t->handle_pbc && !env_flag("GORDER_HIP_LOCAL_ATOMS_ONLY");
+    h->local_rec_stride = (h->local_halo ? 2u : 1u) * nm;
+    ST_TRY(allocate(h, h->d_lcell_of, sl * nm));
+    ST_TRY(allocate(h, h->d_ltrig, sl * h->local_rec_stride * (sizeof(LocalRec) / sizeof(float))));
+    ST_TRY(allocate(h, h->d_lcell_count, sl * (ncell + 1)));
+    ST_TRY(allocate(h, h->d_lcell_fill, sl * ncell));
+    ST_TRY(allocate(h, h->d_lgrid, sl));
+    if (!h->local_halo) return GORDER_OK;   // (GORDER_HIP_LOCAL_ATOMS_ONLY, an A/B switch: every candidate atom by atom, the general passes)
+    const size_t row_cells = sl * (size_t)kLocalMaxCells1D * (kLocalMaxCells1D + 1u);
+    ST_TRY(allocate(h, h->d_lrowpre, row_cells));
+    ST_TRY(allocate(h, h->d_ledge, row_cells));
+    ST_TRY(allocate(h, h->d_lfinfo, sl));
+    ST_TRY(allocate(h, h->d_lneed, sl + 1));
+    ST_TRY(allocate(h, h->d_lsummary, 2, 0));
+    ST_TRY(allocate(h, h->h_lsummary, 2));
+    h->h_lsummary[0] = h->h_lsummary[1] = 0u;
+    HIP_TRY(h, h->lsummary_written.create());
+    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_local_decide), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDecideLds));
+    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_local_sums), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSumsLds));
+    return allocate(h, h->d_ltodo, 1 + sl * (size_t)(p.n_mol_total ? p.n_mol_total : 1));
+}
 
 int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
     if (!t || !out) return GORDER_ERR_INVALID_ARGUMENT;
@@ -1168,114 +1527,36 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
     // united atoms: a wave = 4 slots x 16 molecules (plan.h) — except for per-frame rows and nothing else, where a wave of
     // ONE slot sends a fourth of the atomics (0.433 against 0.449 ms per 3 000 frames of the 256-lipid membrane)
     const bool ua_rows_only = t->timewise && !t->ordermap.enabled && t->geometry.kind == GORDER_GEOM_NONE && !t->dynamic_normal.enabled;
-    int st = gorder::build_plan(*t, env_flag("GORDER_HIP_FORCE_DIRECT"), h->plan, !env_flag("GORDER_HIP_UA_SLOT_WAVES") && !ua_rows_only);
+    const int st = gorder::build_plan(*t, env_flag("GORDER_HIP_FORCE_DIRECT"), h->plan, !env_flag("GORDER_HIP_UA_SLOT_WAVES") && !ua_rows_only);
     if (st != GORDER_OK) return fail(h, st, "invalid bond tables");
     const Plan &p = h->plan;
     for (uint32_t m = 0; m < t->n_molecule_types; m++)
         h->map_max_mol = std::max(h->map_max_mol, t->molecule_types[m].n_molecules);
-    HIP_TRY(h, hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+    HIP_TRY(h, h->own_stream.create());
     h->stream = h->own_stream;
-    if ((st = upload(h, &h->d_tiles, p.tiles)) != GORDER_OK) return st;
-    if ((st = upload(h, &h->d_items, p.items)) != GORDER_OK) return st;
-    if ((st = upload(h, &h->d_tile_slots, p.tile_slots)) != GORDER_OK) return st;
-    if ((st = upload(h, &h->d_direct, p.direct)) != GORDER_OK) return st;
-    if ((st = upload(h, &h->d_ua_tiles, p.ua_tiles)) != GORDER_OK) return st;
-    if ((st = upload(h, &h->d_ua_items, p.ua_items)) != GORDER_OK) return st;
-    if ((st = upload(h, &h->d_ua_tile_slots, p.ua_tile_slots)) != GORDER_OK) return st;
-    {
-        ExtraArgs &e = h->extra;
-        // construction angles of the united-atom hydrogens (uaorder.rs:34-41); sin/cos with the host
-        // libm, as the reference's nalgebra Rotation3::from_axis_angle does
-        e.sin_tet = sinf(1.910633f); e.cos_tet = cosf(1.910633f);
-        e.sin_ch3 = sinf(2.0943952f); e.cos_ch3 = cosf(2.0943952f);
-        e.sin_half = sinf(0.9553165f); e.cos_half = cosf(0.9553165f);
-        const gorder_ordermap_t &om = t->ordermap;
-        if (om.enabled) {
-            if (!(om.bin[0] > 0.0f) || !(om.bin[1] > 0.0f) || om.plane > 2)
-                return fail(h, GORDER_ERR_INVALID_ARGUMENT, "ordermap bin/plane");
-            // groan_rs GridMap::new: n = round(span / bin) + 1 tiles per axis
-            const float fx = roundf((om.span_x[1] - om.span_x[0]) / om.bin[0]);
-            const float fy = roundf((om.span_y[1] - om.span_y[0]) / om.bin[1]);
-            if (!(fx >= 0.0f) || !(fy >= 0.0f) || fx > 65535.0f || fy > 65535.0f)
-                return fail(h, GORDER_ERR_INVALID_ARGUMENT, "ordermap span");
-            h->map_nx = (uint32_t)fx + 1u;
-            h->map_ny = (uint32_t)fy + 1u;
-            const size_t nmap = 3 * (size_t)p.n_acc * h->map_nx * h->map_ny;
-            HIP_TRY(h, hipMalloc((void **)&h->d_map_sums, nmap * sizeof(unsigned long long)));
-            HIP_TRY(h, hipMalloc((void **)&h->d_map_cnts, nmap * sizeof(unsigned long long)));
-            HIP_TRY(h, hipMemset(h->d_map_sums, 0, nmap * sizeof(unsigned long long)));
-            HIP_TRY(h, hipMemset(h->d_map_cnts, 0, nmap * sizeof(unsigned long long)));
-            const size_t npk = (t->leaflets.method != GORDER_LEAFLETS_NONE ? 2 : 1) * (nmap / 3);
-            HIP_TRY(h, hipMalloc((void **)&h->d_map_packed, npk * sizeof(unsigned long long)));
-            HIP_TRY(h, hipMemset(h->d_map_packed, 0, npk * sizeof(unsigned long long)));
-            // united atoms: stage + accumulate in LDS when one slot's packed map (x2 with leaflets) fits
-            const size_t lds_bytes = npk / p.n_acc * sizeof(unsigned long long);
-            h->map_lds_bytes = lds_bytes;
-            if (lds_bytes <= 150u * 1024u && !env_flag("GORDER_HIP_MAP_DIRECT")) {
-                if ((st = upload(h, &h->d_ua_runs, p.ua_runs)) != GORDER_OK) return st;
-                if ((st = upload(h, &h->d_ua_run_begin, p.ua_run_begin)) != GORDER_OK) return st;
-                if ((st = upload(h, &h->d_runs, p.runs)) != GORDER_OK) return st;
-                if ((st = upload(h, &h->d_run_begin, p.run_begin)) != GORDER_OK) return st;
-                if ((st = upload(h, &h->d_items_by_slot, p.items_by_slot)) != GORDER_OK) return st;
-                if ((st = upload(h, &h->d_ua_item_run, p.ua_item_run)) != GORDER_OK) return st;
-                HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_map_accumulate),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-                h->map_staged = true;
-            }
-            e.maps = 1; e.plane = om.plane; e.x0 = om.span_x[0]; e.y0 = om.span_y[0];
-            e.binx = om.bin[0]; e.biny = om.bin[1]; e.nx = h->map_nx; e.ny = h->map_ny;
-            e.inv_binx = 1.0f / om.bin[0]; e.inv_biny = 1.0f / om.bin[1];
-            e.bin_core = (om.bin[0] >= 0x1p-40f && om.bin[0] <= 0x1p+40f && om.bin[1] >= 0x1p-40f && om.bin[1] <= 0x1p+40f) ? 1 : 0;
-            e.map_packed = h->d_map_packed;
-        }
-        e.tw = t->timewise ? 1 : 0;
-        if (t->timewise && !p.tiles.empty()) {      // k_bonds_tiled_tw: the tile items in slot order and their runs
-            if (!h->d_items_by_slot && (st = upload(h, &h->d_items_by_slot, p.items_by_slot)) != GORDER_OK) return st;
-            if ((st = upload(h, &h->d_item_run, p.item_run)) != GORDER_OK) return st;
-        }
-        const gorder_geometry_t &ge = t->geometry;
-        if (ge.kind != GORDER_GEOM_NONE) {
-            if (ge.kind > GORDER_GEOM_SPHERE || ge.reference > GORDER_GEOMREF_GROUP || ge.orientation > 2)
-                return fail(h, GORDER_ERR_INVALID_ARGUMENT, "geometry kind/reference/orientation");
-            if (ge.reference == GORDER_GEOMREF_BOX_CENTER && !t->handle_pbc)
-                return fail(h, GORDER_ERR_INVALID_ARGUMENT, "box-centre reference needs handle_pbc (pbc.rs:243-245)");
-            if (ge.reference == GORDER_GEOMREF_POINT && t->handle_pbc &&
-                !(ge.structure_box[0] > 0.0f && ge.structure_box[1] > 0.0f && ge.structure_box[2] > 0.0f))
-                return fail(h, GORDER_ERR_INVALID_ARGUMENT, "geometry.structure_box");
-            if (ge.reference == GORDER_GEOMREF_GROUP) {
-                if (!ge.group || ge.n_group == 0) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "geometry.group");
-                std::vector<uint32_t> grp(ge.group, ge.group + ge.n_group);
-                for (uint32_t a : grp)
-                    if (a >= t->n_atoms) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "geometry group index out of range");
-                if ((st = upload(h, &h->d_geom_group, grp)) != GORDER_OK) return st;
-            }
-            e.geom_kind = (int)ge.kind; e.geom_invert = ge.invert ? 1 : 0; e.geom_orient = (int)ge.orientation;
-            e.geom_thr = local_radius_threshold(ge.radius);
-            h->tables.geometry.group = nullptr;
-        }
-        if ((e.maps || e.tw || e.geom_kind) && !p.direct.empty())
-            return fail(h, GORDER_ERR_INVALID_ARGUMENT,
-                        "ordermaps / timewise / geometry need every bond to fit an atom window");
+    ST_TRY(upload(h, h->d_tiles, p.tiles));
+    ST_TRY(upload(h, h->d_items, p.items));
+    ST_TRY(upload(h, h->d_tile_slots, p.tile_slots));
+    ST_TRY(upload(h, h->d_direct, p.direct));
+    ST_TRY(upload(h, h->d_ua_tiles, p.ua_tiles));
+    ST_TRY(upload(h, h->d_ua_items, p.ua_items));
+    ST_TRY(upload(h, h->d_ua_tile_slots, p.ua_tile_slots));
+    ExtraArgs &e = h->extra;
+    // construction angles of the united-atom hydrogens (uaorder.rs:34-41); sin/cos with the host
+    // libm, as the reference's nalgebra Rotation3::from_axis_angle does
+    e.sin_tet = sinf(1.910633f); e.cos_tet = cosf(1.910633f);
+    e.sin_ch3 = sinf(2.0943952f); e.cos_ch3 = cosf(2.0943952f);
+    e.sin_half = sinf(0.9553165f); e.cos_half = cosf(0.9553165f);
+    ST_TRY(create_ordermaps(h, t));
+    e.tw = t->timewise ? 1 : 0;
+    if (t->timewise && !p.tiles.empty()) {      // k_bonds_tiled_tw: the tile items in slot order and their runs
+        if (!h->d_items_by_slot) ST_TRY(upload(h, h->d_items_by_slot, p.items_by_slot));
+        ST_TRY(upload(h, h->d_item_run, p.item_run));
     }
-    HIP_TRY(h, hipMalloc((void **)&h->d_err, (kErrWords + 2u) * sizeof(uint32_t)));     // (+ the ticket of k_batch_end)
-    HIP_TRY(h, hipMemset(h->d_err, 0xff, kErrWords * sizeof(uint32_t)));   // kErrNone
-    HIP_TRY(h, hipMemset(h->d_err + kErrWords, 0, 2u * sizeof(uint32_t)));
-    h->acc_words = 4 * (size_t)p.n_acc + 1;
-    HIP_TRY(h, hipMalloc((void **)&h->d_acc, h->acc_words * sizeof(unsigned long long)));
-    HIP_TRY(h, hipMemset(h->d_acc, 0, h->acc_words * sizeof(unsigned long long)));
-    if (const char *e = getenv("GORDER_HIP_MAP_FOLD_LIMIT")) {
-        const long v = atol(e);
-        if (v >= 2 && (unsigned long long)v <= kMapFoldLimit) h->map_fold_limit = (uint64_t)v;
-    }
-    if (const char *e = getenv("GORDER_HIP_REPLICAS")) {
-        const int r = atoi(e);
-        if (r >= 1 && r <= 1024) h->n_rep = (uint32_t)r;
-    }
-    if (p.n_acc) {
-        const size_t rep_bytes = (size_t)h->n_rep * 4u * p.n_acc * sizeof(unsigned long long);
-        HIP_TRY(h, hipMalloc((void **)&h->d_rep, rep_bytes));
-        HIP_TRY(h, hipMemset(h->d_rep, 0, rep_bytes));
-    }
+    ST_TRY(create_geometry(h, t));
+    if ((e.maps || e.tw || e.geom_kind) && !p.direct.empty())
+        return fail(h, GORDER_ERR_INVALID_ARGUMENT, "ordermaps / timewise / geometry need every bond to fit an atom window");
+    ST_TRY(create_accumulators(h));
     {   // |normal| with the f32 sequence of nalgebra's norm (oracle: norm3)
         const float *n = t->normal;
         h->n2sq = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
@@ -1309,212 +1590,16 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
         if (e != hipSuccess || per_cu < 1) per_cu = 4;
         h->wg_capacity = (uint32_t)n_cu * (uint32_t)per_cu;
     }
-
-    const gorder_dynamic_normal_t &dn = t->dynamic_normal;
-    if (dn.enabled) {
-        if (!(dn.radius > 0.0f)) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "dynamic normals need a positive radius");
-        if (!dn.cloud || dn.n_cloud == 0) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "dynamic normals need the NormalHeads group");
-        if (!p.direct.empty()) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "dynamic normals: a bond spans more than the LDS window");
-        std::vector<uint32_t> cloud(dn.cloud, dn.cloud + dn.n_cloud), nheads;
-        for (uint32_t a : cloud)
-            if (a >= t->n_atoms) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "NormalHeads index out of range");
-        for (uint32_t m = 0; m < t->n_molecule_types; m++) {
-            const gorder_moltype_t &mt = t->molecule_types[m];
-            if (!mt.normal_heads) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "dynamic normals need normal_heads[] per molecule type");
-            for (uint32_t k = 0; k < mt.n_molecules; k++) {
-                if (mt.normal_heads[k] >= t->n_atoms) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "normal head index out of range");
-                nheads.push_back(mt.normal_heads[k]);
-            }
-        }
-        if ((st = upload(h, &h->d_dyn_cloud, cloud)) != GORDER_OK) return st;
-        if ((st = upload(h, &h->d_dyn_heads, nheads)) != GORDER_OK) return st;
-        h->host_dyn_heads = nheads;
-        const size_t nm = dn.n_cloud, ncell = (size_t)kLocalMaxCells1D * kLocalMaxCells1D;
-        const size_t sl = h->dyn_slab = local_slab_frames(nm);
-        for (const void *fn : {reinterpret_cast<const void *>(k_local_build<2>), reinterpret_cast<const void *>(k_local_build<5>),
-                               reinterpret_cast<const void *>(k_local_build<kLocalBuildTrips>)})
-            HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLocalBuildLds));
-        HIP_TRY(h, hipMalloc((void **)&h->d_dyn_cell_of, sl * nm * sizeof(uint32_t)));
-        HIP_TRY(h, hipMalloc((void **)&h->d_dyn_rec, sl * nm * 4 * sizeof(float)));
-        HIP_TRY(h, hipMalloc((void **)&h->d_dyn_count, sl * (2 * ncell + 1) * sizeof(uint32_t)));
-        HIP_TRY(h, hipMalloc((void **)&h->d_dyn_cov, sl * (size_t)(p.n_mol_total ? p.n_mol_total : 1) * sizeof(DynCov)));
-        h->dyn = true;
-    }
-
+    ST_TRY(create_dynamic_normals(h, t));
     const gorder_leaflets_t &lf = t->leaflets;
     if (lf.method != GORDER_LEAFLETS_NONE) {
-        if (lf.method > GORDER_LEAFLETS_CLUSTERING) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.method");
-        if (lf.method != GORDER_LEAFLETS_SPHERICAL && lf.method != GORDER_LEAFLETS_CLUSTERING && lf.normal_dim > 2) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.normal_dim");
-        std::vector<uint32_t> heads, mb(1, 0), ma;
-        for (uint32_t m = 0; m < t->n_molecule_types; m++) {
-            const gorder_moltype_t &mt = t->molecule_types[m];
-            if (lf.method != GORDER_LEAFLETS_MANUAL && !mt.heads)
-                return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets need heads[] per molecule type");
-            if (lf.method == GORDER_LEAFLETS_INDIVIDUAL && (!mt.methyls || mt.n_methyls == 0))
-                return fail(h, GORDER_ERR_INVALID_ARGUMENT, "individual leaflets need methyls[]");
-            for (uint32_t k = 0; k < mt.n_molecules; k++) {
-                const uint32_t hd = mt.heads ? mt.heads[k] : 0;
-                if (hd >= t->n_atoms) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "head index out of range");
-                heads.push_back(hd);
-                if (lf.method == GORDER_LEAFLETS_INDIVIDUAL)
-                    for (uint32_t q = 0; q < mt.n_methyls; q++) {
-                        const uint32_t a = mt.methyls[(size_t)k * mt.n_methyls + q];
-                        if (a >= t->n_atoms) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "methyl index out of range");
-                        ma.push_back(a);
-                    }
-                mb.push_back((uint32_t)ma.size());
-            }
-        }
-        if ((st = upload(h, &h->d_heads, heads)) != GORDER_OK) return st;
-        h->host_heads = heads;
-        if (lf.method == GORDER_LEAFLETS_LOCAL) {   // error key of a failed local centre: first slot of the molecule's type
-            std::vector<uint32_t> ms;
-            for (uint32_t m = 0; m < t->n_molecule_types; m++) ms.insert(ms.end(), t->molecule_types[m].n_molecules, p.slot0[m]);
-            if ((st = upload(h, &h->d_mol_slot0, ms)) != GORDER_OK) return st;
-        }
-        if ((st = upload(h, &h->d_methyl_begin, mb)) != GORDER_OK) return st;
-        if ((st = upload(h, &h->d_methyl_atoms, ma)) != GORDER_OK) return st;
-        if (lf.method == GORDER_LEAFLETS_LOCAL && !(lf.radius > 0.0f))
-            return fail(h, GORDER_ERR_INVALID_ARGUMENT, "local leaflets need a positive radius");
-        if (lf.method == GORDER_LEAFLETS_GLOBAL || lf.method == GORDER_LEAFLETS_LOCAL) {
-            if (!lf.membrane || lf.n_membrane == 0)
-                return fail(h, GORDER_ERR_INVALID_ARGUMENT, "global/local leaflets need the membrane group");
-            std::vector<uint32_t> mem(lf.membrane, lf.membrane + lf.n_membrane);
-            for (uint32_t a : mem)
-                if (a >= t->n_atoms) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "membrane index out of range");
-            if ((st = upload(h, &h->d_membrane, mem)) != GORDER_OK) return st;
-            h->membrane_is_frame = lf.n_membrane == t->n_atoms && !env_flag("GORDER_HIP_LEAFLETS_GENERIC");
-            for (uint32_t i = 0; i < lf.n_membrane && h->membrane_is_frame; i++) h->membrane_is_frame = mem[i] == i;
-        }
-        if (lf.method == GORDER_LEAFLETS_SPHERICAL) {
-            // leaflets.membrane is the group "ClusterHeads"; fewer than two atoms: NotEnoughAtomsToCluster (leaflets.rs:106-115)
-            if (!lf.membrane || lf.n_membrane < 2)
-                return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.n_membrane: spherical clustering needs at least two group atoms");
-            std::vector<uint32_t> grp(lf.membrane, lf.membrane + lf.n_membrane);
-            std::vector<int32_t> slot_of(t->n_atoms, -1);       // atom -> slot in the group
-            for (uint32_t i = 0; i < lf.n_membrane; i++) {
-                if (grp[i] >= t->n_atoms) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.membrane: index out of range");
-                if (slot_of[grp[i]] < 0) slot_of[grp[i]] = (int32_t)i;
-            }
-            // each molecule's head is its own atom of the group (get_reference_head, leaflets.rs:1340-1345).  The kernel needs
-            // no molecule -> slot table on the device: it recomputes the head's distance and responsibility from the atom.
-            for (uint32_t hd : heads)
-                if (slot_of[hd] < 0)
-                    return fail(h, GORDER_ERR_INVALID_ARGUMENT, "molecule_types[].heads: a head is not a member of leaflets.membrane");
-            if ((st = upload(h, &h->d_membrane, grp)) != GORDER_OK) return st;
-            // small groups: 256 threads a frame (16 atoms a thread, cheap barriers); larger ones 1024, and past
-            // 16 x 1024 atoms a scratch row per frame of a launch — at most 64 MiB, whatever the batch
-            h->sph_threads = lf.n_membrane <= 256u * (uint32_t)kSphKeep ? 256u : 1024u;
-            const uint32_t resident = h->sph_threads * (uint32_t)kSphKeep;
-            h->sph_spill = lf.n_membrane > resident ? lf.n_membrane - resident : 0u;
-            if (h->sph_spill) {
-                h->sph_slab = (uint32_t)std::min<size_t>(std::max<size_t>(((size_t)64 << 20) / (h->sph_spill * sizeof(float)), 1), 4096);
-                if (const char *ev = getenv("GORDER_HIP_SPHERICAL_SLAB"))      // (tests: frames per launch; only lowers the cap)
-                    h->sph_slab = std::min(h->sph_slab, (uint32_t)std::max(1, atoi(ev)));
-                HIP_TRY(h, hipMalloc((void **)&h->d_sph_spill, (size_t)h->sph_slab * h->sph_spill * sizeof(float)));
-            }
-            HIP_TRY(h, hipMalloc((void **)&h->d_sph_stats, 12 * sizeof(float)));
-            HIP_TRY(h, hipMemset(h->d_sph_stats, 0, 12 * sizeof(float)));
-        }
-        if (lf.method == GORDER_LEAFLETS_CLUSTERING) {
-            // leaflets.membrane is the group "ClusterHeads" (leaflets.rs:96-105: at least two atoms); the dense route holds
-            // n x (steps + 1) basis vectors a frame, hence the bound
-            if (!lf.membrane || lf.n_membrane < kClMinGroup)
-                return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.n_membrane: clustering needs at least two group atoms");
-            h->cl_cut = (t->flags & GORDER_FLAG_CLUSTER_CUTOFF) != 0;
-            if (!h->cl_cut && lf.n_membrane > kClMaxGroup)
-                return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.n_membrane: clustering takes at most 8192 group atoms");
-            if (h->cl_cut && lf.n_membrane > kClCutMaxGroup)
-                return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.n_membrane: clustering with GORDER_FLAG_CLUSTER_CUTOFF takes at most 131072 group atoms");
-            std::vector<uint32_t> grp(lf.membrane, lf.membrane + lf.n_membrane);
-            std::vector<int32_t> slot_of(t->n_atoms, -1);
-            for (uint32_t i = 0; i < lf.n_membrane; i++) {
-                if (grp[i] >= t->n_atoms) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.membrane: index out of range");
-                if (i && grp[i] <= grp[i - 1]) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "leaflets.membrane: clustering needs ascending, distinct atoms");
-                slot_of[grp[i]] = (int32_t)i;
-            }
-            std::vector<uint32_t> head_slot;
-            for (uint32_t hd : heads) {
-                if (slot_of[hd] < 0)
-                    return fail(h, GORDER_ERR_INVALID_ARGUMENT, "molecule_types[].heads: a head is not a member of leaflets.membrane");
-                head_slot.push_back((uint32_t)slot_of[hd]);
-            }
-            if ((st = upload(h, &h->d_membrane, grp)) != GORDER_OK) return st;
-            if ((st = upload(h, &h->d_cl_head_slot, head_slot)) != GORDER_OK) return st;
-            const uint32_t n = lf.n_membrane;
-            h->cl_m_max = std::min<uint32_t>(n - 1u, (uint32_t)kClMaxSteps);
-            // at most 512 MiB of scratch whatever the batch, at most 1024 frames a launch
-            h->cl_stored_w = env_flag("GORDER_HIP_CLUSTER_STORED_W");
-            h->cl_tiles = (n + kClCutTile - 1u) / kClCutTile;
-            h->cl_sort = (n + kClCutSort - 1u) / kClCutSort;
-            const size_t per_frame = h->cl_cut ? clcut_frame_bytes(n, h->cl_m_max)
-                                               : cl_frame_bytes(n, h->cl_m_max) + (h->cl_stored_w ? (size_t)n * n * 4 : 0);
-            h->cl_slab = (uint32_t)std::min<size_t>(std::max<size_t>(((size_t)512 << 20) / per_frame, 1), 1024);
-            HIP_TRY(h, hipMalloc(&h->d_cl_scratch, (size_t)h->cl_slab * per_frame));
-            HIP_TRY(h, hipMalloc((void **)&h->d_cl_carry, n));
-            HIP_TRY(h, hipMalloc((void **)&h->d_cl_is0, h->cl_slab));
-            HIP_TRY(h, hipMalloc((void **)&h->d_cl_stats, 12 * sizeof(float)));
-            HIP_TRY(h, hipMemset(h->d_cl_stats, 0, 12 * sizeof(float)));
-        }
-        // one read for global leaflets + order parameters: the tables of k_bonds_tiled<..., MOM> and k_spec_fixup
-        if (lf.method == GORDER_LEAFLETS_GLOBAL && p.spec_ok && !env_flag("GORDER_HIP_NO_SPECULATE")) {
-            std::vector<uint2> own(p.tiles.size());
-            for (size_t i = 0; i < own.size(); i++) own[i] = make_uint2(p.own[2 * i], p.own[2 * i + 1]);
-            if ((st = upload(h, &h->d_own, own)) != GORDER_OK) return st;
-            std::vector<std::vector<SpecSample>> per_mol(p.n_mol_total);
-            for (const Tile &tile : p.tiles)
-                for (uint32_t q = 0; q < tile.n_items; q++) {
-                    const Item &it = p.items[tile.item0 + q];
-                    per_mol[it.mol].push_back({tile.atom0 + it.li, tile.atom0 + it.lj, p.tile_slots[tile.slot0 + it.lslot]});
-                }
-            std::vector<uint32_t> mbeg(1, 0);
-            std::vector<SpecSample> all;
-            for (const auto &v : per_mol) { all.insert(all.end(), v.begin(), v.end()); mbeg.push_back((uint32_t)all.size()); }
-            if ((st = upload(h, &h->d_spec_mol_begin, mbeg)) != GORDER_OK) return st;
-            if ((st = upload(h, &h->d_spec_samples, all)) != GORDER_OK) return st;
-            std::vector<uint2> oh(p.own_heads.size() / 2);
-            for (size_t i = 0; i < oh.size(); i++) oh[i] = make_uint2(p.own_heads[2 * i], p.own_heads[2 * i + 1]);
-            if ((st = upload(h, &h->d_own_head_begin, p.own_head_begin)) != GORDER_OK) return st;
-            if ((st = upload(h, &h->d_own_heads, oh)) != GORDER_OK) return st;
-            HIP_TRY(h, hipMalloc((void **)&h->d_spec_counters, 4 * sizeof(uint32_t)));
-            HIP_TRY(h, hipMemset(h->d_spec_counters, 0, 4 * sizeof(uint32_t)));
-            HIP_TRY(h, hipHostMalloc((void **)&h->h_spec_counters, 2 * gorder_hip_handle::kSpecRing * sizeof(uint32_t)));
-            for (hipEvent_t &ev : h->spec_counters_copied) HIP_TRY(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            h->spec_enabled = true;
-        }
-        if (lf.method == GORDER_LEAFLETS_LOCAL) {
-            const size_t nm = lf.n_membrane, ncell = (size_t)kLocalMaxCells1D * kLocalMaxCells1D;
-            const size_t sl = h->local_slab = local_slab_frames(nm);
-            for (const void *fn : {reinterpret_cast<const void *>(k_local_build<2>), reinterpret_cast<const void *>(k_local_build<5>),
-                                   reinterpret_cast<const void *>(k_local_build<kLocalBuildTrips>)})
-                HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLocalBuildLds));
-            // rows of cells with a halo (periodic boxes, k_local_flags_rows): the first cells of a row are there twice,
-            // records included — room for twice the membrane
-            h->local_halo = t->handle_pbc && !env_flag("GORDER_HIP_LOCAL_ATOMS_ONLY");
-            h->local_rec_stride = (h->local_halo ? 2u : 1u) * nm;
-            HIP_TRY(h, hipMalloc((void **)&h->d_lcell_of, sl * nm * sizeof(uint32_t)));
-            HIP_TRY(h, hipMalloc((void **)&h->d_ltrig, sl * h->local_rec_stride * sizeof(LocalRec)));
-            HIP_TRY(h, hipMalloc((void **)&h->d_lcell_count, sl * (ncell + 1) * sizeof(uint32_t)));
-            HIP_TRY(h, hipMalloc((void **)&h->d_lcell_fill, sl * ncell * sizeof(uint32_t)));
-            HIP_TRY(h, hipMalloc((void **)&h->d_lgrid, sl * sizeof(uint4)));
-            if (h->local_halo) {    // (GORDER_HIP_LOCAL_ATOMS_ONLY, an A/B switch: every candidate atom by atom, the general passes)
-                HIP_TRY(h, hipMalloc((void **)&h->d_lrowpre, sl * (size_t)kLocalMaxCells1D * (kLocalMaxCells1D + 1u) * sizeof(LocalRowPre)));
-                HIP_TRY(h, hipMalloc((void **)&h->d_ledge, sl * (size_t)kLocalMaxCells1D * (kLocalMaxCells1D + 1u) * sizeof(LocalEdge)));
-                HIP_TRY(h, hipMalloc((void **)&h->d_lfinfo, sl * sizeof(float4)));
-                HIP_TRY(h, hipMalloc((void **)&h->d_lneed, (sl + 1) * sizeof(uint32_t)));
-                HIP_TRY(h, hipMalloc((void **)&h->d_lsummary, 2 * sizeof(uint32_t)));
-                HIP_TRY(h, hipMemset(h->d_lsummary, 0, 2 * sizeof(uint32_t)));
-                HIP_TRY(h, hipHostMalloc((void **)&h->h_lsummary, 2 * sizeof(uint32_t)));
-                h->h_lsummary[0] = h->h_lsummary[1] = 0u;
-                HIP_TRY(h, hipEventCreateWithFlags(&h->lsummary_written, hipEventDisableTiming));
-                HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_local_decide), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)kDecideLds));
-                HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_local_sums), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)kSumsLds));
-                HIP_TRY(h, hipMalloc((void **)&h->d_ltodo, (1 + sl * (size_t)(p.n_mol_total ? p.n_mol_total : 1)) * sizeof(uint2)));
-            }
-        }
-        HIP_TRY(h, hipMalloc((void **)&h->d_adist, sizeof(float) * (p.n_mol_total ? p.n_mol_total : 1)));
+        std::vector<uint32_t> heads;
+        ST_TRY(create_leaflet_tables(h, t, heads));
+        if (lf.method == GORDER_LEAFLETS_SPHERICAL) ST_TRY(create_spherical(h, t, heads));
+        if (lf.method == GORDER_LEAFLETS_CLUSTERING) ST_TRY(create_clustering(h, t, heads));
+        if (lf.method == GORDER_LEAFLETS_GLOBAL && p.spec_ok && !env_flag("GORDER_HIP_NO_SPECULATE")) ST_TRY(create_speculation(h));
+        if (lf.method == GORDER_LEAFLETS_LOCAL) ST_TRY(create_local_leaflets(h, t));
+        ST_TRY(allocate(h, h->d_adist, p.n_mol_total ? p.n_mol_total : 1));
     }
     // the memsets above ran on the null stream, which the handle's non-blocking stream does not wait for
     HIP_TRY(h, hipDeviceSynchronize());
@@ -1524,53 +1609,9 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
 void gorder_hip_destroy(gorder_hip_handle *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);      // (nothing is in flight when the buffers free themselves)
     if (h->traj_cache_free) h->traj_cache_free(h);
-    for (hipEvent_t ev : h->timing_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    (void)hipFree(h->d_mol_slot0);
-    (void)hipFree(h->d_tiles); (void)hipFree(h->d_items); (void)hipFree(h->d_tile_slots);
-    (void)hipFree(h->d_direct); (void)hipFree(h->d_err); (void)hipFree(h->d_xtc_cp);
-    (void)hipFree(h->d_ua_tiles); (void)hipFree(h->d_ua_items); (void)hipFree(h->d_ua_tile_slots);
-    (void)hipFree(h->d_map_sums); (void)hipFree(h->d_map_cnts); (void)hipFree(h->d_map_packed); (void)hipFree(h->d_tw_sums); (void)hipFree(h->d_tw_cnts);
-    (void)hipFree(h->d_twx_blocks); (void)hipFree(h->d_twx_rows); (void)hipFree(h->d_twx_totals); (void)hipFree(h->d_twx_edge); (void)hipFree(h->d_twx_groups); (void)hipFree(h->d_twx_out);
-    (void)hipFree(h->d_omx_groups); (void)hipFree(h->d_omx_out);
-    (void)hipFree(h->d_geom_group); (void)hipFree(h->d_shapes); (void)hipFree(h->d_inv_box);
-    (void)hipFree(h->d_map_rec); (void)hipFree(h->d_ua_runs); (void)hipFree(h->d_ua_run_begin);
-    (void)hipFree(h->d_runs); (void)hipFree(h->d_run_begin); (void)hipFree(h->d_items_by_slot);
-    (void)hipFree(h->d_ua_item_run); (void)hipFree(h->d_item_run); (void)hipFree(h->d_lgrid); (void)hipFree(h->d_lrowpre); (void)hipFree(h->d_ledge);
-    (void)hipFree(h->d_own); (void)hipFree(h->d_mom); (void)hipFree(h->d_head_z); (void)hipFree(h->d_own_head_begin); (void)hipFree(h->d_own_heads); (void)hipFree(h->d_spec_center); (void)hipFree(h->d_spec_ok);
-    (void)hipFree(h->d_spec_counters); (void)hipFree(h->d_spec_mol_begin); (void)hipFree(h->d_spec_samples);
-    if (h->h_spec_counters) (void)hipHostFree(h->h_spec_counters);
-    for (hipEvent_t ev : h->spec_counters_copied) if (ev) (void)hipEventDestroy(ev); (void)hipFree(h->d_lfinfo); (void)hipFree(h->d_ltodo); (void)hipFree(h->d_lneed);
-    (void)hipFree(h->d_lsummary); if (h->h_lsummary) (void)hipHostFree(h->h_lsummary); if (h->lsummary_written) (void)hipEventDestroy(h->lsummary_written);
-    (void)hipFree(h->d_dyn_cloud); (void)hipFree(h->d_dyn_heads); (void)hipFree(h->d_dyn_cell_of); (void)hipFree(h->d_dyn_count);
-    (void)hipFree(h->d_dyn_rec); (void)hipFree(h->d_dyn_normals); (void)hipFree(h->d_dyn_cov);
-    if (!h->acc_external) (void)hipFree(h->d_acc);
-    (void)hipFree(h->d_rep);
-    (void)hipFree(h->d_shell_acc); (void)hipFree(h->d_shell_rep);
-    (void)hipFree(h->d_hist_acc); (void)hipFree(h->d_hist_rep); (void)hipFree(h->d_hist_edges);
-    (void)hipFree(h->d_mol_items); (void)hipFree(h->d_mol_runs); (void)hipFree(h->d_mol_run_begin); (void)hipFree(h->d_mol_stage);
-    h->mol_store.release();
-    (void)hipFree(h->d_heads); (void)hipFree(h->d_membrane); (void)hipFree(h->d_methyl_begin);
-    (void)hipFree(h->d_methyl_atoms); (void)hipFree(h->d_aflags); (void)hipFree(h->d_adist);
-    (void)hipFree(h->d_sph_spill); (void)hipFree(h->d_sph_stats);
-    (void)hipFree(h->d_cl_scratch); (void)hipFree(h->d_cl_head_slot); (void)hipFree(h->d_cl_carry); (void)hipFree(h->d_cl_is0);
-    (void)hipFree(h->d_cl_stats);
-    (void)hipFree(h->d_arow); (void)hipFree(h->d_aframes);
-    (void)hipFree(h->d_collect_words); (void)hipFree(h->d_collect_vec); (void)hipFree(h->d_touched);
-    (void)hipFree(h->d_ltable); (void)hipFree(h->d_ntable); (void)hipFree(h->d_nrow);
-    h->collect_flags.release(); h->collect_normals.release();     // (the stream was waited for above: no copy is in flight)
-    (void)hipFree(h->d_lcell_of); (void)hipFree(h->d_lcell_count); (void)hipFree(h->d_lcell_fill);
-    (void)hipFree(h->d_ltrig);
-    for (int k = 0; k < 2; k++) {
-        (void)hipFree(h->d_stage_xyz[k]); (void)hipFree(h->d_stage_box[k]);
-        if (h->stage_copied[k]) (void)hipEventDestroy(h->stage_copied[k]);
-        if (h->stage_computed[k]) (void)hipEventDestroy(h->stage_computed[k]);
-    }
-    if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    delete h;
+    delete h;      // every member frees what it owns (device_mem.h, Event, Stream, CollectStore)
 }
 
 uint32_t gorder_hip_n_accumulators(const gorder_hip_handle *h) { return h ? h->plan.n_acc : 0; }
@@ -1777,15 +1818,7 @@ static int run_leaflets(gorder_hip_handle *h, const float *d_xyz, const float *d
                         const std::vector<uint32_t> &aframes, uint32_t row0, const uint8_t *skip = nullptr) {
     if (aframes.empty()) return GORDER_OK;
     int st;
-    const size_t cap_before = h->aframes_cap;
-    if ((st = ensure(h, &h->d_aframes, &h->aframes_cap, aframes.size())) != GORDER_OK) return st;
-    if (h->aframes_cap != cap_before) h->up_aframes_at = nullptr;      // a new allocation holds nothing yet
-    if (h->up_aframes_at != h->d_aframes || h->up_aframes != aframes) {
-        HIP_TRY(h, hipMemcpyAsync(h->d_aframes, aframes.data(), aframes.size() * sizeof(uint32_t),
-                                  hipMemcpyHostToDevice, h->stream));
-        h->up_aframes = aframes;
-        h->up_aframes_at = h->d_aframes;
-    }
+    if ((st = upload_if_changed(h, h->d_aframes, h->up_aframes, h->up_aframes_valid, aframes)) != GORDER_OK) return st;
     const gorder_leaflets_t &lf = h->tables.leaflets;
     LeafletArgs la{};
     la.xyz = d_xyz; la.box9 = d_box; la.n_atoms = h->plan.n_atoms;
@@ -1901,8 +1934,7 @@ static int run_leaflets(gorder_hip_handle *h, const float *d_xyz, const float *d
                 TIMING_MARK(h, "k_local_decide");
                 hipLaunchKernelGGL(k_local_decide, dim3(ns), dim3(1024), kDecideLds, h->stream, lo);
             }
-            const int cst = launch_cell_list(h, lo, ns, lf.n_membrane, h->d_lcell_count, ns * (ncell + 1) * sizeof(uint32_t));
-            if (cst != GORDER_OK) return cst;
+            ST_TRY(launch_cell_list(h, lo, ns, lf.n_membrane, h->d_lcell_count, ns * (ncell + 1) * sizeof(uint32_t)));
             if (lo.halo) {
                 TIMING_MARK(h, "k_local_rowprefix");
                 hipLaunchKernelGGL(k_local_rowprefix, dim3(kLocalMaxCells1D / 4u, ns), dim3(256), 0, h->stream, lo);
@@ -2045,28 +2077,19 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
     if (leaflets) {
         if (spec) std::fill(arow.begin(), arow.end(), 0u);
         const size_t rows = (ltable ? replay.expand.size() : aframes.size()) + 1;   // (a speculative batch: row 0 and every frame's exact sides)
-        if (rows > h->aflags_rows) {
-            uint8_t *nb = nullptr;
+        if (rows > h->aflags_rows) {       // grow and keep row 0: the new block is adopted once the copy is through
+            DBuf<uint8_t> nb;
             const size_t nrows = rows + rows / 4;
-            HIP_TRY(h, hipMalloc((void **)&nb, nrows * (size_t)p.n_mol_total));
+            ST_TRY(allocate(h, nb, nrows * (size_t)p.n_mol_total));
             if (h->d_aflags) {
                 // stream-ordered: the handle's stream is non-blocking, a null-stream copy would not be
                 HIP_TRY(h, hipMemcpyAsync(nb, h->d_aflags, p.n_mol_total, hipMemcpyDeviceToDevice, h->stream));
                 HIP_TRY(h, hipStreamSynchronize(h->stream));
-                HIP_TRY(h, hipFree(h->d_aflags));
             }
-            h->d_aflags = nb;
+            h->d_aflags.swap(nb);
             h->aflags_rows = nrows;
         }
-        const size_t cap_before = h->arow_cap;
-        if ((st = ensure(h, &h->d_arow, &h->arow_cap, n_frames)) != GORDER_OK) return st;
-        if (h->arow_cap != cap_before) h->up_arow_at = nullptr;        // a new allocation holds nothing yet
-        if (h->up_arow_at != h->d_arow || h->up_arow != arow) {
-            HIP_TRY(h, hipMemcpyAsync(h->d_arow, arow.data(), n_frames * sizeof(uint32_t), hipMemcpyHostToDevice,
-                                      h->stream));
-            h->up_arow = arow;
-            h->up_arow_at = h->d_arow;
-        }
+        ST_TRY(upload_if_changed(h, h->d_arow, h->up_arow, h->up_arow_valid, arow));
         if (h->collect & GORDER_COLLECT_LEAFLETS)
             for (uint32_t f : aframes) collect_frames.push_back(frame_index[f]);
         if (spec) spec_aframes = aframes;
@@ -2080,21 +2103,19 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
     if (h->extra.tw && h->n_frames + n_frames > h->tw_cap) {   // grow the per-frame rows (timewise.rs:183-186)
         const size_t row = 3 * (size_t)p.n_acc;
         const uint64_t ncap = (h->n_frames + n_frames) * 2;
-        unsigned long long *ns = nullptr, *nc = nullptr;
-        HIP_TRY(h, hipMalloc((void **)&ns, ncap * row * sizeof(unsigned long long)));
-        HIP_TRY(h, hipMalloc((void **)&nc, ncap * row * sizeof(unsigned long long)));
+        DBuf<u64> ns, nc;      // (adopted once the copies are through)
+        ST_TRY(allocate(h, ns, ncap * row));
+        ST_TRY(allocate(h, nc, ncap * row));
         // everything on the handle's own (non-blocking) stream: a null-stream memset / copy is NOT ordered
         // with the kernels that follow and left stale rows behind (seen as a wrong error estimate)
-        HIP_TRY(h, hipMemsetAsync(ns, 0, ncap * row * sizeof(unsigned long long), h->stream));
-        HIP_TRY(h, hipMemsetAsync(nc, 0, ncap * row * sizeof(unsigned long long), h->stream));
+        HIP_TRY(h, hipMemsetAsync(ns, 0, ncap * row * sizeof(u64), h->stream));
+        HIP_TRY(h, hipMemsetAsync(nc, 0, ncap * row * sizeof(u64), h->stream));
         if (h->d_tw_sums) {
-            HIP_TRY(h, hipMemcpyAsync(ns, h->d_tw_sums, h->n_frames * row * sizeof(unsigned long long), hipMemcpyDeviceToDevice, h->stream));
-            HIP_TRY(h, hipMemcpyAsync(nc, h->d_tw_cnts, h->n_frames * row * sizeof(unsigned long long), hipMemcpyDeviceToDevice, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(ns, h->d_tw_sums, h->n_frames * row * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
+            HIP_TRY(h, hipMemcpyAsync(nc, h->d_tw_cnts, h->n_frames * row * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
             HIP_TRY(h, hipStreamSynchronize(h->stream));
-            HIP_TRY(h, hipFree(h->d_tw_sums));
-            HIP_TRY(h, hipFree(h->d_tw_cnts));
         }
-        h->d_tw_sums = ns; h->d_tw_cnts = nc; h->tw_cap = ncap;
+        h->d_tw_sums.swap(ns); h->d_tw_cnts.swap(nc); h->tw_cap = ncap;
     }
     FrameArgs a{};
     a.xyz = d_xyz; a.box9 = d_box; a.n_atoms = p.n_atoms; a.n_frames = n_frames;
@@ -2105,7 +2126,7 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
     h->manual_active = false;
     if (h->manual_frames) {   // normals the host supplied for exactly this batch (arguments checked above)
         const size_t n4 = (size_t)n_frames * p.n_mol_total;
-        if ((st = ensure(h, &h->d_dyn_normals, &h->dyn_normals_cap, n4)) != GORDER_OK) return abort_batch(st);
+        if ((st = ensure(h, h->d_dyn_normals, n4)) != GORDER_OK) return abort_batch(st);
         if (hipStreamSynchronize(h->stream) != hipSuccess ||   // earlier batches may still read the buffer
             hipMemcpy(h->d_dyn_normals, h->manual_normals.data(), n4 * 4 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
             return abort_batch(fail(h, GORDER_ERR_DEVICE, "manual normals: copy to the device failed"));
@@ -2117,8 +2138,8 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
     }
     const uint32_t n_tiles_all = (uint32_t)p.tiles.size();
     if (spec) {
-        if ((st = ensure(h, &h->d_mom, &h->mom_cap, (size_t)n_frames * n_tiles_all)) != GORDER_OK) return abort_batch(st);
-        if ((st = ensure(h, &h->d_head_z, &h->head_z_cap, (size_t)n_frames * p.n_mol_total)) != GORDER_OK) return abort_batch(st);
+        if ((st = ensure(h, h->d_mom, (size_t)n_frames * n_tiles_all)) != GORDER_OK) return abort_batch(st);
+        if ((st = ensure(h, h->d_head_z, (size_t)n_frames * p.n_mol_total)) != GORDER_OK) return abort_batch(st);
         a.own = h->d_own; a.mom = h->d_mom; a.mom_dim = (int)lf.normal_dim;
         a.own_head_begin = h->d_own_head_begin; a.own_heads = h->d_own_heads; a.head_z = h->d_head_z;
     }
@@ -2126,7 +2147,7 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
     if ((h->collect & GORDER_COLLECT_NORMALS) && h->extra.geom_kind && !p.tiles.empty() && p.ua_tiles.empty()) {
         // bond systems fetch a molecule's normal after the geometry test (bond.rs:424-431): k_bonds_extras marks who did
         const size_t nt = (size_t)n_frames * p.n_mol_total;
-        if ((st = ensure(h, &h->d_touched, &h->touched_cap, nt)) != GORDER_OK) return abort_batch(st);
+        if ((st = ensure(h, h->d_touched, nt)) != GORDER_OK) return abort_batch(st);
         if (hipMemsetAsync(h->d_touched, 0, nt, h->stream) != hipSuccess) return abort_batch(fail(h, GORDER_ERR_DEVICE, "collect: hipMemsetAsync"));
         h->extra.touched = h->d_touched;
     }
@@ -2139,10 +2160,8 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
     if (spec) {
         // the exact centres from the order kernel's sums, the exact kernel for the frames they cannot vouch for, the sides
         // of every (frame, molecule) against the prediction, the mispredicted ones moved
-        size_t cap_c = h->spec_frames_cap, cap_o = h->spec_frames_cap;
-        if ((st = ensure(h, &h->d_spec_center, &cap_c, n_frames)) != GORDER_OK) return abort_batch(st);
-        if ((st = ensure(h, &h->d_spec_ok, &cap_o, n_frames)) != GORDER_OK) return abort_batch(st);
-        h->spec_frames_cap = std::min(cap_c, cap_o);
+        if ((st = ensure(h, h->d_spec_center, n_frames)) != GORDER_OK) return abort_batch(st);
+        if ((st = ensure(h, h->d_spec_ok, n_frames)) != GORDER_OK) return abort_batch(st);
         uint32_t *cnt = h->d_spec_counters + 2u * (uint32_t)(h->spec_batches & 1u);
         uint32_t *cnt_next = h->d_spec_counters + 2u * (uint32_t)((h->spec_batches + 1u) & 1u);
         SpecArgs sa{};
@@ -2222,10 +2241,10 @@ int gorder_hip_submit_host(gorder_hip_handle *h, const float *xyz, const float *
     int st;
     const size_t nx = (size_t)n_frames * h->plan.n_atoms * 3u, nb = (size_t)n_frames * 9u;
     if (!h->copy_stream) {
-        HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+        HIP_TRY(h, h->copy_stream.create());
         for (int k = 0; k < 2; k++) {
-            HIP_TRY(h, hipEventCreateWithFlags(&h->stage_copied[k], hipEventDisableTiming));
-            HIP_TRY(h, hipEventCreateWithFlags(&h->stage_computed[k], hipEventDisableTiming));
+            HIP_TRY(h, h->stage_copied[k].create());
+            HIP_TRY(h, h->stage_computed[k].create());
         }
     }
     const int b = h->stage_next;
@@ -2233,10 +2252,10 @@ int gorder_hip_submit_host(gorder_hip_handle *h, const float *xyz, const float *
     // this buffer was last read by the kernels of two calls ago (normally long finished); the kernels of the
     // previous call keep running on the other buffer while this copy is in flight
     if (h->stage_used[b]) HIP_TRY(h, hipEventSynchronize(h->stage_computed[b]));
-    if ((st = ensure(h, &h->d_stage_xyz[b], &h->stage_xyz_cap[b], nx)) != GORDER_OK) return st;
+    if ((st = ensure(h, h->d_stage_xyz[b], nx)) != GORDER_OK) return st;
     HIP_TRY(h, hipMemcpyAsync(h->d_stage_xyz[b], xyz, nx * sizeof(float), hipMemcpyHostToDevice, h->copy_stream));
     if (box) {
-        if ((st = ensure(h, &h->d_stage_box[b], &h->stage_box_cap[b], nb)) != GORDER_OK) return st;
+        if ((st = ensure(h, h->d_stage_box[b], nb)) != GORDER_OK) return st;
         HIP_TRY(h, hipMemcpyAsync(h->d_stage_box[b], box, nb * sizeof(float), hipMemcpyHostToDevice, h->copy_stream));
     }
     HIP_TRY(h, hipEventRecord(h->stage_copied[b], h->copy_stream));
@@ -2262,10 +2281,9 @@ int gorder_hip_prime_leaflets(gorder_hip_handle *h, const float *d_xyz, const fl
         HIP_TRY(h, hipGetLastError());
     }
     if (h->aflags_rows < 2) {
-        uint8_t *nb = nullptr;
-        HIP_TRY(h, hipMalloc((void **)&nb, 2 * (size_t)h->plan.n_mol_total));
-        if (h->d_aflags) HIP_TRY(h, hipFree(h->d_aflags));
-        h->d_aflags = nb;
+        DBuf<uint8_t> nb;
+        ST_TRY(allocate(h, nb, 2 * (size_t)h->plan.n_mol_total));
+        h->d_aflags.swap(nb);
         h->aflags_rows = 2;
     }
     std::vector<uint32_t> aframes(1, 0);
@@ -2291,7 +2309,7 @@ int gorder_hip_set_manual_leaflets(gorder_hip_handle *h, const uint8_t *flags, u
     std::vector<uint8_t> tmp(n);
     for (uint32_t i = 0; i < n; i++) tmp[i] = (uint8_t)((flags[i] & 1) ^ (h->tables.leaflets.flip ? 1 : 0));
     if (h->aflags_rows < 1) {
-        HIP_TRY(h, hipMalloc((void **)&h->d_aflags, 2 * (size_t)n));
+        ST_TRY(allocate(h, h->d_aflags, 2 * (size_t)n));
         h->aflags_rows = 2;
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -2379,23 +2397,20 @@ int gorder_hip_set_manual_leaflet_table(gorder_hip_handle *h, const uint8_t *fla
     if (n_rows && (!n_mol || !gorder::replay_window_ok(first_row, n_rows)))
         return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_leaflet_table: no molecules, or more than 2^32 - 1 rows");
     HIP_TRY(h, hipSetDevice(h->device));
-    unsigned long long *nt = nullptr;
+    DBuf<u64> nt;
     if (n_rows) {
         const size_t wpr = gorder::replay_flag_words(n_mol);
         std::vector<uint64_t> words((size_t)n_rows * wpr);
         for (uint64_t r = 0; r < n_rows; r++) gorder::replay_pack_flags(flags + r * (size_t)n_mol, n_mol, words.data() + r * wpr);
-        if (hipMalloc((void **)&nt, words.size() * sizeof(uint64_t)) != hipSuccess) {
+        if (!nt.alloc(words.size())) {
             (void)hipGetLastError();         // (the handle stays usable: the error is reported here, not by the next launch)
             return fail(h, GORDER_ERR_DEVICE, "gorder_hip_set_manual_leaflet_table: hipMalloc failed");
         }
-        if (hipMemcpy(nt, words.data(), words.size() * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(nt);
+        if (hipMemcpy(nt, words.data(), words.size() * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
             return fail(h, GORDER_ERR_DEVICE, "gorder_hip_set_manual_leaflet_table: copy to the device failed");
-        }
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (h->d_ltable) (void)hipFree(h->d_ltable);
-    h->d_ltable = nt;
+    h->d_ltable = std::move(nt);
     h->ltable_win.first_row = n_rows ? first_row : 0;
     h->ltable_win.n_rows = n_rows;
     // the row carried so far belongs to whatever supplied it: the next batch takes its first row from the new source
@@ -2417,21 +2432,18 @@ int gorder_hip_set_manual_normal_table(gorder_hip_handle *h, const float *normal
         if (!h->plan.direct.empty()) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "manual normals: a bond spans more than the LDS window");
     }
     HIP_TRY(h, hipSetDevice(h->device));
-    ReplayVec3 *nt = nullptr;
+    DBuf<ReplayVec3> nt;
     if (n_rows) {
-        const size_t bytes = (size_t)n_rows * n_mol * sizeof(ReplayVec3);
-        if (hipMalloc((void **)&nt, bytes) != hipSuccess) {
+        const size_t n = (size_t)n_rows * n_mol;
+        if (!nt.alloc(n)) {
             (void)hipGetLastError();
             return fail(h, GORDER_ERR_DEVICE, "gorder_hip_set_manual_normal_table: hipMalloc failed");
         }
-        if (hipMemcpy(nt, normals, bytes, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(nt);
+        if (hipMemcpy(nt, normals, n * sizeof(ReplayVec3), hipMemcpyHostToDevice) != hipSuccess)
             return fail(h, GORDER_ERR_DEVICE, "gorder_hip_set_manual_normal_table: copy to the device failed");
-        }
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (h->d_ntable) (void)hipFree(h->d_ntable);
-    h->d_ntable = nt;
+    h->d_ntable = std::move(nt);
     h->ntable_win.first_row = n_rows ? first_row : 0;
     h->ntable_win.n_rows = n_rows;
     h->ntable_step = n_rows ? step : 1;
@@ -2441,8 +2453,7 @@ int gorder_hip_set_manual_normal_table(gorder_hip_handle *h, const float *normal
 
 int gorder_hip_normals(gorder_hip_handle *h, float *normals, uint32_t *n_points) {
     if (!h || !h->dyn) return GORDER_ERR_INVALID_ARGUMENT;
-    const int st = gorder_hip_synchronize(h);
-    if (st != GORDER_OK) return st;
+    ST_TRY(gorder_hip_synchronize(h));
     const uint32_t n_mol = h->plan.n_mol_total;
     if (h->last_normals.size() < 4 * (size_t)n_mol) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "no frame submitted yet");
     for (uint32_t m = 0; m < n_mol; m++) {
@@ -2455,8 +2466,7 @@ int gorder_hip_normals(gorder_hip_handle *h, float *normals, uint32_t *n_points)
 int gorder_hip_timewise(gorder_hip_handle *h, int64_t *tw_sums, uint64_t *tw_counts, uint64_t capacity_frames) {
     if (!h || !h->extra.tw || !tw_sums || !tw_counts) return GORDER_ERR_INVALID_ARGUMENT;
     if (capacity_frames < h->n_frames) return GORDER_ERR_INVALID_ARGUMENT;
-    const int st = gorder_hip_synchronize(h);
-    if (st != GORDER_OK) return st;
+    ST_TRY(gorder_hip_synchronize(h));
     const size_t n = h->n_frames * 3 * (size_t)h->plan.n_acc;
     if (n) {
         HIP_TRY(h, hipMemcpy(tw_sums, h->d_tw_sums, n * sizeof(int64_t), hipMemcpyDeviceToHost));
@@ -2496,8 +2506,7 @@ static int tw_upload_groups(gorder_hip_handle *h, const char *who, const uint32_
     std::vector<uint32_t> csr((size_t)n_groups + 1u);
     for (uint32_t g = 0; g <= n_groups; g++) csr[g] = group_begin[g] - group_begin[0];
     csr.insert(csr.end(), slots + group_begin[0], slots + group_begin[n_groups]);
-    const int st = ensure(h, &h->d_twx_groups, &h->twx_groups_cap, csr.size());
-    if (st != GORDER_OK) return st;
+    ST_TRY(ensure(h, h->d_twx_groups, csr.size()));
     HIP_TRY(h, hipMemcpyAsync(h->d_twx_groups, csr.data(), csr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));      // (csr leaves scope)
     return GORDER_OK;
@@ -2512,7 +2521,7 @@ static int tw_blocks_device(gorder_hip_handle *h, uint32_t n_blocks, uint64_t to
     const uint64_t bs = gorder::tw_block_size(total_frames, n_blocks);
     if (block_size) *block_size = bs;
     const size_t n = (size_t)n_blocks * row_words;
-    int st = ensure(h, &h->d_twx_blocks, &h->twx_blocks_cap, 2 * n);
+    int st = ensure(h, h->d_twx_blocks, 2 * n);
     if (st != GORDER_OK) return st;
     unsigned long long *d_sums = h->d_twx_blocks, *d_cnts = h->d_twx_blocks + n;
     HIP_TRY(h, hipMemsetAsync(h->d_twx_blocks, 0, 2 * n * sizeof(unsigned long long), h->stream));
@@ -2557,11 +2566,11 @@ int gorder_hip_error_estimate(gorder_hip_handle *h, uint32_t n_blocks, const uin
     const uint32_t n_acc = h->plan.n_acc;
     const size_t n = (size_t)n_blocks * 3u * n_acc;
     if (block_sums) {            // merged blocks of several shards
-        if ((st = ensure(h, &h->d_twx_blocks, &h->twx_blocks_cap, 2 * n)) != GORDER_OK) return st;
+        if ((st = ensure(h, h->d_twx_blocks, 2 * n)) != GORDER_OK) return st;
         HIP_TRY(h, hipMemcpyAsync(h->d_twx_blocks, block_sums, n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipMemcpyAsync(h->d_twx_blocks + n, block_counts, n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
     } else if ((st = tw_blocks_device(h, n_blocks, h->n_frames, 0, nullptr)) != GORDER_OK) return st;
-    if ((st = ensure(h, &h->d_twx_out, &h->twx_out_cap, (size_t)n_groups * 3u)) != GORDER_OK) return st;
+    if ((st = ensure(h, h->d_twx_out, (size_t)n_groups * 3u)) != GORDER_OK) return st;
     TIMING_MARK(h, "k_tw_errors");
     hipLaunchKernelGGL(k_tw_errors, dim3(n_groups * 3u), dim3(64), 0, h->stream, h->d_twx_blocks, h->d_twx_blocks + n, n_blocks, n_acc,
                        h->d_twx_groups, h->d_twx_groups + n_groups + 1u, h->d_twx_out);
@@ -2592,10 +2601,10 @@ int gorder_hip_convergence(gorder_hip_handle *h, const uint32_t *group_begin, co
     if (!prefix) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_convergence: null output");
     const uint64_t n_chunks = gorder::tw_n_chunks(n_frames);
     const size_t n_rows = (size_t)n_frames * n_cols, n_tot = (size_t)n_chunks * n_cols;
-    if ((st = ensure(h, &h->d_twx_rows, &h->twx_rows_cap, 2 * n_rows)) != GORDER_OK) return st;
-    if ((st = ensure(h, &h->d_twx_totals, &h->twx_totals_cap, 2 * n_tot)) != GORDER_OK) return st;
-    if ((st = ensure(h, &h->d_twx_edge, &h->twx_edge_cap, 4 * (size_t)n_cols)) != GORDER_OK) return st;
-    if ((st = ensure(h, &h->d_twx_out, &h->twx_out_cap, n_rows)) != GORDER_OK) return st;
+    if ((st = ensure(h, h->d_twx_rows, 2 * n_rows)) != GORDER_OK) return st;
+    if ((st = ensure(h, h->d_twx_totals, 2 * n_tot)) != GORDER_OK) return st;
+    if ((st = ensure(h, h->d_twx_edge, 4 * (size_t)n_cols)) != GORDER_OK) return st;
+    if ((st = ensure(h, h->d_twx_out, n_rows)) != GORDER_OK) return st;
     unsigned long long *d_rs = h->d_twx_rows, *d_rc = d_rs + n_rows, *d_ts = h->d_twx_totals, *d_tc = d_ts + n_tot;
     unsigned long long *d_cs = nullptr, *d_cc = nullptr, *d_es = h->d_twx_edge + 2 * (size_t)n_cols, *d_ec = d_es + n_cols;
     if (carry_sums) {
@@ -2656,9 +2665,9 @@ int gorder_hip_ordermaps(gorder_hip_handle *h, const uint32_t *group_begin, cons
     std::vector<uint32_t> csr((size_t)n_groups + 1u);
     for (uint32_t g = 0; g <= n_groups; g++) csr[g] = group_begin[g] - group_begin[0];
     csr.insert(csr.end(), slots + group_begin[0], slots + group_begin[n_groups]);
-    if ((st = ensure(h, &h->d_omx_groups, &h->omx_groups_cap, csr.size())) != GORDER_OK) return st;
+    if ((st = ensure(h, h->d_omx_groups, csr.size())) != GORDER_OK) return st;
     const size_t n_out = (size_t)n_groups * 3u * n_tiles;
-    if ((st = ensure(h, &h->d_omx_out, &h->omx_out_cap, n_out)) != GORDER_OK) return st;
+    if ((st = ensure(h, h->d_omx_out, n_out)) != GORDER_OK) return st;
     HIP_TRY(h, hipMemcpyAsync(h->d_omx_groups, csr.data(), csr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     TIMING_MARK(h, "k_map_finalise");
     hipLaunchKernelGGL(k_map_finalise, dim3((uint32_t)n_blocks), dim3(256), 0, h->stream,
@@ -2675,8 +2684,7 @@ int gorder_hip_ordermaps(gorder_hip_handle *h, const uint32_t *group_begin, cons
 int gorder_hip_leaflets(gorder_hip_handle *h, uint8_t *flags, uint64_t *assignment_frame) {
     if (!h) return GORDER_ERR_INVALID_ARGUMENT;
     if (!h->have_assignment) return GORDER_ERR_LEAFLETS_NOT_PRIMED;
-    const int st = gorder_hip_synchronize(h);
-    if (st != GORDER_OK) return st;
+    ST_TRY(gorder_hip_synchronize(h));
     if (flags) HIP_TRY(h, hipMemcpy(flags, h->d_aflags, h->plan.n_mol_total, hipMemcpyDeviceToHost));
     if (assignment_frame) *assignment_frame = h->assignment_frame;
     return GORDER_OK;
@@ -2694,7 +2702,7 @@ int gorder_hip_set_collect(gorder_hip_handle *h, uint32_t what) {
         return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_collect: normals are collected for dynamic membrane normals only");
     if (what && !h->plan.n_mol_total) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_collect: no molecules");
     HIP_TRY(h, hipSetDevice(h->device));
-    const gorder::CollectAlloc pinned{collect_host_alloc, collect_host_free};
+    const gorder::CollectAlloc pinned{PinnedMem::alloc, PinnedMem::release};
     if ((what & GORDER_COLLECT_LEAFLETS) && !h->collect_flags.configured())
         h->collect_flags.configure(gorder::collect_flag_words(h->plan.n_mol_total) * sizeof(uint64_t), pinned);
     if ((what & GORDER_COLLECT_NORMALS) && !h->collect_normals.configured())
@@ -2745,23 +2753,14 @@ int gorder_hip_set_radial_shells(gorder_hip_handle *h, const float *radii, uint3
             return refuse("the last radius is not tables.geometry.radius");
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, hipStreamSynchronize(h->stream));       // (a reset still queued may be zeroing the old blocks)
-        (void)hipFree(h->d_shell_acc); (void)hipFree(h->d_shell_rep);
-        h->d_shell_acc = h->d_shell_rep = nullptr;
         h->n_shells = 0;
-        // replicas against contention on the global shell words, as the ordinary sums have them; fewer where the block would pass 64 MiB
-        const size_t words = (size_t)n_radii * 4u * p.n_acc;
-        uint32_t n_rep = h->n_rep;
-        while (n_rep > 1 && (size_t)n_rep * words * sizeof(unsigned long long) > ((size_t)64 << 20)) n_rep /= 2;
-        HIP_TRY(h, hipMalloc((void **)&h->d_shell_acc, words * sizeof(unsigned long long)));
-        HIP_TRY(h, hipMalloc((void **)&h->d_shell_rep, (size_t)n_rep * words * sizeof(unsigned long long)));
-        HIP_TRY(h, hipMemset(h->d_shell_acc, 0, words * sizeof(unsigned long long)));
-        HIP_TRY(h, hipMemset(h->d_shell_rep, 0, (size_t)n_rep * words * sizeof(unsigned long long)));
+        // replicas against contention on the global shell words, as the ordinary sums have them (gorder::replica_count)
+        ST_TRY(alloc_zeroed(h, h->shells, (size_t)n_radii * 4u * p.n_acc));
         uint32_t max_slots = 1;
         for (const Tile &tile : p.tiles) max_slots = std::max(max_slots, tile.n_slots);
         const uint32_t planes = t.leaflets.method != GORDER_LEAFLETS_NONE ? 2u : 1u;
         h->shell_lds_bytes = (size_t)planes * n_radii * max_slots * sizeof(unsigned long long);
         h->shell_direct = h->shell_force_direct || h->shell_lds_bytes > 64u * 1024u;
-        h->shell_rep = n_rep;
         for (uint32_t k = 0; k < n_radii; k++) h->shell_thr[k] = thr[k];
         h->n_shells = n_radii;
         return GORDER_OK;
@@ -2769,8 +2768,7 @@ int gorder_hip_set_radial_shells(gorder_hip_handle *h, const float *radii, uint3
     if (h->n_shells) {
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        (void)hipFree(h->d_shell_acc); (void)hipFree(h->d_shell_rep);
-        h->d_shell_acc = h->d_shell_rep = nullptr;
+        h->shells.reset();
         h->n_shells = 0;
     }
     return GORDER_OK;
@@ -2782,14 +2780,10 @@ int gorder_hip_radial_shells(gorder_hip_handle *h, int64_t *sums, uint64_t *coun
     if (!h->n_shells) return GORDER_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     const uint32_t n = h->plan.n_acc;
-    const size_t words = (size_t)h->n_shells * 4u * n;
-    hipLaunchKernelGGL(k_fold_replicas, dim3((uint32_t)((words + 255) / 256)), dim3(256), 0, h->stream, h->d_shell_acc, h->d_shell_rep,
-                       h->shell_rep, (uint32_t)words);
-    HIP_TRY(h, hipGetLastError());
-    const int st = gorder_hip_synchronize(h);
-    if (st != GORDER_OK) return st;
-    std::vector<unsigned long long> raw(words);
-    HIP_TRY(h, hipMemcpy(raw.data(), h->d_shell_acc, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIP_TRY(h, h->shells.fold(h->stream));
+    ST_TRY(gorder_hip_synchronize(h));
+    std::vector<unsigned long long> raw(h->shells.words);
+    HIP_TRY(h, hipMemcpy(raw.data(), h->shells.acc, raw.size() * sizeof(u64), hipMemcpyDeviceToHost));
     const bool lf = h->tables.leaflets.method != GORDER_LEAFLETS_NONE;
     for (uint32_t k = 0; k < h->n_shells; k++) {
         const unsigned long long *r = raw.data() + (size_t)k * 4u * n;
@@ -2826,27 +2820,19 @@ int gorder_hip_set_order_histogram(gorder_hip_handle *h, const int32_t *edges, u
     }
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));       // (a reset still queued may be zeroing the old blocks)
-    (void)hipFree(h->d_hist_acc); (void)hipFree(h->d_hist_rep); (void)hipFree(h->d_hist_edges);
-    h->d_hist_acc = h->d_hist_rep = nullptr; h->d_hist_edges = nullptr;
+    h->hist.reset();
+    h->d_hist_edges.reset();
     h->hist_edges = 0;
     if (!n_edges) return GORDER_OK;
-    // replicas against contention on the global words, as the ordinary sums have them; fewer where the block would pass 64 MiB
+    // replicas against contention on the global words, as the ordinary sums have them (gorder::replica_count)
     const uint32_t n_bins = n_edges - 1u;
-    const size_t words = (size_t)n_bins * 2u * p.n_acc;
-    uint32_t n_rep = h->n_rep;
-    while (n_rep > 1 && (size_t)n_rep * words * sizeof(unsigned long long) > ((size_t)64 << 20)) n_rep /= 2;
-    HIP_TRY(h, hipMalloc((void **)&h->d_hist_edges, n_edges * sizeof(int32_t)));
-    HIP_TRY(h, hipMalloc((void **)&h->d_hist_acc, words * sizeof(unsigned long long)));
-    HIP_TRY(h, hipMalloc((void **)&h->d_hist_rep, (size_t)n_rep * words * sizeof(unsigned long long)));
-    HIP_TRY(h, hipMemcpy(h->d_hist_edges, edges, n_edges * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemset(h->d_hist_acc, 0, words * sizeof(unsigned long long)));
-    HIP_TRY(h, hipMemset(h->d_hist_rep, 0, (size_t)n_rep * words * sizeof(unsigned long long)));
+    ST_TRY(upload(h, h->d_hist_edges, std::vector<int32_t>(edges, edges + n_edges)));
+    ST_TRY(alloc_zeroed(h, h->hist, (size_t)n_bins * 2u * p.n_acc));
     uint32_t max_slots = 1;
     for (const Tile &tile : p.tiles) max_slots = std::max(max_slots, tile.n_slots);
     const uint32_t planes = h->tables.leaflets.method != GORDER_LEAFLETS_NONE ? 2u : 1u;
     h->hist_table_words = (size_t)planes * n_bins * max_slots;
     h->hist_direct = h->hist_force_direct || kDistEdgeBytes + h->hist_table_words * sizeof(uint32_t) > 64u * 1024u;
-    h->hist_rep = n_rep;
     h->hist_edges = n_edges;
     return GORDER_OK;
 }
@@ -2858,15 +2844,11 @@ int gorder_hip_order_histogram(gorder_hip_handle *h, uint64_t *counts, uint32_t 
     if (!nb) return GORDER_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     const uint32_t n = h->plan.n_acc;
-    const size_t words = (size_t)nb * 2u * n;
-    hipLaunchKernelGGL(k_fold_replicas, dim3((uint32_t)((words + 255) / 256)), dim3(256), 0, h->stream, h->d_hist_acc, h->d_hist_rep,
-                       h->hist_rep, (uint32_t)words);
-    HIP_TRY(h, hipGetLastError());
-    const int st = gorder_hip_synchronize(h);
-    if (st != GORDER_OK) return st;
+    HIP_TRY(h, h->hist.fold(h->stream));
+    ST_TRY(gorder_hip_synchronize(h));
     if (!counts) return GORDER_OK;
-    std::vector<unsigned long long> raw(words);
-    HIP_TRY(h, hipMemcpy(raw.data(), h->d_hist_acc, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    std::vector<unsigned long long> raw(h->hist.words);
+    HIP_TRY(h, hipMemcpy(raw.data(), h->hist.acc, raw.size() * sizeof(u64), hipMemcpyDeviceToHost));
     const bool lf = h->tables.leaflets.method != GORDER_LEAFLETS_NONE;
     for (uint32_t k = 0; k < nb; k++) {
         const unsigned long long *r = raw.data() + (size_t)k * 2u * n;
@@ -2906,18 +2888,17 @@ int gorder_hip_set_molecule_rows(gorder_hip_handle *h, const uint32_t *group_beg
     }
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));       // (copies of a run before the reset may still be writing the chunks)
-    (void)hipFree(h->d_mol_items); (void)hipFree(h->d_mol_runs); (void)hipFree(h->d_mol_run_begin);
-    h->d_mol_items = nullptr; h->d_mol_runs = nullptr; h->d_mol_run_begin = nullptr;
+    h->d_mol_items.reset(); h->d_mol_runs.reset(); h->d_mol_run_begin.reset();
     h->mol = gorder::MolRows();
     h->mol_store.release();
     h->mol_failed = false;
     h->mol_batch_log.clear();
     if (!n_groups) return GORDER_OK;
     int st;
-    if ((st = upload(h, &h->d_mol_items, mol.items)) != GORDER_OK) return st;
-    if ((st = upload(h, &h->d_mol_runs, mol.runs)) != GORDER_OK) return st;
-    if ((st = upload(h, &h->d_mol_run_begin, mol.run_begin)) != GORDER_OK) return st;
-    h->mol_store.configure((size_t)n_groups * p.n_mol_total * sizeof(uint64_t), gorder::CollectAlloc{collect_host_alloc, collect_host_free});
+    if ((st = upload(h, h->d_mol_items, mol.items)) != GORDER_OK) return st;
+    if ((st = upload(h, h->d_mol_runs, mol.runs)) != GORDER_OK) return st;
+    if ((st = upload(h, h->d_mol_run_begin, mol.run_begin)) != GORDER_OK) return st;
+    h->mol_store.configure((size_t)n_groups * p.n_mol_total * sizeof(uint64_t), gorder::CollectAlloc{PinnedMem::alloc, PinnedMem::release});
     h->mol = std::move(mol);
     return GORDER_OK;
 }
@@ -2993,8 +2974,7 @@ int gorder_hip_collected_normals(gorder_hip_handle *h, float *normals, uint64_t 
     const gorder::CollectStore &store = h->collect_normals;
     *n_rows = store.n_rows();
     if ((normals || frames) && capacity_rows < store.n_rows()) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_collected_normals: capacity_rows is too small");
-    const int st = gorder_hip_synchronize(h);
-    if (st != GORDER_OK) return st;
+    ST_TRY(gorder_hip_synchronize(h));
     const size_t row_floats = (size_t)h->plan.n_mol_total * 3u;
     if (normals)
         store.for_each_row([&](uint64_t r, const void *row) { memcpy(normals + r * row_floats, row, row_floats * sizeof(float)); });
@@ -3004,8 +2984,7 @@ int gorder_hip_collected_normals(gorder_hip_handle *h, float *normals, uint64_t 
 
 int gorder_hip_leaflet_distances(gorder_hip_handle *h, float *dist) {
     if (!h || !dist || !h->d_adist) return GORDER_ERR_INVALID_ARGUMENT;
-    const int st = gorder_hip_synchronize(h);
-    if (st != GORDER_OK) return st;
+    ST_TRY(gorder_hip_synchronize(h));
     HIP_TRY(h, hipMemcpy(dist, h->d_adist, sizeof(float) * h->plan.n_mol_total, hipMemcpyDeviceToHost));
     return GORDER_OK;
 }
@@ -3013,8 +2992,7 @@ int gorder_hip_leaflet_distances(gorder_hip_handle *h, float *dist) {
 int gorder_hip_spherical_stats(gorder_hip_handle *h, float out[12]) {
     if (!h || !out || h->tables.leaflets.method != GORDER_LEAFLETS_SPHERICAL || !h->d_sph_stats) return GORDER_ERR_INVALID_ARGUMENT;
     if (!h->have_assignment) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_spherical_stats: no assignment frame yet");
-    const int st = gorder_hip_synchronize(h);
-    if (st != GORDER_OK) return st;
+    ST_TRY(gorder_hip_synchronize(h));
     HIP_TRY(h, hipMemcpy(out, h->d_sph_stats, 12 * sizeof(float), hipMemcpyDeviceToHost));
     return GORDER_OK;
 }
@@ -3022,8 +3000,7 @@ int gorder_hip_spherical_stats(gorder_hip_handle *h, float out[12]) {
 int gorder_hip_clustering_stats(gorder_hip_handle *h, float out[12]) {
     if (!h || !out || h->tables.leaflets.method != GORDER_LEAFLETS_CLUSTERING || !h->d_cl_stats) return GORDER_ERR_INVALID_ARGUMENT;
     if (!h->have_assignment) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_clustering_stats: no assignment frame yet");
-    const int st = gorder_hip_synchronize(h);
-    if (st != GORDER_OK) return st;
+    ST_TRY(gorder_hip_synchronize(h));
     HIP_TRY(h, hipMemcpy(out, h->d_cl_stats, 12 * sizeof(float), hipMemcpyDeviceToHost));
     return GORDER_OK;
 }
@@ -3031,10 +3008,7 @@ int gorder_hip_clustering_stats(gorder_hip_handle *h, float out[12]) {
 int gorder_hip_accumulators_device(gorder_hip_handle *h, void **d_ptr, uint64_t *n_u64) {
     if (!h || !d_ptr || !n_u64) return GORDER_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
-    {   // the packed block must be complete before a collective reads it (stream-ordered)
-        const int st = fold_replicas(h);
-        if (st != GORDER_OK) return st;
-    }
+    ST_TRY(fold_replicas(h));      // the packed block must be complete before a collective reads it (stream-ordered)
     *d_ptr = h->d_acc;
     *n_u64 = h->acc_words;
     return GORDER_OK;
@@ -3045,8 +3019,7 @@ int gorder_hip_export_maps(gorder_hip_handle *h, void *d_sums, void *d_counts, u
     const uint64_t n = 3ull * h->plan.n_acc * h->map_nx * h->map_ny;
     if (n_u64 < n) return GORDER_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
-    const int st = fold_maps(h);
-    if (st != GORDER_OK) return st;
+    ST_TRY(fold_maps(h));
     HIP_TRY(h, hipMemcpyAsync(d_sums, h->d_map_sums, n * sizeof(unsigned long long), hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(d_counts, h->d_map_cnts, n * sizeof(unsigned long long), hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -3056,15 +3029,11 @@ int gorder_hip_export_maps(gorder_hip_handle *h, void *d_sums, void *d_counts, u
 int gorder_hip_bind_accumulators(gorder_hip_handle *h, void *d_ptr, uint64_t n_u64) {
     if (!h || !d_ptr || n_u64 < h->acc_words || ((uintptr_t)d_ptr & 7u)) return GORDER_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
-    {
-        const int st = fold_replicas(h);
-        if (st != GORDER_OK) return st;
-    }
+    ST_TRY(fold_replicas(h));
     HIP_TRY(h, hipMemcpyAsync(d_ptr, h->d_acc, h->acc_words * sizeof(unsigned long long), hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (!h->acc_external) HIP_TRY(h, hipFree(h->d_acc));
+    h->own_acc.reset();
     h->d_acc = (unsigned long long *)d_ptr;
-    h->acc_external = true;
     return GORDER_OK;
 }
 
@@ -3076,16 +3045,8 @@ int gorder_hip_reset(gorder_hip_handle *h) {
     HIP_TRY(h, hipMemsetAsync(h->d_acc, 0, h->acc_words * sizeof(unsigned long long), h->stream));
     if (h->d_rep) HIP_TRY(h, hipMemsetAsync(h->d_rep, 0, (size_t)h->n_rep * 4u * p.n_acc * sizeof(unsigned long long), h->stream));
     h->rep_dirty = false;
-    if (h->n_shells) {      // (the radii stay)
-        const size_t words = (size_t)h->n_shells * 4u * p.n_acc;
-        HIP_TRY(h, hipMemsetAsync(h->d_shell_acc, 0, words * sizeof(unsigned long long), h->stream));
-        HIP_TRY(h, hipMemsetAsync(h->d_shell_rep, 0, (size_t)h->shell_rep * words * sizeof(unsigned long long), h->stream));
-    }
-    if (h->hist_edges) {    // (the edges stay)
-        const size_t words = (size_t)(h->hist_edges - 1u) * 2u * p.n_acc;
-        HIP_TRY(h, hipMemsetAsync(h->d_hist_acc, 0, words * sizeof(unsigned long long), h->stream));
-        HIP_TRY(h, hipMemsetAsync(h->d_hist_rep, 0, (size_t)h->hist_rep * words * sizeof(unsigned long long), h->stream));
-    }
+    if (h->n_shells) HIP_TRY(h, h->shells.zero_async(h->stream));       // (the radii stay)
+    if (h->hist_edges) HIP_TRY(h, h->hist.zero_async(h->stream));      // (the edges stay)
     if (h->extra.maps) {
         const size_t nmap = 3 * (size_t)p.n_acc * h->map_nx * h->map_ny;
         const size_t npk = (h->tables.leaflets.method != GORDER_LEAFLETS_NONE ? 2 : 1) * (nmap / 3);
@@ -3200,8 +3161,7 @@ int gorder_hip_kernel_time(gorder_hip_handle *h, double *ms, uint64_t *launches,
     HIP_TRY(h, hipSetDevice(h->device));
     h->timing_on = true;   // the first call switches the events on (submits before it are not timed)
     while (!h->timing_pending.empty()) {
-        const int st = timing_drain_oldest(h);
-        if (st != GORDER_OK) return st;
+        ST_TRY(timing_drain_oldest(h));
     }
     double total = 0.0;
     for (double v : h->timing_label_ms) total += v;
@@ -3220,8 +3180,7 @@ int gorder_hip_kernel_time_group(gorder_hip_handle *h, uint32_t index, const cha
     if (!h) return GORDER_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
     while (!h->timing_pending.empty()) {
-        const int st = timing_drain_oldest(h);
-        if (st != GORDER_OK) return st;
+        ST_TRY(timing_drain_oldest(h));
     }
     if (index >= h->timing_labels.size()) return GORDER_ERR_INVALID_ARGUMENT;
     if (name) *name = h->timing_labels[index].c_str();
@@ -3258,8 +3217,7 @@ int xtc_decode_on(gorder_hip_handle *h, hipStream_t stream, const uint8_t *d_blo
         // caller's buffer (a slot of gorder_hip_run_trajectory has its own: several batches decode at once) or the handle's.
         const uint32_t n_chunks = (std::max(n_stop, 1u) + kXtcChunk - 1u) / kXtcChunk;
         if (!d_cp) {
-            const int st = ensure(h, &h->d_xtc_cp, &h->xtc_cp_cap, xtc_checkpoints(n_frames, n_stop));
-            if (st != GORDER_OK) return st;
+            ST_TRY(ensure(h, h->d_xtc_cp, xtc_checkpoints(n_frames, n_stop)));
             d_cp = h->d_xtc_cp;
         }
         hipLaunchKernelGGL(k_xtc_scan, dim3((n_frames + 3u) / 4u), dim3(256), 0, stream, d_blob, (unsigned long long)blob_bytes,

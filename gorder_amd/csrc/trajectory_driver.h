@@ -31,24 +31,27 @@
 namespace {
 
 struct TrajSlot {
-    float *h_xyz = nullptr, *h_box = nullptr, *h_time = nullptr;   // pinned
-    float *d_xyz = nullptr, *d_box = nullptr;
+    HBuf<float> h_xyz, h_box, h_time;   // pinned
+    DBuf<float> d_xyz, d_box;
     // device decode: the compressed blocks and their table, pinned and on the device, and the slot's own stream
-    uint8_t *h_blob = nullptr, *d_blob = nullptr;
-    gorder_xtc_frame_t *h_frames = nullptr, *d_frames = nullptr;
-    float *d_box_in = nullptr;      // the boxes land here first: d_box may still be read by the kernels of the slot's last batch
+    HBuf<uint8_t> h_blob;
+    DBuf<uint8_t> d_blob;
+    HBuf<gorder_xtc_frame_t> h_frames;
+    DBuf<gorder_xtc_frame_t> d_frames;
+    DBuf<float> d_box_in;           // the boxes land here first: d_box may still be read by the kernels of the slot's last batch
     // what the decoder reports back (2 words: short frames, largest need in 2^-16 of the bytes given; then the list of
     // the short frames), on the device and pinned; where every frame of the batch lies in which file
-    uint32_t *d_stat = nullptr, *d_short = nullptr, *h_stat = nullptr, *h_short = nullptr;
-    XtcCheckpoint *d_cp = nullptr;   // where the chunks of the batch's frames start (between the decoder's two kernels)
+    DBuf<uint32_t> d_stat, d_short;
+    HBuf<uint32_t> h_stat, h_short;
+    DBuf<XtcCheckpoint> d_cp;        // where the chunks of the batch's frames start (between the decoder's two kernels)
     std::vector<int64_t> file_pos;
     std::vector<uint32_t> file_idx;
     uint32_t prefix_q16 = 65536;    // the part of every block this batch was packed with
     uint32_t kinds = 0;             // what the batch's table holds (kXtcTableXtc | kXtcTableTrr)
     size_t moved = 0;               // bytes copied to the device for this batch
     uint64_t blob_bytes = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t staged = nullptr, copied = nullptr, computed = nullptr;   // host buffers read; device buffers ready; kernels done
+    Stream stream;
+    Event staged, copied, computed;      // host buffers read; device buffers ready; kernels done
     bool copy_issued = false, compute_issued = false;
     uint32_t n = 0;
     std::vector<uint64_t> fidx;
@@ -62,9 +65,9 @@ struct TrajCache {
     bool dev = false, has_xtc = false;
     uint32_t batch = 0, n_stop = 0;
     size_t blob_cap = 0, xyz_bytes = 0;
-    hipStream_t copy_stream = nullptr;
-    unsigned long long *h_err = nullptr;     // pinned mirror of the device error key
-    float *h_fix = nullptr;                  // pinned: one frame + its box, for the frames the host decodes after all
+    Stream copy_stream;
+    HBuf<u64> h_err;                         // pinned mirror of the device error key
+    HBuf<float> h_fix;                       // pinned: one frame + its box, for the frames the host decodes after all
 };
 
 struct TrajPipe {
@@ -87,33 +90,7 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
 }
 
 void traj_cache_free(gorder_hip_handle *h) {
-    TrajCache *c = static_cast<TrajCache *>(h->traj_cache);
-    if (!c) return;
-    for (TrajSlot &s : c->slot) {
-        if (s.h_xyz) (void)hipHostFree(s.h_xyz);
-        if (s.h_box) (void)hipHostFree(s.h_box);
-        if (s.h_time) (void)hipHostFree(s.h_time);
-        if (s.h_blob) (void)hipHostFree(s.h_blob);
-        if (s.h_frames) (void)hipHostFree(s.h_frames);
-        (void)hipFree(s.d_xyz);
-        (void)hipFree(s.d_box);
-        (void)hipFree(s.d_blob);
-        (void)hipFree(s.d_frames);
-        (void)hipFree(s.d_box_in);
-        (void)hipFree(s.d_stat);
-        (void)hipFree(s.d_short);
-        (void)hipFree(s.d_cp);
-        if (s.h_stat) (void)hipHostFree(s.h_stat);
-        if (s.h_short) (void)hipHostFree(s.h_short);
-        if (s.stream) (void)hipStreamDestroy(s.stream);
-        if (s.staged) (void)hipEventDestroy(s.staged);
-        if (s.copied) (void)hipEventDestroy(s.copied);
-        if (s.computed) (void)hipEventDestroy(s.computed);
-    }
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    if (c->h_err) (void)hipHostFree(c->h_err);
-    if (c->h_fix) (void)hipHostFree(c->h_fix);
-    delete c;
+    delete static_cast<TrajCache *>(h->traj_cache);      // (the slots' members free what they own)
     h->traj_cache = nullptr;
 }
 
@@ -231,17 +208,13 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
                 if (sk < 0) break;
             }
             if (got != 1) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "cannot read the leaflet assignment frame that precedes this shard");
-            float *d_x = nullptr, *d_b = nullptr;
-            hipError_t e = hipMalloc((void **)&d_x, x.size() * sizeof(float));
-            if (e == hipSuccess) e = hipMalloc((void **)&d_b, 9 * sizeof(float));
+            DBuf<float> d_x, d_b;
+            hipError_t e = d_x.alloc(x.size()) && d_b.alloc(9) ? hipSuccess : hipErrorOutOfMemory;
             if (e == hipSuccess) e = hipMemcpy(d_x, x.data(), x.size() * sizeof(float), hipMemcpyHostToDevice);
             if (e == hipSuccess) e = hipMemcpy(d_b, bx.data(), 9 * sizeof(float), hipMemcpyHostToDevice);
-            int st = e == hipSuccess ? gorder_hip_prime_leaflets(h, d_x, h->tables.handle_pbc ? d_b : nullptr, f_assign)
-                                     : fail(h, GORDER_ERR_DEVICE, std::string("priming frame: ") + hipGetErrorString(e));
-            if (st == GORDER_OK) st = gorder_hip_synchronize(h);       // (the buffers go away below)
-            (void)hipFree(d_x);
-            (void)hipFree(d_b);
-            if (st != GORDER_OK) return st;
+            if (e != hipSuccess) return fail(h, GORDER_ERR_DEVICE, std::string("priming frame: ") + hipGetErrorString(e));
+            ST_TRY(gorder_hip_prime_leaflets(h, d_x, h->tables.handle_pbc ? d_b.get() : nullptr, f_assign));
+            ST_TRY(gorder_hip_synchronize(h));       // (the buffers go away with this scope)
         }
     }
     // frames per batch: ~128 MB of coordinates per slot unless the host asks otherwise (>= 16 so that the launches
@@ -269,7 +242,7 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
         }
     }
     if (batch == 0) batch = (uint32_t)std::min<size_t>(4096, std::max<size_t>(16, ((size_t)128 << 20) / ((size_t)n_atoms * 12u)));
-    const size_t xyz_bytes = (size_t)batch * n_atoms * 3u * sizeof(float), box_bytes = (size_t)batch * 9u * sizeof(float);
+    const size_t xyz_bytes = (size_t)batch * n_atoms * 3u * sizeof(float);
     // a compressed atom takes 3-5 bytes at the usual precision, never more than 10: 6 per atom and frame on average,
     // and room for one worst-case frame
     // (a file with much more in it than the analysed atoms — water — would ask for gigabytes: at most 1 GiB per slot,
@@ -296,56 +269,36 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
     TrajPipe pipe;
     pipe.slot = cache->slot;
     for (int k = 0; k < TrajPipe::kSlots; k++) { pipe.slot[k].copy_issued = pipe.slot[k].compute_issued = false; }   // (the last run ended synchronised)
-    int32_t *d_slot_of = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_slot_of); };
-#define TRAJ_TRY(expr)                                                                              \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) {                                                                     \
-            cleanup();                                                                              \
-            return fail(h, GORDER_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-        }                                                                                           \
-    } while (0)
-    if (!cache->copy_stream) TRAJ_TRY(hipStreamCreateWithFlags(&cache->copy_stream, hipStreamNonBlocking));
-    if (!cache->h_err) TRAJ_TRY(hipHostMalloc((void **)&cache->h_err, sizeof(unsigned long long), hipHostMallocDefault));
-    if (dev && !cache->h_fix) TRAJ_TRY(hipHostMalloc((void **)&cache->h_fix, ((size_t)n_atoms * 3u + 9u) * sizeof(float), hipHostMallocDefault));
+    DBuf<int32_t> d_slot_of;
+    HIP_TRY(h, cache->copy_stream.create());
+    if (!cache->h_err) ST_TRY(allocate(h, cache->h_err, 1));
+    if (dev && !cache->h_fix) ST_TRY(allocate(h, cache->h_fix, (size_t)n_atoms * 3u + 9u));
     const hipStream_t copy_stream = cache->copy_stream;
     unsigned long long *h_err = cache->h_err;   // lets the loop stop at the first error
     *h_err = kErrNone;
-    if (dev && !slot_of.empty()) {
-        TRAJ_TRY(hipMalloc((void **)&d_slot_of, slot_of.size() * sizeof(int32_t)));
-        TRAJ_TRY(hipMemcpy(d_slot_of, slot_of.data(), slot_of.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
+    if (dev && !slot_of.empty()) ST_TRY(upload(h, d_slot_of, slot_of));
     // Pinning a gigabyte takes tens of milliseconds: only the first slot's share of that stands before the first frame
     // is read, the other slots are made ready by a thread of their own.
     auto alloc_slot = [&](TrajSlot &s) -> hipError_t {
         if (s.computed) return hipSuccess;           // kept from an earlier call
-        hipError_t e = hipSuccess;
-        auto ok = [&](hipError_t r) { if (e == hipSuccess) e = r; return e == hipSuccess; };
+        const size_t n_box = (size_t)batch * 9u;
+        bool mem = s.h_box.alloc(n_box) && s.h_time.alloc(batch) && s.d_xyz.alloc((size_t)batch * n_atoms * 3u) && s.d_box.alloc(n_box);
         if (dev) {
-            ok(hipHostMalloc((void **)&s.h_blob, blob_cap, hipHostMallocDefault));   // (write-combined: no faster, measured)
-            ok(hipHostMalloc((void **)&s.h_frames, (size_t)batch * sizeof(gorder_xtc_frame_t), hipHostMallocDefault));
-            ok(hipMalloc((void **)&s.d_blob, blob_cap));
-            ok(hipMalloc((void **)&s.d_frames, (size_t)batch * sizeof(gorder_xtc_frame_t)));
-            ok(hipMalloc((void **)&s.d_box_in, box_bytes));
-            ok(hipMalloc((void **)&s.d_stat, 4 * sizeof(uint32_t)));      // [0..1] the decoder's report, [2..3] its error key
-            ok(hipMalloc((void **)&s.d_short, (size_t)batch * sizeof(uint32_t)));
-            if (has_xtc) ok(hipMalloc((void **)&s.d_cp, xtc_checkpoints(batch, n_stop) * sizeof(XtcCheckpoint)));
-            ok(hipHostMalloc((void **)&s.h_stat, 2 * sizeof(uint32_t), hipHostMallocDefault));
-            ok(hipHostMalloc((void **)&s.h_short, (size_t)batch * sizeof(uint32_t), hipHostMallocDefault));
+            // (h_blob write-combined: no faster, measured; d_stat: [0..1] the decoder's report, [2..3] its error key)
+            mem = mem && s.h_blob.alloc(blob_cap) && s.h_frames.alloc(batch) && s.d_blob.alloc(blob_cap) && s.d_frames.alloc(batch) &&
+                  s.d_box_in.alloc(n_box) && s.d_stat.alloc(4) && s.d_short.alloc(batch) &&
+                  (!has_xtc || s.d_cp.alloc(xtc_checkpoints(batch, n_stop))) && s.h_stat.alloc(2) && s.h_short.alloc(batch);
             s.file_pos.resize(batch);
             s.file_idx.resize(batch);
-            ok(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
         } else {
-            ok(hipHostMalloc((void **)&s.h_xyz, xyz_bytes, hipHostMallocDefault));
+            mem = mem && s.h_xyz.alloc((size_t)batch * n_atoms * 3u);
         }
-        ok(hipHostMalloc((void **)&s.h_box, box_bytes, hipHostMallocDefault));
-        ok(hipHostMalloc((void **)&s.h_time, (size_t)batch * sizeof(float), hipHostMallocDefault));
-        ok(hipMalloc((void **)&s.d_xyz, xyz_bytes));
-        ok(hipMalloc((void **)&s.d_box, box_bytes));
-        ok(hipEventCreateWithFlags(&s.staged, hipEventDisableTiming));
-        ok(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
-        ok(hipEventCreateWithFlags(&s.computed, hipEventDisableTiming));
+        hipError_t e = mem ? hipSuccess : hipGetLastError();
+        if (!mem && e == hipSuccess) e = hipErrorOutOfMemory;
+        if (e == hipSuccess && dev) e = s.stream.create();
+        if (e == hipSuccess) e = s.staged.create();
+        if (e == hipSuccess) e = s.copied.create();
+        if (e == hipSuccess) e = s.computed.create();
         return e;
     };
     const int n_slots = dev ? TrajPipe::kSlots : 3;
@@ -354,7 +307,7 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
         const hipError_t e0 = alloc_slot(pipe.slot[0]);
         if (e0 != hipSuccess) {
             traj_cache_free(h);        // (a slot that is only partly there)
-            TRAJ_TRY(e0);
+            HIP_TRY(h, e0);
         }
     }
     pipe.free_q.push_back(0);
@@ -631,7 +584,7 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
         }
         if (status == GORDER_OK) {
             e = hipEventRecord(s.computed, h->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(h_err, reinterpret_cast<unsigned long long *>(h->d_err) + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(h_err, reinterpret_cast<unsigned long long *>(h->d_err.get()) + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream);
             if (e != hipSuccess) { status = GORDER_ERR_DEVICE; hip_msg = std::string("trajectory submit: ") + hipGetErrorString(e); }
             s.compute_issued = true;
             frames += s.n;
@@ -720,8 +673,6 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
         stats->shard_first = shard_lo;
         stats->shard_frames_total = tr->shard_count > 1 ? shard_total : frames;
     }
-    cleanup();
     if (pipe.alloc_failed) traj_cache_free(h);      // (a slot that is only partly there)
-#undef TRAJ_TRY
     return status;
 }
