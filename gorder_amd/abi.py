@@ -329,6 +329,7 @@ _EXPORTS = [
     "gorder_hip_set_radial_shells", "gorder_hip_radial_shells", "gorder_hip_radial_thresholds",
     "gorder_hip_set_molecule_rows", "gorder_hip_molecule_rows_count", "gorder_hip_molecule_rows", "gorder_hip_molecule_rows_stats",
     "gorder_hip_set_order_histogram", "gorder_hip_order_histogram",
+    "gorder_hip_set_bond_correlation", "gorder_hip_bond_correlation",
 ]
 
 _lib = None
@@ -438,12 +439,16 @@ def load_library() -> C.CDLL:
     lib.gorder_hip_molecule_rows_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u32), C.POINTER(u32)]
     lib.gorder_hip_set_order_histogram.argtypes = [vp, vp, u32]
     lib.gorder_hip_order_histogram.argtypes = [vp, vp, C.POINTER(u32)]
+    lib.gorder_hip_set_bond_correlation.argtypes = [vp, vp, u32]
+    lib.gorder_hip_bond_correlation.argtypes = [vp, vp, vp, C.POINTER(u32)]
     _lib = lib
     return lib
 
 
 RADIAL_MAX_SHELLS = 32       # GORDER_RADIAL_MAX_SHELLS
 HIST_MAX_BINS = 256          # GORDER_HIST_MAX_BINS
+CORR_MAX_LAGS = 64           # GORDER_CORR_MAX_LAGS
+CORR_MAX_LAG = 4096          # GORDER_CORR_MAX_LAG
 
 
 def radial_thresholds(radii) -> np.ndarray:
@@ -913,6 +918,30 @@ class HipEngine:
         if n.value:
             self._check(self.lib.gorder_hip_order_histogram(self._h, counts.ctypes.data_as(C.c_void_p), C.byref(n)))
         return counts
+
+    def set_bond_correlation(self, lags):
+        """Strictly ascending lags in analysed frames (structure.correlation_lags; 1 to CORR_MAX_LAGS values, none above
+        CORR_MAX_LAG, 0 allowed): from now on the handle also books, per lag, accumulator slot and leaflet, the P2 tick of every
+        bond vector against its own vector `lag` analysed frames earlier (gorder_hip_set_bond_correlation).  Before the first
+        submit or right after reset(); an empty list switches the correlation off."""
+        l = np.asarray([] if lags is None else lags).reshape(-1)
+        if l.size and (not np.issubdtype(l.dtype, np.integer) or l.min() < 0 or l.max() >= 2**32):
+            raise ValueError("the lags are non-negative integers")
+        l = np.ascontiguousarray(l, dtype=np.uint32)
+        self._check(self.lib.gorder_hip_set_bond_correlation(self._h, l.ctypes.data_as(C.c_void_p) if l.size else None, l.size))
+
+    def bond_correlation(self):
+        """(sums int64 [n_lags, 3, n_acc], counts uint64 [n_lags, 3, n_acc]) of the frames analysed so far, the planes total,
+        upper, lower: raw integers, C = sums / counts / 1e6 (structure.correlation_values), the arrays of several shards add
+        up (gorder_hip_bond_correlation).  Waits like finish(); [0, 3, n_acc] with the correlation off."""
+        n = C.c_uint32()
+        self._check(self.lib.gorder_hip_bond_correlation(self._h, None, None, C.byref(n)))
+        sums = np.zeros((n.value, 3, self.n_acc), dtype=np.int64)
+        counts = np.zeros((n.value, 3, self.n_acc), dtype=np.uint64)
+        if n.value:
+            self._check(self.lib.gorder_hip_bond_correlation(self._h, sums.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
+                                                             C.byref(n)))
+        return sums, counts
 
     def molecule_rows_count(self) -> int:
         """Per-molecule rows kept so far (one per analysed frame); does not wait."""

@@ -44,6 +44,7 @@
 #include "order_route.h"
 #include "molecule_rows.h"
 #include "order_hist.h"
+#include "bond_corr.h"
 
 #pragma clang fp contract(off)
 
@@ -60,6 +61,7 @@ using gorder::Tile;
 #include "kernels_molrows.h"
 #include "kernels_radial.h"
 #include "kernels_hist.h"
+#include "kernels_corr.h"
 #include "kernels_leaflets.h"
 #include "kernels_cluster.h"
 #include "kernels_cluster_cutoff.h"
@@ -127,6 +129,22 @@ struct RepAcc {
         hipLaunchKernelGGL(k_fold_replicas, dim3((uint32_t)((words + 255) / 256)), dim3(256), 0, stream, acc.get(), rep.get(), n_rep, (uint32_t)words);
         return hipGetLastError();
     }
+};
+
+// bond reorientation (gorder_hip_set_bond_correlation; bond_corr.h, kernels_corr.h): the lags, the ring of frame planes
+// float4 [ring_planes][plane_items] (allocated at the first submit), the sums and counts [n_lags][4][n_acc] laid out like d_acc
+// per lag and their replicas (k_bond_corr adds into them)
+struct BondCorr {
+    std::vector<uint32_t> lags;                 // empty: off
+    DBuf<uint32_t> d_lags;                      // padded to whole groups of kCorrLagBlock with kCorrNoLag
+    DBuf<float4> ring;
+    uint32_t ring_planes = 0, subrange = 0;     // R = max lag + subrange; 0: no ring yet
+    uint32_t plane_items = 0;                   // n_tiles * kBlock
+    uint64_t seen = 0;                          // analysed frames since create / reset: frame g lives in plane g mod R
+    RepAcc acc;
+    uint32_t forced_subrange = 0;               // GORDER_HIP_CORR_SUBRANGE, read once at gorder_hip_create
+    bool chunk_major = false;                   // GORDER_HIP_CORR_GRID=chunks, read once likewise: a workgroup walks every group of lags
+    bool on() const { return !lags.empty(); }
 };
 
 struct gorder_hip_handle {
@@ -345,6 +363,7 @@ struct gorder_hip_handle {
     bool hist_direct = false;                   // per-sample global atomics: the table does not fit, or ...
     bool hist_force_direct = false;             // ... GORDER_HIP_DIST_DIRECT, read once at gorder_hip_create
     uint32_t hist_samples_per_word = gorder::kDistSamplesPerWord;       // dist_chunks; GORDER_HIP_DIST_SAMPLES_PER_WORD, read once likewise
+    BondCorr corr;
     // per-molecule rows (gorder_hip_set_molecule_rows; molecule_rows.h, kernels_molrows.h): the lane order and the run tables,
     // the staging block of one frame sub-range [frames][n_groups][n_mol_total] packed words, and the rows in pinned chunks
     gorder::MolRows mol;                        // mol.n_groups != 0: the rows are on
@@ -1568,6 +1587,8 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
     if (const char *e = getenv("GORDER_HIP_KERNEL")) h->use_gather = strcmp(e, "gather") == 0;
     h->shell_force_direct = env_flag("GORDER_HIP_RADIAL_DIRECT");
     h->hist_force_direct = env_flag("GORDER_HIP_DIST_DIRECT");
+    if (const char *ev = getenv("GORDER_HIP_CORR_SUBRANGE")) h->corr.forced_subrange = (uint32_t)std::max(0, atoi(ev));
+    if (const char *ev = getenv("GORDER_HIP_CORR_GRID")) h->corr.chunk_major = strcmp(ev, "chunks") == 0;
     if (const char *ev = getenv("GORDER_HIP_DIST_SAMPLES_PER_WORD")) h->hist_samples_per_word = (uint32_t)std::min(std::max(0, atoi(ev)), 1 << 16);
     if (const char *e = getenv("GORDER_HIP_MOL_ROWS_STAGING")) {      // bytes of the per-molecule rows' device staging (tests set it small)
         const long long v = atoll(e);
@@ -1963,6 +1984,42 @@ static int run_leaflets(gorder_hip_handle *h, const float *d_xyz, const float *d
     return GORDER_OK;
 }
 
+// ---- bond reorientation: the batch's bond vectors into the ring, then every pair (frame, frame - lag), a sub-range at a time
+static int launch_bond_corr(gorder_hip_handle *h, const FrameArgs &a) {
+    BondCorr &bc = h->corr;
+    const Plan &p = h->plan;
+    const uint32_t n_tiles = (uint32_t)p.tiles.size(), n_lags = (uint32_t)bc.lags.size(), max_lag = bc.lags.back();
+    if (!bc.ring) {      // the first batch: the sub-range is fixed here (the setter has checked that one frame fits)
+        const uint64_t fit = gorder::corr_subrange_fit(gorder::corr_plane_bytes(n_tiles, kBlock), max_lag, gorder::kCorrRingBudget);
+        bc.subrange = gorder::corr_subrange(fit, a.n_frames, bc.forced_subrange);
+        bc.ring_planes = gorder::corr_ring_planes(max_lag, bc.subrange);
+        bc.plane_items = n_tiles * kBlock;
+        ST_TRY(allocate(h, bc.ring, (size_t)bc.ring_planes * bc.plane_items));
+    }
+    CorrArgs c{};
+    c.ring = bc.ring; c.ring_planes = bc.ring_planes; c.plane_items = bc.plane_items;
+    c.base = gorder::corr_plane_of(bc.seen, bc.ring_planes);
+    c.history = (uint32_t)std::min<uint64_t>(bc.seen, GORDER_CORR_MAX_LAG);
+    c.n_lags = n_lags; c.lags = bc.d_lags; c.rep = bc.acc.rep; c.n_rep = bc.acc.n_rep; c.n_acc = p.n_acc;
+    c.leaflets = a.leaflets; c.aflags = a.aflags; c.arow = a.arow; c.n_mol_total = a.n_mol_total;
+    c.xyz = a.xyz; c.box9 = a.box9; c.n_atoms = a.n_atoms; c.pbc = a.pbc;
+    for (uint32_t lo = 0; lo < a.n_frames; lo += bc.subrange) {
+        const uint32_t hi = (uint32_t)std::min<uint64_t>(a.n_frames, (uint64_t)lo + bc.subrange), nf = hi - lo;
+        const gorder::CorrChunks ch = gorder::corr_chunks(nf, n_tiles, h->wg_target, h->wg_capacity);
+        const uint32_t n_groups = (n_lags + gorder::kCorrLagBlock - 1u) / gorder::kCorrLagBlock;
+        const uint64_t grid = (uint64_t)n_tiles * ch.n_chunks * (bc.chunk_major ? 1u : n_groups);
+        if ((uint64_t)n_tiles * nf > 0x7fffffffull || grid > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "batch too large");
+        c.frame0 = lo; c.n_frames = hi; c.frames_per_chunk = ch.frames_per_chunk; c.n_chunks = bc.chunk_major ? 0u : ch.n_chunks;
+        TIMING_MARK(h, "k_bond_units");
+        hipLaunchKernelGGL(k_bond_units, dim3(n_tiles * nf), dim3(kBlock), 0, h->stream, c, h->d_tiles, h->d_items, n_tiles);
+        TIMING_MARK(h, "k_bond_corr");
+        hipLaunchKernelGGL((k_bond_corr<gorder::kCorrLagBlock>), dim3((uint32_t)grid), dim3(kBlock), 0, h->stream, c, h->d_tiles,
+                           h->d_items, h->d_tile_slots, n_tiles);
+        HIP_TRY(h, hipGetLastError());
+    }
+    return GORDER_OK;
+}
+
 int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const float *d_box,
                              const uint64_t *frame_index, uint32_t n_frames) {
     if (!h || !d_xyz || !frame_index) return GORDER_ERR_INVALID_ARGUMENT;
@@ -1993,7 +2050,7 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
     ri.dyn_or_manual = h->dyn || ri.manual_frames || ri.normal_table;       // (manual_active is set further down)
     ri.use_gather = h->use_gather; ri.item_run = h->d_item_run != nullptr; ri.frames_per_stage = h->frames_per_stage; ri.max_window = p.max_window;
     ri.bond_tiles = !p.tiles.empty(); ri.ua_tiles = !p.ua_tiles.empty(); ri.direct_items = !p.direct.empty(); ri.ua_fast_flag = (h->tables.flags & GORDER_FLAG_UA_FAST_NORMALISE) != 0;
-    ri.global_leaflets = lf.method == GORDER_LEAFLETS_GLOBAL; ri.spec_enabled = h->spec_enabled; ri.have_assignment = h->have_assignment;
+    ri.global_leaflets = lf.method == GORDER_LEAFLETS_GLOBAL; ri.spec_enabled = h->spec_enabled && !h->corr.on(); ri.have_assignment = h->have_assignment;
     ri.shells = h->n_shells != 0;
     ri.dist = h->hist_edges != 0;
     ri.mol_rows = h->mol.n_groups != 0 && !h->mol_failed;
@@ -2070,7 +2127,7 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
         spec_poll(h, false);
         const uint32_t slot = (uint32_t)(h->spec_batches % gorder_hip_handle::kSpecRing);
         if (h->spec_ring_frames[slot]) (void)hipEventSynchronize(h->spec_counters_copied[slot]), spec_poll(h, false);
-        ri.spec_enabled = h->spec_enabled;
+        ri.spec_enabled = h->spec_enabled && !h->corr.on();
         if (!ri.spec_enabled) route = gorder::choose_order_route(ri);      // the counters of an earlier batch turned it off
     }
     const bool spec = route.speculative;
@@ -2188,6 +2245,8 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
         h->spec_ring_frames[ring_slot] = n_frames;
         h->spec_batches++;
     }
+    // bond reorientation: an additional pass over the batch, behind everything that writes the flag rows
+    if (h->corr.on() && (st = launch_bond_corr(h, a)) != GORDER_OK) return abort_batch(st);
     // the history a host asked for (rows 1.. of d_aflags hold every assignment frame's exact sides by now)
     if ((st = collect_flag_rows(h, 1, collect_frames)) != GORDER_OK) return abort_batch(st);
     if (ltable && (h->collect & GORDER_COLLECT_LEAFLETS)) {
@@ -2230,6 +2289,7 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
         h->n_submits++;
     }
     h->n_frames += n_frames;
+    if (h->corr.on()) h->corr.seen += n_frames;
     return GORDER_OK;
 }
 
@@ -2861,6 +2921,65 @@ int gorder_hip_order_histogram(gorder_hip_handle *h, uint64_t *counts, uint32_t 
     return GORDER_OK;
 }
 
+// ---- bond reorientation (bond_corr.h, kernels_corr.h) ----------------------------------------------------------------------
+int gorder_hip_set_bond_correlation(gorder_hip_handle *h, const uint32_t *lags, uint32_t n_lags) {
+    if (!h || (n_lags && !lags)) return GORDER_ERR_INVALID_ARGUMENT;
+    const char *who = "gorder_hip_set_bond_correlation: ";
+    auto refuse = [&](const std::string &why) { return fail(h, GORDER_ERR_INVALID_ARGUMENT, std::string(who) + why); };
+    if (h->collect_locked) return refuse("only before the first submit or prime, or right after gorder_hip_reset");
+    const Plan &p = h->plan;
+    if (n_lags) {
+        if (!p.ua_tiles.empty()) return refuse("united-atom molecule types");
+        if (h->extra.geom_kind) return refuse("a geometry selection (a pair may be half inside)");
+        if (!p.direct.empty()) return refuse("a bond spans more than the LDS window");
+        if (!p.n_acc || p.tiles.empty()) return refuse("no bond samples");
+        if (const char *why = gorder::corr_lags_check(lags, n_lags)) return refuse(why);
+        const uint64_t plane = gorder::corr_plane_bytes(p.tiles.size(), kBlock);
+        if (!gorder::corr_subrange_fit(plane, lags[n_lags - 1], gorder::kCorrRingBudget))
+            return refuse("the ring is over budget: (" + std::to_string(lags[n_lags - 1]) + " + 1) planes x " + std::to_string(plane) + " bytes = " +
+                          std::to_string(((uint64_t)lags[n_lags - 1] + 1u) * plane) + " bytes > " + std::to_string(gorder::kCorrRingBudget));
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // (a reset still queued may be zeroing the old blocks)
+    BondCorr &bc = h->corr;
+    bc.lags.clear(); bc.d_lags.reset(); bc.ring.reset(); bc.acc.reset();
+    bc.ring_planes = bc.subrange = 0; bc.seen = 0;
+    if (!n_lags) return GORDER_OK;
+    std::vector<uint32_t> padded(lags, lags + n_lags);
+    padded.resize((n_lags + gorder::kCorrLagBlock - 1u) / gorder::kCorrLagBlock * gorder::kCorrLagBlock, gorder::kCorrNoLag);
+    ST_TRY(upload(h, bc.d_lags, padded));
+    ST_TRY(alloc_zeroed(h, bc.acc, (size_t)n_lags * 4u * p.n_acc));
+    bc.lags.assign(lags, lags + n_lags);
+    return GORDER_OK;
+}
+
+int gorder_hip_bond_correlation(gorder_hip_handle *h, int64_t *sums, uint64_t *counts, uint32_t *n_lags) {
+    if (!h) return GORDER_ERR_INVALID_ARGUMENT;
+    const uint32_t nl = (uint32_t)h->corr.lags.size();
+    if (n_lags) *n_lags = nl;
+    if (!nl) return GORDER_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, h->corr.acc.fold(h->stream));
+    const int st = gorder_hip_synchronize(h);
+    if (st != GORDER_OK) return st;
+    if (!sums && !counts) return GORDER_OK;
+    std::vector<unsigned long long> raw(h->corr.acc.words);
+    HIP_TRY(h, hipMemcpy(raw.data(), h->corr.acc.acc, raw.size() * sizeof(u64), hipMemcpyDeviceToHost));
+    const bool lf = h->tables.leaflets.method != GORDER_LEAFLETS_NONE;
+    const uint32_t n = h->plan.n_acc;
+    for (uint32_t k = 0; k < nl; k++) {
+        const unsigned long long *r = raw.data() + (size_t)k * 4u * n;
+        for (uint32_t s = 0; s < n; s++) {
+            const int64_t stot = (int64_t)r[s], sup = (int64_t)r[n + s];
+            const uint64_t ctot = r[2u * n + s], cup = r[3u * n + s];
+            const size_t o = (size_t)k * 3u * n + s;
+            if (sums) { sums[o] = stot; sums[o + n] = lf ? sup : 0; sums[o + 2 * (size_t)n] = lf ? stot - sup : 0; }
+            if (counts) { counts[o] = ctot; counts[o + n] = lf ? cup : 0; counts[o + 2 * (size_t)n] = lf ? ctot - cup : 0; }
+        }
+    }
+    return GORDER_OK;
+}
+
 // ---- per-molecule rows (molecule_rows.h, kernels_molrows.h) -------------------------------------------------------------
 int gorder_hip_set_molecule_rows(gorder_hip_handle *h, const uint32_t *group_begin, const uint32_t *slots, uint32_t n_groups) {
     if (!h || (n_groups && (!group_begin || !slots))) return GORDER_ERR_INVALID_ARGUMENT;
@@ -3047,6 +3166,10 @@ int gorder_hip_reset(gorder_hip_handle *h) {
     h->rep_dirty = false;
     if (h->n_shells) HIP_TRY(h, h->shells.zero_async(h->stream));       // (the radii stay)
     if (h->hist_edges) HIP_TRY(h, h->hist.zero_async(h->stream));      // (the edges stay)
+    if (h->corr.on()) {     // (the lags and the ring stay; its planes are history no pair will ask for)
+        HIP_TRY(h, h->corr.acc.zero_async(h->stream));
+        h->corr.seen = 0;
+    }
     if (h->extra.maps) {
         const size_t nmap = 3 * (size_t)p.n_acc * h->map_nx * h->map_ny;
         const size_t npk = (h->tables.leaflets.method != GORDER_LEAFLETS_NONE ? 2 : 1) * (nmap / 3);

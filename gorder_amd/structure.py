@@ -662,6 +662,53 @@ def order_density(hist, edges, analysis: str):
     return density, lo, hi
 
 
+# ---- bond reorientation (HipEngine.bond_correlation): this project's own output, the reference has none ----------
+def correlation_lags(max_lag: int, per_octave: int = 4) -> np.ndarray:
+    """uint32 lags for HipEngine.set_bond_correlation: 0, 1, 2, ... while consecutive integers are at least as dense as
+    `per_octave` values per doubling, then log-spaced with that density, ending at max_lag exactly; thinned evenly (both ends
+    kept) where that would be more than 64."""
+    if not 0 <= max_lag <= 4096 or per_octave < 1:
+        raise ValueError("max_lag 0 to 4096, per_octave at least 1")
+    lags, x = {0, int(max_lag)}, 1.0
+    while x < max_lag:
+        lags.add(int(round(x)))
+        x = max(x * 2.0 ** (1.0 / per_octave), np.floor(x) + 1.0)
+    out = np.array(sorted(lags), dtype=np.uint32)
+    if len(out) > 64:
+        out = np.unique(out[np.rint(np.linspace(0, len(out) - 1, 64)).astype(np.int64)])
+    return out
+
+
+def correlation_values(sums, counts, groups, min_samples: int = 1) -> np.ndarray:
+    """C(lag) float64 [n_groups, 3, n_lags] of every group (a list of accumulator slots, as error_groups gives them) and
+    leaflet from the integers [n_lags, 3, n_acc] of HipEngine.bond_correlation(): the group's sums and counts are added first,
+    then sum / count / 1e6; NaN where fewer than min_samples pairs were booked."""
+    s, c = np.asarray(sums, dtype=np.int64), np.asarray(counts, dtype=np.uint64)
+    if s.ndim != 3 or s.shape[1] != 3 or c.shape != s.shape:
+        raise ValueError("sums and counts [n_lags, 3, n_acc]")
+    out = np.full((len(groups), 3, s.shape[0]), np.nan, dtype=np.float64)
+    for g, slots in enumerate(groups):
+        idx = [int(q) for q in slots]
+        gs = s[:, :, idx].sum(axis=2, dtype=np.int64).T
+        gc = c[:, :, idx].sum(axis=2, dtype=np.uint64).T
+        ok = (gc >= np.uint64(max(int(min_samples), 1)))
+        out[g][ok] = gs[ok].astype(np.float64) / gc[ok].astype(np.float64) / 1e6
+    return out
+
+
+def correlation_time(values, lags, dt: float, plateau):
+    """Effective correlation time: the trapezoid of (C - plateau) / (1 - plateau) over the given lags times dt (the time
+    between two analysed frames), along the last axis of `values`.  `plateau` is the long-time limit S^2, the square of the
+    order parameter finish() gives for the same group (a scalar, or an array that broadcasts against values[..., 0])."""
+    v, l = np.asarray(values, dtype=np.float64), np.asarray(lags, dtype=np.float64)
+    if l.ndim != 1 or v.shape[-1] != l.size or l.size < 2 or (np.diff(l) <= 0).any():
+        raise ValueError("values [..., n_lags] over at least two ascending lags")
+    p = np.asarray(plateau, dtype=np.float64)[..., None]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        y = (v - p) / (1.0 - p)
+    return float(dt) * (0.5 * (y[..., 1:] + y[..., :-1]) * np.diff(l)).sum(axis=-1)
+
+
 # ---- ordermaps: which maps the reference writes, and their values (presentation layer arithmetic) ----------
 @dataclass
 class OrdermapGroup:

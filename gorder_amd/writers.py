@@ -393,6 +393,31 @@ def order_histogram_text(counts, edges, names, angles=None, header: Optional[str
     return "\n".join(out) + "\n"
 
 
+def bond_correlation_text(values, lags, names, dt: float = 1.0, header: Optional[str] = None) -> str:
+    """A bond reorientation correlation as text (this project's own layout: the reference has no such file), from the values
+    [n_groups, 3, n_lags] of structure.correlation_values, the lags given to HipEngine.set_bond_correlation and one name per
+    group: one row per lag — the lag in analysed frames, the lag times `dt` with four decimals — then per group its full,
+    upper and lower C(lag) with six decimals (NaN as `NaN`), under `#` lines that name the columns."""
+    n_lags = len(lags)
+    if len(values) != len(names) or any(len(w) != n_lags for v in values for w in v) or any(len(v) != 3 for v in values):
+        raise ValueError("values [n_groups, 3, n_lags], one name per group, one lag per column")
+    out = [header or "# bond reorientation: C(lag) = <P2(u(t) . u(t + lag))> over t and the molecules",
+           "# column 1: lag [analysed frames]", "# column 2: lag * dt"]
+    col = 3
+    for name in names:
+        for which in ("full", "upper", "lower"):
+            out.append(f"# column {col}: {name} {which}")
+            col += 1
+    for k in range(n_lags):
+        cells = [str(int(lags[k])), _fixed(float(lags[k]) * float(dt))]
+        for g in range(len(names)):
+            for w in range(3):
+                x = float(values[g][w][k])
+                cells.append("NaN" if x != x else f"{x:.6f}")
+        out.append(" ".join(cells))
+    return "\n".join(out) + "\n"
+
+
 _PLANE_LABELS = {0: ("x", "y"), 1: ("x", "z"), 2: ("z", "y")}     # Plane::get_labels (input/ordermap.rs:54-60)
 _LEAFLET_NAMES = ("full", "upper", "lower")
 

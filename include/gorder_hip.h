@@ -633,6 +633,52 @@ int gorder_hip_molecule_rows_stats(gorder_hip_handle *h, uint64_t *n_runs, uint3
 int gorder_hip_set_order_histogram(gorder_hip_handle *h, const int32_t *edges, uint32_t n_edges);
 int gorder_hip_order_histogram(gorder_hip_handle *h, uint64_t *counts, uint32_t *n_bins);
 
+/* ---- bond reorientation: the second-rank autocorrelation of every bond vector, in the same pass over the frames ------------
+ * Everything above says how ordered a bond is; this says how fast it reorients:  C(lag) = < P2( u(t) . u(t + lag) ) >  over t
+ * and the molecules, u the direction of the bond.  Its plateau is S^2, its decay gives correlation times.  The reference has
+ * no counterpart.
+ * gorder_hip_set_bond_correlation takes 1 .. GORDER_CORR_MAX_LAGS strictly ascending lags, each at most GORDER_CORR_MAX_LAG;
+ *   lag 0 is allowed.  The unit of a lag is ANALYSED FRAMES IN SUBMIT ORDER, counted by the handle from its first frame
+ *   since gorder_hip_create or gorder_hip_reset — not frame_index.
+ * For every bond sample and every analysed frame s with s - lag at or behind that first frame the handle books one tick,
+ *   tick = round(10^6 * S),  S = 1.5 q - 0.5,  q = (v_s . v_e)^2 / (|v_s|^2 * n2sq),  e = s - lag,
+ *   v = p2 - p1 of that frame under the handle's minimum image (or none), never normalised; the later frame s is the sample,
+ *   the earlier frame e plays the membrane normal, n2sq = (x*x + y*y) + z*z of v_e: the arithmetic of a per-molecule manual
+ *   normal (gorder_hip_set_normals), operation for operation.  The ticks ALWAYS use this default squared-cosine form, also on
+ *   a handle with GORDER_FLAG_TRIG_ACOS_COS: that flag is about reproducing the reference's order parameter, and the
+ *   reference has no correlation.
+ * A pair is booked on the leaflet its molecule has in the LATER frame s.  Every step is an integer add: the result is exact
+ *   and does not depend on the cut into batches, the chunking or the launch geometry.
+ * The pass is an additional one behind the batch's leaflet and order kernels (k_bond_units, k_bond_corr in
+ *   gorder_hip_kernel_time_names / _group); gorder_hip_finish returns exactly what it returns without it, and a handle that
+ *   never calls the setter queues exactly what it queued before.  With the correlation on, global leaflets are assigned by
+ *   their own kernel (no one-read speculation).
+ * Memory: a ring of max_lag + S frame planes of 16 bytes per bond sample (tiles padded to 256), S the frames of a batch
+ *   handled at once; at most 2 GiB.  The ring is allocated at the first submit: S is the largest sub-range that fits, capped
+ *   by that batch's length (not below 64), and GORDER_HIP_CORR_SUBRANGE (read once at gorder_hip_create) forces a smaller
+ *   one; GORDER_HIP_CORR_GRID=chunks (likewise) takes k_bond_corr's chunk-major grid, same integers.  256 all-atom lipids (16 384 samples) are 262 KB a plane, 1.07 GB at lag 4096; a million coarse-grained bonds are
+ *   14.7 MB a plane, about 130 frames of lag.
+ * gorder_hip_set_bond_correlation: accepted before the first submit / prime or right after gorder_hip_reset (the rule of
+ *   gorder_hip_set_collect); n_lags = 0 switches the correlation off.  GORDER_ERR_INVALID_ARGUMENT, with the reason in
+ *   gorder_hip_last_error_message, for united-atom molecule types; a geometry selection (a pair may be half inside); a bond
+ *   that spans more than the LDS window; a plan without bond samples; bad lags; a ring that would pass 2 GiB with S = 1 (the
+ *   message has the arithmetic).  Everything else combines with it on the same handle: timewise rows, ordermaps, dynamic or
+ *   manual normals, every leaflet method, order histograms, molecule rows, both cosine modes of the order parameter.
+ * gorder_hip_bond_correlation: waits like gorder_hip_finish (a device error of the run is returned); sums int64
+ *   [n_lags][3][n_acc] and counts uint64 [n_lags][3][n_acc], the planes total / upper / lower (lower = total - upper; without
+ *   leaflets upper and lower are 0); C of a slot = sums / counts / 10^6.  n_lags = 0 with the correlation off (nothing is
+ *   written).  Any pointer may be NULL.  The total count of a lag after F frames is max(0, F - lag) * samples of the slot.
+ *   After a batch that ended in an error the arrays have the standing of the ordinary accumulators.
+ * gorder_hip_reset zeroes sums and counts, forgets the history and keeps the lags.
+ * Pairs across a shard boundary are lost: shards add their arrays on the host (gorder_hip_allreduce does NOT carry them), and
+ *   the counts say what is missing.
+ * Not covered: united atoms; geometry selections; cross-correlation between different bonds; lags beyond 4096 frames;
+ *   per-molecule correlation rows. */
+#define GORDER_CORR_MAX_LAGS 64
+#define GORDER_CORR_MAX_LAG 4096
+int gorder_hip_set_bond_correlation(gorder_hip_handle *h, const uint32_t *lags, uint32_t n_lags);
+int gorder_hip_bond_correlation(gorder_hip_handle *h, int64_t *sums, uint64_t *counts, uint32_t *n_lags);
+
 /* Signed distances (nm) behind those flags, [n_molecules_total] (leaflets.rs:725, 796).  GORDER_LEAFLETS_SPHERICAL: each
  * molecule's head-centre distance (nm, non-negative) in the last assignment frame. */
 int gorder_hip_leaflet_distances(gorder_hip_handle *h, float *distances);
