@@ -330,6 +330,7 @@ _EXPORTS = [
     "gorder_hip_set_molecule_rows", "gorder_hip_molecule_rows_count", "gorder_hip_molecule_rows", "gorder_hip_molecule_rows_stats",
     "gorder_hip_set_order_histogram", "gorder_hip_order_histogram",
     "gorder_hip_set_bond_correlation", "gorder_hip_bond_correlation",
+    "gorder_hip_set_neighbour_classes", "gorder_hip_neighbour_classes", "gorder_hip_neighbour_class_rows",
 ]
 
 _lib = None
@@ -441,6 +442,9 @@ def load_library() -> C.CDLL:
     lib.gorder_hip_order_histogram.argtypes = [vp, vp, C.POINTER(u32)]
     lib.gorder_hip_set_bond_correlation.argtypes = [vp, vp, u32]
     lib.gorder_hip_bond_correlation.argtypes = [vp, vp, vp, C.POINTER(u32)]
+    lib.gorder_hip_set_neighbour_classes.argtypes = [vp, vp, vp, u32, C.c_float, u32]
+    lib.gorder_hip_neighbour_classes.argtypes = [vp, vp, vp, C.POINTER(u32)]
+    lib.gorder_hip_neighbour_class_rows.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32)]
     _lib = lib
     return lib
 
@@ -449,6 +453,8 @@ RADIAL_MAX_SHELLS = 32       # GORDER_RADIAL_MAX_SHELLS
 HIST_MAX_BINS = 256          # GORDER_HIST_MAX_BINS
 CORR_MAX_LAGS = 64           # GORDER_CORR_MAX_LAGS
 CORR_MAX_LAG = 4096          # GORDER_CORR_MAX_LAG
+NEIGHBOUR_MAX_ATOMS = 16384  # GORDER_NEIGHBOUR_MAX_ATOMS
+NEIGHBOUR_MAX_CLASSES = 32   # GORDER_NEIGHBOUR_MAX_CLASSES
 
 
 def radial_thresholds(radii) -> np.ndarray:
@@ -942,6 +948,49 @@ class HipEngine:
             self._check(self.lib.gorder_hip_bond_correlation(self._h, sums.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
                                                              C.byref(n)))
         return sums, counts
+
+    def set_neighbour_classes(self, centres, neighbours, radius, n_classes):
+        """One centre atom per molecule (structure.neighbour_centres: the heads), strictly ascending neighbour atoms (1 to
+        NEIGHBOUR_MAX_ATOMS), a radius in nm and 2 to NEIGHBOUR_MAX_CLASSES classes: from now on the handle also books every
+        bond sample on the class min(neighbour atoms within the radius of its molecule's centre, n_classes - 1) of its frame
+        (gorder_hip_set_neighbour_classes).  Before the first submit or right after reset(); an empty neighbour list switches
+        the feature off."""
+        def atoms(a):
+            a = np.asarray([] if a is None else a).reshape(-1)
+            if a.size and (not np.issubdtype(a.dtype, np.integer) or a.min() < 0 or a.max() >= 2**32):
+                raise ValueError("atom indices are non-negative integers")
+            return np.ascontiguousarray(a, dtype=np.uint32)
+        c, q = atoms(centres), atoms(neighbours)
+        if q.size and c.size != self.tables.n_molecules_total:
+            raise ValueError("one centre per molecule")
+        self._check(self.lib.gorder_hip_set_neighbour_classes(self._h, c.ctypes.data_as(C.c_void_p) if c.size else None,
+                                                              q.ctypes.data_as(C.c_void_p) if q.size else None, q.size,
+                                                              float(radius), int(n_classes)))
+
+    def neighbour_classes(self) -> List[Results]:
+        """One Results per class (sums, counts [3, n_acc] as finish() gives them, n_frames the frames analysed so far): raw
+        integers, the classes of several shards add up element by element (gorder_hip_neighbour_classes).  Waits like
+        finish(); an empty list with the feature off."""
+        n = C.c_uint32()
+        self._check(self.lib.gorder_hip_neighbour_classes(self._h, None, None, C.byref(n)))
+        k = int(n.value)
+        sums = np.zeros((max(k, 1), 3, self.n_acc), dtype=np.int64)
+        counts = np.zeros((max(k, 1), 3, self.n_acc), dtype=np.uint64)
+        if k:
+            self._check(self.lib.gorder_hip_neighbour_classes(self._h, sums.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p), C.byref(n)))
+        nf = C.c_uint64()
+        self._check(self.lib.gorder_hip_finish(self._h, None, None, None, None, C.byref(nf)))
+        return [Results(sums[q], counts[q], int(nf.value)) for q in range(k)]
+
+    def neighbour_class_rows(self) -> np.ndarray:
+        """The class bytes uint8 [frames, n_molecules_total] of the last submitted batch (gorder_hip_neighbour_class_rows): a
+        diagnostic.  Waits like finish(); [0, 0] with the feature off or nothing submitted."""
+        nf, nm = C.c_uint32(), C.c_uint32()
+        self._check(self.lib.gorder_hip_neighbour_class_rows(self._h, None, C.byref(nf), C.byref(nm)))
+        rows = np.zeros((nf.value, nm.value), dtype=np.uint8)
+        if rows.size:
+            self._check(self.lib.gorder_hip_neighbour_class_rows(self._h, rows.ctypes.data_as(C.c_void_p), C.byref(nf), C.byref(nm)))
+        return rows
 
     def molecule_rows_count(self) -> int:
         """Per-molecule rows kept so far (one per analysed frame); does not wait."""

@@ -45,6 +45,7 @@
 #include "molecule_rows.h"
 #include "order_hist.h"
 #include "bond_corr.h"
+#include "neighbour_classes.h"
 
 #pragma clang fp contract(off)
 
@@ -60,6 +61,7 @@ using gorder::Tile;
 #include "kernels_extras.h"
 #include "kernels_molrows.h"
 #include "kernels_radial.h"
+#include "kernels_neighbours.h"
 #include "kernels_hist.h"
 #include "kernels_corr.h"
 #include "kernels_leaflets.h"
@@ -145,6 +147,26 @@ struct BondCorr {
     uint32_t forced_subrange = 0;               // GORDER_HIP_CORR_SUBRANGE, read once at gorder_hip_create
     bool chunk_major = false;                   // GORDER_HIP_CORR_GRID=chunks, read once likewise: a workgroup walks every group of lags
     bool on() const { return !lags.empty(); }
+};
+
+// order by local composition (gorder_hip_set_neighbour_classes; neighbour_classes.h, kernels_neighbours.h): the centre atom of
+// every molecule and the neighbour atoms on the device and on the host (the payload of an undefined position), the class bytes
+// [frames][n_mol_total] of the last batch (k_neighbour_counts writes them, k_bonds_classes reads them), the sums and counts
+// [n_classes][4][n_acc] laid out like d_acc per class and their replicas (k_bonds_classes adds into them)
+struct NeighbourClasses {
+    uint32_t n_classes = 0;                     // 0: off
+    float radius = 0.0f, thr = 0.0f;            // thr = local_radius_threshold(radius)
+    std::vector<uint32_t> centres, neighbours;
+    DBuf<uint32_t> d_centres, d_neighbours;
+    DBuf<uint8_t> rows;
+    uint32_t rows_frames = 0;                   // frames the rows hold right now (the last batch, or its last sub-range)
+    RepAcc acc;
+    size_t lds_bytes = 0;                       // the LDS table of the widest tile
+    bool direct = false;                        // per-sample global atomics: the table does not fit, or ...
+    bool force_direct = false;                  // ... GORDER_HIP_NB_DIRECT, read once at gorder_hip_create
+    uint32_t forced_subrange = 0;               // GORDER_HIP_NB_SUBRANGE, read once likewise
+    uint64_t row_bytes = gorder::kClassRowBytes;    // the most the class rows take; GORDER_HIP_NB_ROW_BYTES, read once likewise (tests set it small)
+    bool on() const { return n_classes != 0; }
 };
 
 struct gorder_hip_handle {
@@ -364,6 +386,7 @@ struct gorder_hip_handle {
     bool hist_force_direct = false;             // ... GORDER_HIP_DIST_DIRECT, read once at gorder_hip_create
     uint32_t hist_samples_per_word = gorder::kDistSamplesPerWord;       // dist_chunks; GORDER_HIP_DIST_SAMPLES_PER_WORD, read once likewise
     BondCorr corr;
+    NeighbourClasses nb;
     // per-molecule rows (gorder_hip_set_molecule_rows; molecule_rows.h, kernels_molrows.h): the lane order and the run tables,
     // the staging block of one frame sub-range [frames][n_groups][n_mol_total] packed words, and the rows in pinned chunks
     gorder::MolRows mol;                        // mol.n_groups != 0: the rows are on
@@ -499,6 +522,10 @@ int check_device_error(gorder_hip_handle *h) {
     h->err_index = 0;
     if (status == GORDER_ERR_UNDEFINED_POSITION) {
         if (stage == kStageTypes && sample) h->err_index = sample_atom(h->plan, slot, mol, detail);
+        else if (h->nb.on() && stage == kStageSystem) {      // k_neighbour_counts: a molecule's centre, or a position in the neighbour list
+            const std::vector<uint32_t> &atoms = detail ? h->nb.neighbours : h->nb.centres;
+            if (mol < atoms.size()) h->err_index = atoms[mol];
+        }
         else if (mol < h->host_dyn_heads.size()) h->err_index = h->host_dyn_heads[mol];   // head of a dynamic-normal cloud
     } else if (status == GORDER_ERR_INVALID_LOCAL_MEMBRANE_CENTER) {
         if (mol < h->host_heads.size()) h->err_index = h->host_heads[mol];                // leaflets.rs:661-675: the head's index
@@ -753,7 +780,16 @@ int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &
         e.dyn = (h->dyn || h->manual_active) ? h->d_dyn_normals : nullptr;
         const bool staged = route.map_accumulate;
         const size_t rec_per_frame = std::max(p.ua_tiles.size() * 3u, route.extras ? p.tiles.size() : (size_t)0) * kBlock;   // staged words per frame
-        const uint32_t sub = gorder::map_subrange(a.n_frames, e.maps != 0, staged, h->map_fold_limit, h->map_max_mol, rec_per_frame);
+        uint32_t sub = gorder::map_subrange(a.n_frames, e.maps != 0, staged, h->map_fold_limit, h->map_max_mol, rec_per_frame);
+        // neighbour classes: the class rows hold the whole batch where it fits them (gorder_hip_neighbour_class_rows then returns
+        // it), else one sub-range at a time; a sub-range is one launch of k_neighbour_counts, a frame per row of gridDim.y
+        const bool classes = route.family == BondFamily::Classes;
+        bool class_rows_whole = false;
+        if (classes) {
+            class_rows_whole = gorder::class_rows_whole(a.n_frames, p.n_mol_total, h->nb.row_bytes);
+            sub = gorder::class_subrange(a.n_frames, p.n_mol_total, h->nb.forced_subrange, h->nb.row_bytes);
+            ST_TRY(ensure(h, h->nb.rows, (size_t)(class_rows_whole ? a.n_frames : sub) * p.n_mol_total));
+        }
         if (staged) {
             ST_TRY(ensure(h, h->d_map_rec, rec_per_frame * (((size_t)sub + 15) / 16 * 16)));
         }
@@ -769,7 +805,7 @@ int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &
             for (int pass = 0; pass < 2; pass++) {      // the bond tiles, then the united-atom tiles
                 const uint32_t nt = pass == 0 ? (route.extras ? n_tiles : 0u) : (uint32_t)p.ua_tiles.size();
                 if (!nt) continue;
-                const FrameChunks c = pass == 0 && route.family == BondFamily::Shells
+                const FrameChunks c = pass == 0 && (route.family == BondFamily::Shells || classes)
                                           ? gorder::shells_chunks(nf, nt, h->wg_target, h->wg_capacity, kShellChunkMax)
                                       : pass == 0 && route.family == BondFamily::Dist
                                           ? gorder::dist_chunks(nf, nt, h->wg_target, h->wg_capacity, h->hist_direct ? 0u : (uint32_t)h->hist_table_words, h->hist_samples_per_word, kDistChunkMax)
@@ -782,8 +818,26 @@ int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &
                 const dim3 g(pass == 0 ? nt * c.n_chunks : (nt * c.n_chunks + 7u) / 8u * 8u), blk(kBlock);   // united atoms: see the XCD mapping in k_ua_extras
                 if (pass == 0) {
                     const Item *items = route.items_by_slot ? h->d_items_by_slot : h->d_items;
+                    ClassArgs ca{};
+                    if (classes) {      // the class of every (frame, molecule) of the sub-range, ahead of the kernel that reads it
+                        NeighbourClasses &nb = h->nb;
+                        ca.centres = nb.d_centres; ca.neighbours = nb.d_neighbours; ca.n_neighbours = (uint32_t)nb.neighbours.size();
+                        ca.thr = nb.thr; ca.n = nb.n_classes; ca.rows = nb.rows; ca.row_base = class_rows_whole ? 0u : lo;
+                        ca.axis = h->axis; ca.rep = nb.acc.rep; ca.n_rep = nb.acc.n_rep;
+                        nb.rows_frames = class_rows_whole ? a.n_frames : nf;
+                        TIMING_MARK(h, "k_neighbour_counts");
+                        hipLaunchKernelGGL(k_neighbour_counts, dim3((p.n_mol_total + 255u) / 256u, nf), dim3(256), 0, h->stream, ca, b.xyz, b.box9,
+                                           b.n_atoms, p.n_mol_total, b.pbc, lo, h->d_err);
+                    }
                     TIMING_MARK(h, route.label);
-                    if (route.family == BondFamily::Shells) {
+                    if (classes) {
+                        // the table of the widest tile, or the [2][256] u64 + [2][256] u32 of the direct route's reduction
+                        const size_t lds = h->nb.direct ? (size_t)kBlock * 24u : h->nb.lds_bytes;
+                        with_bool(ac, [&](auto AC) { with_bool(h->nb.direct, [&](auto DIRECT) {
+                            hipLaunchKernelGGL((k_bonds_classes<AC(), DIRECT()>), g, blk, lds, h->stream, b, ca, b.xyz, b.box9, b.aflags, b.arow,
+                                               h->d_tiles, items, h->d_tile_slots, nt);
+                        }); });
+                    } else if (route.family == BondFamily::Shells) {
                         ShellArgs sa{};
                         sa.n = h->n_shells; sa.rep = h->shells.rep; sa.n_rep = h->shells.n_rep;
                         for (uint32_t k = 0; k < GORDER_RADIAL_MAX_SHELLS; k++) sa.thr[k] = k < h->n_shells ? h->shell_thr[k] : INFINITY;
@@ -1587,6 +1641,12 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
     if (const char *e = getenv("GORDER_HIP_KERNEL")) h->use_gather = strcmp(e, "gather") == 0;
     h->shell_force_direct = env_flag("GORDER_HIP_RADIAL_DIRECT");
     h->hist_force_direct = env_flag("GORDER_HIP_DIST_DIRECT");
+    h->nb.force_direct = env_flag("GORDER_HIP_NB_DIRECT");
+    if (const char *ev = getenv("GORDER_HIP_NB_SUBRANGE")) h->nb.forced_subrange = (uint32_t)std::max(0, atoi(ev));
+    if (const char *ev = getenv("GORDER_HIP_NB_ROW_BYTES")) {
+        const long long v = atoll(ev);
+        if (v > 0) h->nb.row_bytes = (uint64_t)v;
+    }
     if (const char *ev = getenv("GORDER_HIP_CORR_SUBRANGE")) h->corr.forced_subrange = (uint32_t)std::max(0, atoi(ev));
     if (const char *ev = getenv("GORDER_HIP_CORR_GRID")) h->corr.chunk_major = strcmp(ev, "chunks") == 0;
     if (const char *ev = getenv("GORDER_HIP_DIST_SAMPLES_PER_WORD")) h->hist_samples_per_word = (uint32_t)std::min(std::max(0, atoi(ev)), 1 << 16);
@@ -2053,6 +2113,7 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
     ri.global_leaflets = lf.method == GORDER_LEAFLETS_GLOBAL; ri.spec_enabled = h->spec_enabled && !h->corr.on(); ri.have_assignment = h->have_assignment;
     ri.shells = h->n_shells != 0;
     ri.dist = h->hist_edges != 0;
+    ri.classes = h->nb.on();
     ri.mol_rows = h->mol.n_groups != 0 && !h->mol_failed;
     ri.npf5 = env_flag("GORDER_HIP_NPF5"); ri.tw_gather = env_flag("GORDER_HIP_TW_GATHER"); ri.maps_gather = env_flag("GORDER_HIP_MAPS_GATHER");
     std::vector<uint32_t> spec_aframes;
@@ -2434,6 +2495,7 @@ int gorder_hip_set_normals(gorder_hip_handle *h, const float *normals, uint32_t 
     if (h->n_shells) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_normals: the handle has radial shells (static normals only)");
     if (h->mol.n_groups) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_normals: the handle has molecule rows (static normals only)");
     if (h->hist_edges) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_normals: the handle has an order histogram (static normals only)");
+    if (h->nb.on()) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_normals: the handle has neighbour classes (static normals only)");
     const size_t n = (size_t)n_frames * h->plan.n_mol_total;
     h->manual_normals.resize(4 * n);
     for (size_t i = 0; i < n; i++) {
@@ -2484,6 +2546,7 @@ int gorder_hip_set_manual_normal_table(gorder_hip_handle *h, const float *normal
     if (h->n_shells) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_normal_table: the handle has radial shells (static normals only)");
     if (h->mol.n_groups) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_normal_table: the handle has molecule rows (static normals only)");
     if (h->hist_edges) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_normal_table: the handle has an order histogram (static normals only)");
+    if (h->nb.on()) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_normal_table: the handle has neighbour classes (static normals only)");
     const uint32_t n_mol = h->plan.n_mol_total;
     if (n_rows) {
         if (step == 0) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_manual_normal_table: step 0");
@@ -2790,6 +2853,7 @@ int gorder_hip_set_radial_shells(gorder_hip_handle *h, const float *radii, uint3
         const gorder_tables_t &t = h->tables;
         if (h->mol.n_groups) return refuse("the handle has molecule rows");
         if (h->hist_edges) return refuse("the handle has an order histogram");
+        if (h->nb.on()) return refuse("the handle has neighbour classes");
         if (n_radii > GORDER_RADIAL_MAX_SHELLS) return refuse("more than GORDER_RADIAL_MAX_SHELLS radii");
         if (t.geometry.kind != GORDER_GEOM_CYLINDER && t.geometry.kind != GORDER_GEOM_SPHERE)
             return refuse("the tables select no cylinder or sphere");
@@ -2874,6 +2938,7 @@ int gorder_hip_set_order_histogram(gorder_hip_handle *h, const int32_t *edges, u
         if (h->manual_frames) return refuse("normals were supplied by gorder_hip_set_normals");
         if (h->n_shells) return refuse("the handle has radial shells");
         if (h->mol.n_groups) return refuse("the handle has molecule rows");
+        if (h->nb.on()) return refuse("the handle has neighbour classes");
         if (!p.direct.empty()) return refuse("a bond spans more than the LDS window");
         if (!p.n_acc || p.tiles.empty()) return refuse("no bond samples");
         if (const char *why = gorder::hist_edges_check(edges, n_edges)) return refuse(why);
@@ -2980,6 +3045,91 @@ int gorder_hip_bond_correlation(gorder_hip_handle *h, int64_t *sums, uint64_t *c
     return GORDER_OK;
 }
 
+// ---- order by local composition (neighbour_classes.h, kernels_neighbours.h) ----------------------------------------------
+int gorder_hip_set_neighbour_classes(gorder_hip_handle *h, const uint32_t *centres, const uint32_t *neighbours, uint32_t n_neighbours,
+                                     float radius, uint32_t n_classes) {
+    if (!h) return GORDER_ERR_INVALID_ARGUMENT;
+    const char *who = "gorder_hip_set_neighbour_classes: ";
+    auto refuse = [&](const char *why) { return fail(h, GORDER_ERR_INVALID_ARGUMENT, std::string(who) + why); };
+    if (h->collect_locked) return refuse("only before the first submit or prime, or right after gorder_hip_reset");
+    const Plan &p = h->plan;
+    NeighbourClasses &nb = h->nb;
+    if (n_neighbours) {
+        if (!p.ua_tiles.empty()) return refuse("united-atom molecule types");
+        if (!p.direct.empty()) return refuse("direct items: a bond spans more than the LDS window");
+        if (!p.n_acc || p.tiles.empty() || !p.n_mol_total) return refuse("no bond samples");
+        if (h->extra.maps) return refuse("ordermaps are on");
+        if (h->extra.tw) return refuse("timewise is on");
+        if (h->n_shells) return refuse("the handle has radial shells");       // (ahead of the selection they come with)
+        if (h->extra.geom_kind) return refuse("a geometry selection");
+        if (h->dyn) return refuse("dynamic membrane normals");
+        if (h->d_ntable) return refuse("a manual normal table is set");
+        if (h->manual_frames) return refuse("normals were supplied by gorder_hip_set_normals");
+        if (h->mol.n_groups) return refuse("the handle has molecule rows");
+        if (h->hist_edges) return refuse("the handle has an order histogram");
+        if (const char *why = gorder::neighbour_args_check(centres, p.n_mol_total, neighbours, n_neighbours, radius, n_classes, p.n_atoms))
+            return refuse(why);
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // (a reset still queued may be zeroing the old blocks)
+    nb.n_classes = 0; nb.rows_frames = 0;
+    nb.acc.reset(); nb.rows.reset(); nb.d_centres.reset(); nb.d_neighbours.reset();
+    nb.centres.clear(); nb.neighbours.clear();
+    if (!n_neighbours) return GORDER_OK;
+    nb.centres.assign(centres, centres + p.n_mol_total);
+    nb.neighbours.assign(neighbours, neighbours + n_neighbours);
+    ST_TRY(upload(h, nb.d_centres, nb.centres));
+    ST_TRY(upload(h, nb.d_neighbours, nb.neighbours));
+    // replicas against contention on the global class words, as the ordinary sums have them (gorder::replica_count)
+    ST_TRY(alloc_zeroed(h, nb.acc, (size_t)n_classes * 4u * p.n_acc));
+    uint32_t max_slots = 1;
+    for (const Tile &tile : p.tiles) max_slots = std::max(max_slots, tile.n_slots);
+    const uint32_t planes = h->tables.leaflets.method != GORDER_LEAFLETS_NONE ? 2u : 1u;
+    nb.lds_bytes = (size_t)gorder::class_table_bytes(planes, n_classes, max_slots);
+    nb.direct = nb.force_direct || !gorder::class_table_fits(planes, n_classes, max_slots);
+    nb.radius = radius; nb.thr = local_radius_threshold(radius);
+    nb.n_classes = n_classes;
+    return GORDER_OK;
+}
+
+int gorder_hip_neighbour_classes(gorder_hip_handle *h, int64_t *sums, uint64_t *counts, uint32_t *n_classes) {
+    if (!h) return GORDER_ERR_INVALID_ARGUMENT;
+    const uint32_t nc = h->nb.n_classes;
+    if (n_classes) *n_classes = nc;
+    if (!nc) return GORDER_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const uint32_t n = h->plan.n_acc;
+    HIP_TRY(h, h->nb.acc.fold(h->stream));
+    ST_TRY(gorder_hip_synchronize(h));
+    if (!sums && !counts) return GORDER_OK;
+    std::vector<unsigned long long> raw(h->nb.acc.words);
+    HIP_TRY(h, hipMemcpy(raw.data(), h->nb.acc.acc, raw.size() * sizeof(u64), hipMemcpyDeviceToHost));
+    const bool lf = h->tables.leaflets.method != GORDER_LEAFLETS_NONE;
+    for (uint32_t k = 0; k < nc; k++) {
+        const unsigned long long *r = raw.data() + (size_t)k * 4u * n;
+        for (uint32_t s = 0; s < n; s++) {
+            const int64_t tot = (int64_t)r[s], up = (int64_t)r[n + s];
+            const uint64_t ctot = r[2 * (size_t)n + s], cup = r[3 * (size_t)n + s];
+            const size_t o = (size_t)k * 3u * n + s;
+            if (sums) { sums[o] = tot; sums[o + n] = lf ? up : 0; sums[o + 2 * (size_t)n] = lf ? tot - up : 0; }
+            if (counts) { counts[o] = ctot; counts[o + n] = lf ? cup : 0; counts[o + 2 * (size_t)n] = lf ? ctot - cup : 0; }
+        }
+    }
+    return GORDER_OK;
+}
+
+int gorder_hip_neighbour_class_rows(gorder_hip_handle *h, uint8_t *rows, uint32_t *n_frames, uint32_t *n_mol) {
+    if (!h) return GORDER_ERR_INVALID_ARGUMENT;
+    const uint32_t nf = h->nb.on() ? h->nb.rows_frames : 0u, nm = h->nb.on() ? h->plan.n_mol_total : 0u;
+    if (n_frames) *n_frames = nf;
+    if (n_mol) *n_mol = nm;
+    if (!rows || !nf) return GORDER_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    ST_TRY(gorder_hip_synchronize(h));
+    HIP_TRY(h, hipMemcpy(rows, h->nb.rows, (size_t)nf * nm, hipMemcpyDeviceToHost));
+    return GORDER_OK;
+}
+
 // ---- per-molecule rows (molecule_rows.h, kernels_molrows.h) -------------------------------------------------------------
 int gorder_hip_set_molecule_rows(gorder_hip_handle *h, const uint32_t *group_begin, const uint32_t *slots, uint32_t n_groups) {
     if (!h || (n_groups && (!group_begin || !slots))) return GORDER_ERR_INVALID_ARGUMENT;
@@ -2994,6 +3144,7 @@ int gorder_hip_set_molecule_rows(gorder_hip_handle *h, const uint32_t *group_beg
         if (h->extra.tw) return refuse("timewise is on");
         if (h->n_shells) return refuse("the handle has radial shells");
         if (h->hist_edges) return refuse("the handle has an order histogram");
+        if (h->nb.on()) return refuse("the handle has neighbour classes");
         if (h->extra.geom_kind) return refuse("a geometry selection");
         if (h->dyn) return refuse("dynamic membrane normals");
         if (h->d_ntable) return refuse("a manual normal table is set");
@@ -3166,6 +3317,10 @@ int gorder_hip_reset(gorder_hip_handle *h) {
     h->rep_dirty = false;
     if (h->n_shells) HIP_TRY(h, h->shells.zero_async(h->stream));       // (the radii stay)
     if (h->hist_edges) HIP_TRY(h, h->hist.zero_async(h->stream));      // (the edges stay)
+    if (h->nb.on()) {       // (the setting stays; the class rows are those of a batch of the run that ends here)
+        HIP_TRY(h, h->nb.acc.zero_async(h->stream));
+        h->nb.rows_frames = 0;
+    }
     if (h->corr.on()) {     // (the lags and the ring stay; its planes are history no pair will ask for)
         HIP_TRY(h, h->corr.acc.zero_async(h->stream));
         h->corr.seen = 0;

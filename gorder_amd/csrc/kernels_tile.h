@@ -3,8 +3,8 @@
 // Part of the single translation unit gorder_hip.hip (included there between kernels_common.h and kernels_bonds.h);
 // device code for gfx950 only.  Callers: k_bonds_tiled, k_bonds_gather (kernels_bonds.h), k_bonds_tiled_maps
 // (kernels_extras.h) and k_bonds_tiled_mol (kernels_molrows.h) use all of it; k_bonds_tiled_tw (kernels_extras.h) all but
-// tile_prologue; k_bonds_extras (kernels_extras.h), k_bonds_shells (kernels_radial.h) and k_bonds_dist (kernels_hist.h)
-// fold_tile_sums only.
+// tile_prologue; k_bonds_extras (kernels_extras.h), k_bonds_shells (kernels_radial.h), k_bonds_classes (kernels_neighbours.h)
+// and k_bonds_dist (kernels_hist.h) fold_tile_sums only.
 //
 // Every function is inlined into its kernel, none has a template parameter or a flag that says which kernel called it:
 // where two kernels differ, the difference is at the call.  The contracts:

@@ -9,12 +9,14 @@
 //   united-atom tiles                                                                     -> k_ua_extras<mode> (+ _fast)
 //   per-molecule rows (gorder_hip_set_molecule_rows: bond tiles, no other extra, either cosine)  -> TiledMol
 //   order distributions (gorder_hip_set_order_histogram: bond tiles, at most a geometry selection, either cosine) -> Dist
+//   neighbour classes (gorder_hip_set_neighbour_classes: bond tiles, no other extra, either cosine)              -> Classes
 // A batch speculates (one read for global leaflets and order parameters) only where Tiled or the unstaged TiledTw runs:
 // those are the kernels with a MOM variant, and k_spec_check / k_spec_fixup read what that variant wrote.  TiledMol has
 // none, and no gather variant either: GORDER_HIP_KERNEL=gather does not apply to a handle with rows (the rows need the lanes'
 // ticks in LDS).  With per-molecule rows global leaflets take the two-kernel path (k_leaflets_global, then the order kernel), no
 // one-read speculation.  Dist runs through the extras' sub-range and chunk loop like Shells (its chunks: dist_chunks); it
 // has no MOM or gather variant either, so a handle with a histogram never speculates and GORDER_HIP_KERNEL=gather does not apply.
+// Classes likewise: k_neighbour_counts, then k_bonds_classes per sub-range of that loop, its chunks shells_chunks.
 #ifndef GORDER_ORDER_ROUTE_H
 #define GORDER_ORDER_ROUTE_H
 #include <stddef.h>
@@ -42,8 +44,10 @@ struct OrderRouteIn {
     bool mol_rows = false;
     // an order histogram is set on the handle (it excludes every extra but a geometry selection, united atoms and direct items)
     bool dist = false;
+    // neighbour classes are set on the handle (they exclude every extra, united atoms and direct items)
+    bool classes = false;
 };
-enum class BondFamily { None, Tiled, Gather, TiledTw, TiledMaps, Extras, Shells, TiledMol, Dist };
+enum class BondFamily { None, Tiled, Gather, TiledTw, TiledMaps, Extras, Shells, TiledMol, Dist, Classes };
 
 struct OrderRoute {
     BondFamily family = BondFamily::None;   // what runs over the bond tiles
@@ -63,19 +67,20 @@ inline OrderRoute choose_order_route(const OrderRouteIn &in) {
     const bool staged = in.maps && in.map_staged;
     const bool rows_or_maps_only = !in.geom && !in.dyn_or_manual;
     const bool tiled_out = !in.acos && !in.use_gather && in.frames_per_stage == (int)kStageFrames;   // the tiled staging with a second output
-    r.extras = in.maps || in.tw || in.geom || in.dyn_or_manual || in.dist;     // (Dist launches from the extras' loop)
+    r.extras = in.maps || in.tw || in.geom || in.dyn_or_manual || in.dist || in.classes;     // (Dist and Classes launch from the extras' loop)
     r.maps_only = staged && !in.tw && rows_or_maps_only;
     r.npf = (3u * in.max_window + 6u) / 4u <= 4u * 64u && !in.npf5 ? 4 : 5;      // enough float4 for the widest window (64 threads stage a frame)
     if (!in.bond_tiles) r.family = BondFamily::None;
     else if (in.mol_rows) r.family = BondFamily::TiledMol;
     else if (in.dist) r.family = BondFamily::Dist;
+    else if (in.classes) r.family = BondFamily::Classes;
     else if (!r.extras) r.family = in.use_gather ? BondFamily::Gather : BondFamily::Tiled;
     else if (in.shells) r.family = BondFamily::Shells;
     else if (r.maps_only && tiled_out && !in.maps_gather) r.family = BondFamily::TiledMaps;
     else if (in.tw && (!in.maps || staged) && rows_or_maps_only && tiled_out && in.item_run && !in.tw_gather) r.family = BondFamily::TiledTw;
     else r.family = BondFamily::Extras;
     static const char *const labels[] = {nullptr, "k_bonds_tiled", "k_bonds_gather", "k_bonds_tiled_tw", "k_bonds_tiled_maps", "k_bonds_extras", "k_bonds_shells",
-                                         "k_bonds_tiled_mol", "k_bonds_dist"};
+                                         "k_bonds_tiled_mol", "k_bonds_dist", "k_bonds_classes"};
     r.label = labels[(int)r.family];
     r.tw_maps = r.family == BondFamily::TiledTw && staged;
     r.items_by_slot = r.family == BondFamily::TiledTw || r.family == BondFamily::TiledMaps || (r.family == BondFamily::Extras && staged);
@@ -113,7 +118,7 @@ inline FrameChunks extras_chunks(uint32_t n_frames, uint32_t n_tiles, uint32_t w
     return {fpc, ceil_div(n_frames, fpc)};
 }
 
-// k_bonds_shells: the extras' chunks, none longer than max_chunk frames (the packed words of a workgroup's shell table)
+// k_bonds_shells, k_bonds_classes: the extras' chunks, none longer than max_chunk frames (the packed words of a workgroup's shell table)
 inline FrameChunks shells_chunks(uint32_t n_frames, uint32_t n_tiles, uint32_t wg_target, uint32_t wg_capacity, uint32_t max_chunk) {
     const FrameChunks c = extras_chunks(n_frames, n_tiles, wg_target, wg_capacity, false, false);
     if (c.frames_per_chunk <= max_chunk) return c;

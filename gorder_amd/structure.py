@@ -556,9 +556,15 @@ def radial_profile(shells, radii, groups, analysis: str, min_samples: int = 1) -
     output; NaN below min_samples (and in the upper and lower rows of an analysis without leaflets)."""
     if len(shells) != len(radii):
         raise ValueError(f"{len(shells)} shells for {len(radii)} radii")
+    return _binned_profile(shells, groups, analysis, min_samples)
+
+
+def _binned_profile(results, groups, analysis: str, min_samples: int) -> np.ndarray:
+    """float32 [n_groups, 3, n_results]: per Results of a list (the shells of a radial profile, the classes of
+    HipEngine.neighbour_classes) and group the value of the group's added sums and counts — radial_profile says how."""
     sign = -1.0 if analysis == "aa" else 1.0
-    out = np.full((len(groups), 3, len(shells)), np.nan, dtype=np.float32)
-    for k, res in enumerate(shells):
+    out = np.full((len(groups), 3, len(results)), np.nan, dtype=np.float32)
+    for k, res in enumerate(results):
         sums, counts = np.asarray(res.sums, dtype=np.int64), np.asarray(res.counts, dtype=np.uint64)
         for g, slots in enumerate(groups):
             slots = [int(q) for q in slots]
@@ -566,6 +572,33 @@ def radial_profile(shells, radii, groups, analysis: str, min_samples: int = 1) -
                 v = _mean_ticks(int(sums[w, slots].sum(dtype=np.int64)), int(counts[w, slots].sum(dtype=np.uint64)), min_samples)
                 out[g, w, k] = v if v != v else np.float32(sign * v)
     return out
+
+
+# ---- order by local composition (HipEngine.neighbour_classes): this project's own output, the reference has none ----------
+def neighbour_centres(tables) -> np.ndarray:
+    """One centre atom per molecule for HipEngine.set_neighbour_classes: the concatenated `heads` of the tables' molecule
+    types, uint32 [n_molecules_total], molecule-type-major like the leaflet flags.  ValueError where a type has none (tables
+    without leaflets: name the centres yourself)."""
+    heads = []
+    for k, m in enumerate(tables.molecule_types):
+        if m.heads is None or len(m.heads) != m.n_molecules:
+            raise ValueError(f"molecule type {k} ({getattr(m, 'name', '') or 'unnamed'}) has no heads")
+        heads.append(np.asarray(m.heads, dtype=np.uint32))
+    return np.concatenate(heads) if heads else np.zeros(0, dtype=np.uint32)
+
+
+def class_counts(classes, groups) -> np.ndarray:
+    """Samples uint64 [n_groups, 3, n_classes] of every group (a list of accumulator slots, as error_groups gives them),
+    leaflet and class of HipEngine.neighbour_classes()."""
+    return radial_counts(classes, groups)
+
+
+def class_profile(classes, groups, analysis: str, min_samples: int = 1) -> np.ndarray:
+    """Order parameter by number of neighbours: float32 [n_groups, 3, n_classes] (total, upper, lower) from the per-class
+    Results of HipEngine.neighbour_classes(), the last class holding every count >= n_classes - 1.  The arithmetic is
+    radial_profile's: calc_order's truncating division on the added integers of a group's slots, negated for "aa", NaN below
+    min_samples (and in the upper and lower rows of an analysis without leaflets)."""
+    return _binned_profile(classes, groups, analysis, min_samples)
 
 
 # ---- per-molecule order rows (HipEngine.molecule_rows): this project's own output, the reference has none ----------

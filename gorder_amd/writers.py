@@ -345,6 +345,35 @@ def radial_profile_text(values, counts, radii, names, header: Optional[str] = No
     return "\n".join(out) + "\n"
 
 
+def class_profile_text(values, counts, names, header: Optional[str] = None) -> str:
+    """Order parameters by number of neighbours as text (this project's own layout: the reference has no such file), from the
+    values [n_groups, 3, n_classes] of structure.class_profile and one name per group: one line per class — the number of
+    neighbours, the last class labelled `>= n - 1` —, then per group its full, upper and lower value with four decimals, NaN as
+    `NaN`, under `#` lines that name the columns.  counts [n_groups, 3, n_classes] (structure.class_counts), or None: with
+    them every group gets a fourth column, the samples behind its full value."""
+    n_classes = len(values[0][0]) if len(values) else 0
+    if len(values) != len(names) or any(len(w) != n_classes for v in values for w in v):
+        raise ValueError("values [n_groups, 3, n_classes], one name per group")
+    if counts is not None and (len(counts) != len(names) or any(len(c[0]) != n_classes for c in counts)):
+        raise ValueError("counts [n_groups, 3, n_classes]")
+    out = [header or "# order parameters by number of neighbours",
+           "# class k holds the samples of molecules with k neighbour atoms within the radius of their centre, the last class that many or more",
+           "# column 1: neighbours"]
+    col = 2
+    for name in names:
+        for which in ("full", "upper", "lower") + (("samples",) if counts is not None else ()):
+            out.append(f"# column {col}: {name} {which}")
+            col += 1
+    for k in range(n_classes):
+        cells = [f">={k}" if k == n_classes - 1 else str(k)]
+        for g in range(len(names)):
+            cells += [f"{_fixed(float(values[g][w][k])):>8s}" for w in range(3)]
+            if counts is not None:
+                cells.append(str(int(counts[g][0][k])))
+        out.append(" ".join(cells))
+    return "\n".join(out) + "\n"
+
+
 def molecule_order_text(values, frames, names, header: Optional[str] = None) -> str:
     """Per-molecule order parameters as text (this project's own layout: the reference has no such file), from the values
     [rows, n_groups, n_molecules] of structure.molecule_order, the frames of HipEngine.molecule_rows and one name per group:

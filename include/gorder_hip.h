@@ -679,6 +679,61 @@ int gorder_hip_order_histogram(gorder_hip_handle *h, uint64_t *counts, uint32_t 
 int gorder_hip_set_bond_correlation(gorder_hip_handle *h, const uint32_t *lags, uint32_t n_lags);
 int gorder_hip_bond_correlation(gorder_hip_handle *h, int64_t *sums, uint64_t *counts, uint32_t *n_lags);
 
+/* ---- order by local composition: neighbour counts per molecule, order sums per class of that count -------------------------
+ * Everything above says how ordered a bond is in space, per lipid, as a distribution and in time; this says how a lipid's order
+ * depends on what surrounds it — a POPC tail with 0, 1, 2 or 3 cholesterols within a nanometre.  The reference has no
+ * counterpart.
+ * Per analysed frame and molecule m the handle counts the neighbour atoms q != centres[m] whose distance from the atom
+ *   centres[m] is below `radius`: d = x_q - x_c per component in f32; with handle_pbc the minimum image of every component
+ *   under the frame's own box; d2 = (dx*dx + dy*dy) + dz*dz; counted where sqrtf(d2) < radius, evaluated as d2 < thr with thr
+ *   the value gorder_hip_radial_thresholds gives for the radius.  The distance is three-dimensional and leaflets play no part
+ *   in it; an atom is looked at once, at its minimum image.  The class of (frame, m) is min(count, n_classes - 1).
+ * Every bond sample of molecule m in that frame is booked, with its ordinary tick, on (class, accumulator slot, leaflet) —
+ *   next to everything else the handle does and in the same submit.  Every step is an integer add: the result is exact and
+ *   does not depend on the cut into batches, sub-ranges, chunks or the launch geometry, the classes add up to what
+ *   gorder_hip_finish returns, and gorder_hip_finish returns exactly what it returns without the feature.  A handle that never
+ *   calls the setter queues exactly what it queued before.
+ * The order pass then runs as k_neighbour_counts, then k_bonds_classes (their names in gorder_hip_kernel_time_names /
+ *   _group).  Global leaflets are assigned by their own kernel on this route (no one-read speculation), and
+ *   GORDER_HIP_KERNEL=gather does not apply.  Environment, read once at gorder_hip_create: GORDER_HIP_NB_DIRECT=1 takes
+ *   k_bonds_classes' per-sample global atomics where its LDS table would fit; GORDER_HIP_NB_SUBRANGE=n walks a batch in
+ *   sub-ranges of n frames; GORDER_HIP_NB_ROW_BYTES=n bounds the class bytes on the device (default 1 GiB).  A batch is walked
+ *   in sub-ranges of at most 65 535 frames in any case.
+ * An undefined (NaN) x of a centre or a neighbour atom raises GORDER_ERR_UNDEFINED_POSITION for that frame, the atom's index
+ *   in gorder_hip_last_error_index (the error key has 17 bits for the molecule, as for the heads of the dynamic normals: the
+ *   index is that of the right centre for the first 131 072 molecules; status and frame are right for all).
+ * gorder_hip_set_neighbour_classes: centres [n_molecules_total], one atom index per molecule, molecule-type-major (the order of
+ *   the leaflet flags); neighbours [n_neighbours] strictly ascending atom indices, 1 .. GORDER_NEIGHBOUR_MAX_ATOMS of them;
+ *   radius finite and > 0; 2 <= n_classes <= GORDER_NEIGHBOUR_MAX_CLASSES.  n_neighbours = 0 switches the feature off.
+ *   Accepted before the first submit / prime or right after gorder_hip_reset (the rule of gorder_hip_set_collect).
+ *   GORDER_ERR_INVALID_ARGUMENT, with the reason in gorder_hip_last_error_message, for united-atom molecule types; direct items
+ *   (a bond that spans more than the LDS window); a plan without bond samples; ordermaps; timewise; a geometry selection;
+ *   dynamic membrane normals; a manual normal table or normals supplied by gorder_hip_set_normals; radial shells; molecule
+ *   rows; an order histogram; an index >= n_atoms; neighbours not strictly ascending or too many; classes out of range; a
+ *   bad radius.  A handle with classes in turn refuses gorder_hip_set_normals, gorder_hip_set_manual_normal_table,
+ *   gorder_hip_set_radial_shells, gorder_hip_set_molecule_rows and gorder_hip_set_order_histogram.  Everything else combines:
+ *   both cosine modes, periodic boundaries or none, a static normal on an axis or general, every leaflet method, flip, any
+ *   frequency, any cut into batches, gorder_hip_submit_host / _device and gorder_hip_run_trajectory (device decoding
+ *   included).  Bond correlation is an independent pass: allowed, not tested.
+ * gorder_hip_neighbour_classes: sums int64 / counts uint64 [n_classes][3][n_acc], the planes total / upper / lower as in
+ *   gorder_hip_finish (lower = total - upper; upper and lower are 0 without leaflets).  Waits for the queued batches like
+ *   gorder_hip_radial_shells (a device error of the run is returned).  Either array may be NULL; *n_classes is set when the
+ *   pointer is given (0: the feature is off, nothing is written).  Shards add the arrays on the host — gorder_hip_allreduce
+ *   does NOT carry them.
+ * gorder_hip_neighbour_class_rows: a diagnostic like gorder_hip_spherical_stats — the class bytes [n_frames][n_molecules_total]
+ *   of the LAST submitted batch (of its last sub-range where the batch exceeds 1 GiB of them; none after gorder_hip_reset).
+ *   rows = NULL only returns the sizes; otherwise it waits like gorder_hip_finish.
+ * gorder_hip_reset zeroes the class arrays and keeps the setting.
+ * Not covered: united atoms; lateral or cylinder distance; a same-leaflet restriction; several neighbour groups at once;
+ *   weighting by distance; class rows for a whole run through gorder_hip_set_collect; classes in gorder_hip_allreduce; a cell
+ *   list for the count. */
+#define GORDER_NEIGHBOUR_MAX_ATOMS 16384
+#define GORDER_NEIGHBOUR_MAX_CLASSES 32
+int gorder_hip_set_neighbour_classes(gorder_hip_handle *h, const uint32_t *centres, const uint32_t *neighbours, uint32_t n_neighbours,
+                                     float radius, uint32_t n_classes);
+int gorder_hip_neighbour_classes(gorder_hip_handle *h, int64_t *sums, uint64_t *counts, uint32_t *n_classes);
+int gorder_hip_neighbour_class_rows(gorder_hip_handle *h, uint8_t *rows, uint32_t *n_frames, uint32_t *n_mol);
+
 /* Signed distances (nm) behind those flags, [n_molecules_total] (leaflets.rs:725, 796).  GORDER_LEAFLETS_SPHERICAL: each
  * molecule's head-centre distance (nm, non-negative) in the last assignment frame. */
 int gorder_hip_leaflet_distances(gorder_hip_handle *h, float *distances);
