@@ -14,7 +14,7 @@
 //   SystemSphericalClusterClassification spherical_clustering.rs:42-277, leaflets.rs:1296-1366 -> k_leaflets_spherical
 //   SystemClusterClassification (precise route) clustering.rs:478-800 -> k_cluster_{degrees,lanczos,embed,orient}
 //   LocalClassification + local centres leaflets.rs:661-675, pbc.rs:273-318 -> k_local_{build,rowprefix,decide,flags_rows,flags_todo} (k_local_{bin,scan,scatter,flags}: very large membranes, no box)
-//   should_assign / get_assigned       leaflets.rs:435-441, 1437-1472   (host: assignment-row table)
+//   should_assign / get_assigned       leaflets.rs:435-441, 1437-1472   (host: leaflet_rows.h)
 //   SystemTopology::add / reduce       topology/mod.rs:236-272          (integer sums: order-free)
 //
 // Built for gfx950 only.  No CPU fallback: without a device every entry point fails loudly.
@@ -39,6 +39,7 @@
 #include "collect_store.h"
 #include "device_mem.h"
 #include "replay_rows.h"
+#include "leaflet_rows.h"
 #include "timewise_blocks.h"
 #include "ordermap_final.h"
 #include "order_route.h"
@@ -461,10 +462,6 @@ int alloc_zeroed(gorder_hip_handle *h, RepAcc &r, size_t words) {
     return GORDER_OK;
 }
 
-bool should_assign(uint32_t frequency, uint64_t frame) {   // leaflets.rs:435-441
-    return frequency == 0 ? frame == 0 : (frame % frequency) == 0;
-}
-
 // (slot, molecule, which atom) of an order sample -> atom index in the frame (the payload of UndefinedPosition,
 // errors.rs:136).  Error path only: a linear walk over the plan.
 uint32_t sample_atom(const Plan &p, uint32_t slot, uint32_t mol, uint32_t which) {
@@ -719,194 +716,273 @@ int launch_molecule_rows(gorder_hip_handle *h, const FrameArgs &a, const gorder:
     return GORDER_OK;
 }
 
-// The order kernels of one batch, as `route` has them (every kernel group opens a timing segment of its own).  A combination
-// of template arguments without a kernel (`if constexpr`) is one the route never asks for: tests/test_order_route_cpu.py.
-int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &route) {
-    using gorder::BondFamily, gorder::FrameChunks;
-    const Plan &p = h->plan;
-    const uint32_t n_tiles = (uint32_t)p.tiles.size();
-    const bool ac = (h->tables.flags & GORDER_FLAG_TRIG_ACOS_COS) != 0;
-    if (h->dyn && !h->manual_active) {
-        ST_TRY(run_dynamic_normals(h, a));
-    }
-    if (h->extra.geom_kind) {
-        int st2;
-        if ((st2 = ensure(h, h->d_shapes, (size_t)a.n_frames * 8)) != GORDER_OK) return st2;
-        const gorder_geometry_t &ge = h->tables.geometry;
-        GeomArgs ga{};
-        ga.xyz = a.xyz; ga.box9 = a.box9; ga.n_atoms = a.n_atoms; ga.pbc = a.pbc;
-        ga.kind = ge.kind; ga.reference = ge.reference; ga.orientation = ge.orientation;
-        for (int d = 0; d < 3; d++) { ga.point[d] = ge.point[d]; ga.structure_box[d] = ge.structure_box[d]; }
-        for (int d = 0; d < 2; d++) { ga.xdim[d] = ge.xdim[d]; ga.ydim[d] = ge.ydim[d]; ga.zdim[d] = ge.zdim[d]; ga.span[d] = ge.span[d]; }
-        ga.radius = ge.radius; ga.group = h->d_geom_group; ga.n_group = ge.n_group;
-        ga.shapes = h->d_shapes; ga.err = h->d_err;
-        TIMING_MARK(h, "k_geom_shapes");
-        hipLaunchKernelGGL(k_geom_shapes, dim3(a.n_frames), dim3(256), 0, h->stream, ga);
-        HIP_TRY(h, hipGetLastError());
-    }
-    if (route.family == BondFamily::Tiled || route.family == BondFamily::Gather) {
-        const FrameChunks c = gorder::tiled_chunks(a.n_frames, (uint32_t)h->frames_per_stage, n_tiles, h->wg_target, h->wg_capacity);
-        a.frames_per_chunk = c.frames_per_chunk;
-        const uint64_t grid = (uint64_t)n_tiles * c.n_chunks;
-        if (grid > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "batch too large");
-        const dim3 g((uint32_t)grid), b(kBlock);
-        TIMING_MARK(h, route.label);
-        with_bool(ac, [&](auto AC) { with_bool(a.pbc, [&](auto PBC) { with_bool(a.leaflets, [&](auto LF) {
-            if (route.family == BondFamily::Gather)
-                hipLaunchKernelGGL((k_bonds_gather<4, AC(), PBC(), LF()>), g, b, 0, h->stream, a, a.xyz, a.box9, a.aflags, a.arow,
-                                   h->d_tiles, h->d_items, h->d_tile_slots, n_tiles);
-            else with_npf(route.npf, [&](auto NPF) { with_axis(h->axis, [&](auto AX) { with_bool(route.mom, [&](auto MOM) {
-                if constexpr (LF() || !MOM())
-                    hipLaunchKernelGGL((k_bonds_tiled<4, NPF(), AC(), PBC(), LF(), AX(), MOM()>), g, b, h->lds_bytes, h->stream, a,
-                                       a.xyz, a.box9, a.aflags, a.arow, h->d_tiles, h->d_items, h->d_tile_slots, n_tiles, h->lw);
-            }); }); });
+// ---- the order kernels of one batch, as `route` has them: launch_orders, at the end of this section, is the dispatcher; every
+// kernel group opens a timing segment of its own.  A combination of template arguments without a kernel (`if constexpr`) is
+// one the route never asks for: tests/test_order_route_cpu.py.
+bool literal_cosine(const gorder_hip_handle *h) { return (h->tables.flags & GORDER_FLAG_TRIG_ACOS_COS) != 0; }
+
+// the shape of the geometry selection in every frame of the batch -> h->d_shapes
+int launch_geometry_shapes(gorder_hip_handle *h, const FrameArgs &a) {
+    ST_TRY(ensure(h, h->d_shapes, (size_t)a.n_frames * 8));
+    const gorder_geometry_t &ge = h->tables.geometry;
+    GeomArgs ga{};
+    ga.xyz = a.xyz; ga.box9 = a.box9; ga.n_atoms = a.n_atoms; ga.pbc = a.pbc;
+    ga.kind = ge.kind; ga.reference = ge.reference; ga.orientation = ge.orientation;
+    for (int d = 0; d < 3; d++) { ga.point[d] = ge.point[d]; ga.structure_box[d] = ge.structure_box[d]; }
+    for (int d = 0; d < 2; d++) { ga.xdim[d] = ge.xdim[d]; ga.ydim[d] = ge.ydim[d]; ga.zdim[d] = ge.zdim[d]; ga.span[d] = ge.span[d]; }
+    ga.radius = ge.radius; ga.group = h->d_geom_group; ga.n_group = ge.n_group;
+    ga.shapes = h->d_shapes; ga.err = h->d_err;
+    TIMING_MARK(h, "k_geom_shapes");
+    hipLaunchKernelGGL(k_geom_shapes, dim3(a.n_frames), dim3(256), 0, h->stream, ga);
+    HIP_TRY(h, hipGetLastError());
+    return GORDER_OK;
+}
+
+// Tiled and Gather: one launch over the whole batch (its chunking stays in `a`)
+int launch_tiled(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &route) {
+    const uint32_t n_tiles = (uint32_t)h->plan.tiles.size();
+    const gorder::FrameChunks c = gorder::tiled_chunks(a.n_frames, (uint32_t)h->frames_per_stage, n_tiles, h->wg_target, h->wg_capacity);
+    a.frames_per_chunk = c.frames_per_chunk;
+    const uint64_t grid = (uint64_t)n_tiles * c.n_chunks;
+    if (grid > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "batch too large");
+    const dim3 g((uint32_t)grid), b(kBlock);
+    TIMING_MARK(h, route.label);
+    with_bool(literal_cosine(h), [&](auto AC) { with_bool(a.pbc, [&](auto PBC) { with_bool(a.leaflets, [&](auto LF) {
+        if (route.family == gorder::BondFamily::Gather)
+            hipLaunchKernelGGL((k_bonds_gather<4, AC(), PBC(), LF()>), g, b, 0, h->stream, a, a.xyz, a.box9, a.aflags, a.arow,
+                               h->d_tiles, h->d_items, h->d_tile_slots, n_tiles);
+        else with_npf(route.npf, [&](auto NPF) { with_axis(h->axis, [&](auto AX) { with_bool(route.mom, [&](auto MOM) {
+            if constexpr (LF() || !MOM())
+                hipLaunchKernelGGL((k_bonds_tiled<4, NPF(), AC(), PBC(), LF(), AX(), MOM()>), g, b, h->lds_bytes, h->stream, a,
+                                   a.xyz, a.box9, a.aflags, a.arow, h->d_tiles, h->d_items, h->d_tile_slots, n_tiles, h->lw);
         }); }); });
-        HIP_TRY(h, hipGetLastError());
-    }
-    if (route.family == BondFamily::TiledMol) {
-        ST_TRY(launch_molecule_rows(h, a, route));
-    }
-    if (route.extras || route.ua_mode >= 0) {
-        // scatter-bound modes: plain per-sample kernels (see "Extras" above)
-        ExtraArgs e = h->extra;
-        e.tw_sums = h->d_tw_sums; e.tw_cnts = h->d_tw_cnts; e.tw_row0 = h->n_frames;
-        e.shapes = h->d_shapes; e.inv_box = nullptr;
-        if (route.ua_fast && a.pbc) {      // 1 / box edge per frame, once per frame instead of once per lane and frame
-            int st3;
-            if ((st3 = ensure(h, h->d_inv_box, (size_t)a.n_frames * 8)) != GORDER_OK) return st3;
-            hipLaunchKernelGGL(k_inv_box, dim3((4u * a.n_frames + 255u) / 256u), dim3(256), 0, h->stream, a.box9, a.n_frames, h->d_inv_box);
-            e.inv_box = h->d_inv_box;
-        }
-        e.dyn = (h->dyn || h->manual_active) ? h->d_dyn_normals : nullptr;
-        const bool staged = route.map_accumulate;
-        const size_t rec_per_frame = std::max(p.ua_tiles.size() * 3u, route.extras ? p.tiles.size() : (size_t)0) * kBlock;   // staged words per frame
-        uint32_t sub = gorder::map_subrange(a.n_frames, e.maps != 0, staged, h->map_fold_limit, h->map_max_mol, rec_per_frame);
-        // neighbour classes: the class rows hold the whole batch where it fits them (gorder_hip_neighbour_class_rows then returns
-        // it), else one sub-range at a time; a sub-range is one launch of k_neighbour_counts, a frame per row of gridDim.y
-        const bool classes = route.family == BondFamily::Classes;
-        bool class_rows_whole = false;
-        if (classes) {
-            class_rows_whole = gorder::class_rows_whole(a.n_frames, p.n_mol_total, h->nb.row_bytes);
-            sub = gorder::class_subrange(a.n_frames, p.n_mol_total, h->nb.forced_subrange, h->nb.row_bytes);
-            ST_TRY(ensure(h, h->nb.rows, (size_t)(class_rows_whole ? a.n_frames : sub) * p.n_mol_total));
-        }
-        if (staged) {
-            ST_TRY(ensure(h, h->d_map_rec, rec_per_frame * (((size_t)sub + 15) / 16 * 16)));
-        }
-        for (uint32_t lo = 0; lo < a.n_frames; lo += sub) {
-            const uint32_t hi = std::min(a.n_frames, lo + sub), nf = hi - lo;
-            if (e.maps) {
-                const uint64_t cost = (uint64_t)nf * h->map_max_mol;
-                if (h->map_pending + cost >= h->map_fold_limit) {
-                    ST_TRY(fold_maps(h));
-                }
-                h->map_pending += cost;
-            }
-            for (int pass = 0; pass < 2; pass++) {      // the bond tiles, then the united-atom tiles
-                const uint32_t nt = pass == 0 ? (route.extras ? n_tiles : 0u) : (uint32_t)p.ua_tiles.size();
-                if (!nt) continue;
-                const FrameChunks c = pass == 0 && (route.family == BondFamily::Shells || classes)
-                                          ? gorder::shells_chunks(nf, nt, h->wg_target, h->wg_capacity, kShellChunkMax)
-                                      : pass == 0 && route.family == BondFamily::Dist
-                                          ? gorder::dist_chunks(nf, nt, h->wg_target, h->wg_capacity, h->hist_direct ? 0u : (uint32_t)h->hist_table_words, h->hist_samples_per_word, kDistChunkMax)
-                                          : gorder::extras_chunks(nf, nt, h->wg_target, h->wg_capacity, staged, pass == 0 && route.family == BondFamily::TiledTw);
-                FrameArgs b = a;
-                b.frame0 = lo; b.n_frames = hi; b.frames_per_chunk = c.frames_per_chunk;
-                e.map_rec = staged ? h->d_map_rec : nullptr;
-                e.item_run = pass == 0 ? h->d_item_run : h->d_ua_item_run;      // (bond tiles: k_bonds_tiled_tw only)
-                e.rec_frame0 = lo; e.rec_stride = (nf + 15u) / 16u * 16u;
-                const dim3 g(pass == 0 ? nt * c.n_chunks : (nt * c.n_chunks + 7u) / 8u * 8u), blk(kBlock);   // united atoms: see the XCD mapping in k_ua_extras
-                if (pass == 0) {
-                    const Item *items = route.items_by_slot ? h->d_items_by_slot : h->d_items;
-                    ClassArgs ca{};
-                    if (classes) {      // the class of every (frame, molecule) of the sub-range, ahead of the kernel that reads it
-                        NeighbourClasses &nb = h->nb;
-                        ca.centres = nb.d_centres; ca.neighbours = nb.d_neighbours; ca.n_neighbours = (uint32_t)nb.neighbours.size();
-                        ca.thr = nb.thr; ca.n = nb.n_classes; ca.rows = nb.rows; ca.row_base = class_rows_whole ? 0u : lo;
-                        ca.axis = h->axis; ca.rep = nb.acc.rep; ca.n_rep = nb.acc.n_rep;
-                        nb.rows_frames = class_rows_whole ? a.n_frames : nf;
-                        TIMING_MARK(h, "k_neighbour_counts");
-                        hipLaunchKernelGGL(k_neighbour_counts, dim3((p.n_mol_total + 255u) / 256u, nf), dim3(256), 0, h->stream, ca, b.xyz, b.box9,
-                                           b.n_atoms, p.n_mol_total, b.pbc, lo, h->d_err);
-                    }
-                    TIMING_MARK(h, route.label);
-                    if (classes) {
-                        // the table of the widest tile, or the [2][256] u64 + [2][256] u32 of the direct route's reduction
-                        const size_t lds = h->nb.direct ? (size_t)kBlock * 24u : h->nb.lds_bytes;
-                        with_bool(ac, [&](auto AC) { with_bool(h->nb.direct, [&](auto DIRECT) {
-                            hipLaunchKernelGGL((k_bonds_classes<AC(), DIRECT()>), g, blk, lds, h->stream, b, ca, b.xyz, b.box9, b.aflags, b.arow,
-                                               h->d_tiles, items, h->d_tile_slots, nt);
-                        }); });
-                    } else if (route.family == BondFamily::Shells) {
-                        ShellArgs sa{};
-                        sa.n = h->n_shells; sa.rep = h->shells.rep; sa.n_rep = h->shells.n_rep;
-                        for (uint32_t k = 0; k < GORDER_RADIAL_MAX_SHELLS; k++) sa.thr[k] = k < h->n_shells ? h->shell_thr[k] : INFINITY;
-                        // the table of the widest tile, or the [2][256] u64 + [2][256] u32 of the direct route's reduction
-                        const size_t lds = h->shell_direct ? (size_t)kBlock * 24u : h->shell_lds_bytes;
-                        with_bool(ac, [&](auto AC) { with_bool(h->shell_direct, [&](auto DIRECT) {
-                            hipLaunchKernelGGL((k_bonds_shells<AC(), DIRECT()>), g, blk, lds, h->stream, b, e, sa, b.xyz, b.box9, b.aflags, b.arow,
-                                               h->d_tiles, items, h->d_tile_slots, nt);
-                        }); });
-                    } else if (route.family == BondFamily::Dist) {
-                        DistArgs da{};
-                        da.n_edges = h->hist_edges; da.edges = h->d_hist_edges; da.rep = h->hist.rep; da.n_rep = h->hist.n_rep;
-                        // the edges, then the table of the widest tile or the ordinary sums' reduction, whichever is larger
-                        const size_t lds = kDistEdgeBytes + std::max<size_t>(kDistReduceBytes, h->hist_direct ? 0u : h->hist_table_words * sizeof(uint32_t));
-                        with_bool(ac, [&](auto AC) { with_bool(h->hist_direct, [&](auto DIRECT) {
-                            hipLaunchKernelGGL((k_bonds_dist<AC(), DIRECT()>), g, blk, lds, h->stream, b, e, da, b.xyz, b.box9, b.aflags, b.arow,
-                                               h->d_tiles, items, h->d_tile_slots, nt);
-                        }); });
-                    } else if (route.family == BondFamily::Extras)
-                        with_bool(ac, [&](auto AC) { with_bool(route.maps_only, [&](auto MO) {
-                            hipLaunchKernelGGL((k_bonds_extras<AC(), MO()>), g, blk, 0, h->stream, b, e, b.xyz, b.box9, b.aflags, b.arow,
-                                               h->d_tiles, items, h->d_tile_slots, nt);
-                        }); });
-                    else    // the tiled kernel with a second output: the stage's ticks (k_bonds_tiled_tw) or its map words (k_bonds_tiled_maps)
-                        with_npf(route.npf, [&](auto NPF) { with_bool(b.pbc, [&](auto PBC) { with_bool(b.leaflets, [&](auto LF) { with_axis(h->axis, [&](auto AX) {
-                            if (route.family == BondFamily::TiledMaps)
-                                hipLaunchKernelGGL((k_bonds_tiled_maps<NPF(), PBC(), LF(), AX()>), g, blk, h->lds_bytes, h->stream, b, e, b.xyz,
-                                                   b.box9, b.aflags, b.arow, h->d_tiles, items, h->d_tile_slots, nt, h->lw);
-                            else with_bool(route.tw_maps, [&](auto MAPS) { with_bool(route.mom, [&](auto MOM) {
-                                if constexpr (!MOM() || (LF() && !MAPS()))
-                                    hipLaunchKernelGGL((k_bonds_tiled_tw<NPF(), PBC(), LF(), AX(), MAPS(), MOM()>), g, blk, h->lds_bytes, h->stream, b, e,
-                                                       b.xyz, b.box9, b.aflags, b.arow, h->d_tiles, items, h->d_tile_slots, nt, h->lw);
-                            }); });
-                        }); }); }); });
-                } else {
-                    TIMING_MARK(h, "k_ua_extras");
-                    with_bool(ac, [&](auto AC) { with_bool(route.ua_fast, [&](auto FAST) { with_int<0, 1, 2, 3>(route.ua_mode, [&](auto MODE) {
-                        if constexpr (FAST() && !AC())
-                            hipLaunchKernelGGL((k_ua_extras_fast<MODE()>), g, blk, 0, h->stream, b, e, b.xyz, b.box9, b.aflags, b.arow,
-                                               h->d_ua_tiles, h->d_ua_items, h->d_ua_tile_slots, nt, (const float *)e.inv_box);
-                        else if constexpr (!FAST())
-                            hipLaunchKernelGGL((k_ua_extras<AC(), MODE()>), g, blk, 0, h->stream, b, e, b.xyz, b.box9, b.aflags, b.arow,
-                                               h->d_ua_tiles, h->d_ua_items, h->d_ua_tile_slots, nt, (const float *)nullptr);
-                    }); }); });
-                }
-                if (staged) {   // second step: slot-major accumulation of the staged samples in LDS
-                    const uint32_t planes = h->tables.leaflets.method != GORDER_LEAFLETS_NONE ? 2u : 1u;
-                    const uint32_t ntm = h->map_nx * h->map_ny, n_words = planes * ntm;
-                    const char *ev = getenv("GORDER_HIP_MAP_CHUNKS");
-                    const FrameChunks m = gorder::map_chunks(nf, p.n_acc, ev ? (uint32_t)std::max(1, atoi(ev)) : 0u);
-                    TIMING_MARK(h, "k_map_accumulate");
-                    hipLaunchKernelGGL(k_map_accumulate, dim3(p.n_acc * m.n_chunks), dim3(1024), n_words * sizeof(unsigned long long),
-                                       h->stream, h->d_map_rec, pass == 0 ? h->d_runs : h->d_ua_runs,
-                                       pass == 0 ? h->d_run_begin : h->d_ua_run_begin, p.n_acc, nf, e.rec_stride, m.frames_per_chunk,
-                                       pass == 0 ? 1u : 3u, n_words, ntm, h->d_map_packed, p.n_acc);
-                }
-                HIP_TRY(h, hipGetLastError());
-            }
-        }
-    }
-    if (route.direct) {
-        const uint32_t n_items = (uint32_t)p.direct.size(), bpc = (n_items + kBlock - 1) / kBlock;
-        const FrameChunks c = gorder::direct_chunks(a.n_frames, bpc, h->wg_target);
+    }); }); });
+    HIP_TRY(h, hipGetLastError());
+    return GORDER_OK;
+}
+
+// One sub-range [lo, hi) of the batch's frames in the loop of the scatter-bound kernels: what its passes are handed
+struct SubRange {
+    const FrameArgs &a;                 // the batch
+    const gorder::OrderRoute &route;
+    uint32_t lo, hi;
+    bool class_rows_whole;              // neighbour classes: the class rows hold the whole batch, not this sub-range alone
+    uint32_t nf() const { return hi - lo; }
+    FrameArgs frames(const gorder::FrameChunks &c) const {      // the batch's arguments narrowed to the sub-range, cut as `c` says
         FrameArgs b = a;
-        b.frames_per_chunk = c.frames_per_chunk;
-        TIMING_MARK(h, "k_bonds_direct");
-        with_bool(ac, [&](auto AC) { hipLaunchKernelGGL(k_bonds_direct<AC()>, dim3(bpc * c.n_chunks), dim3(kBlock), 0, h->stream, b, h->d_direct, n_items, bpc); });
-        HIP_TRY(h, hipGetLastError());
+        b.frame0 = lo; b.n_frames = hi; b.frames_per_chunk = c.frames_per_chunk;
+        return b;
     }
+};
+const Item *bond_items(const gorder_hip_handle *h, const gorder::OrderRoute &route) { return route.items_by_slot ? h->d_items_by_slot : h->d_items; }
+
+// the class of every (frame, molecule) of the sub-range (k_neighbour_counts, a frame per row of gridDim.y), then the kernel that reads it
+int launch_classes(gorder_hip_handle *h, const SubRange &s) {
+    const Plan &p = h->plan;
+    NeighbourClasses &nb = h->nb;
+    const uint32_t nt = (uint32_t)p.tiles.size(), nf = s.nf();
+    const gorder::FrameChunks c = gorder::shells_chunks(nf, nt, h->wg_target, h->wg_capacity, kShellChunkMax);
+    FrameArgs b = s.frames(c);
+    ClassArgs ca{};
+    ca.centres = nb.d_centres; ca.neighbours = nb.d_neighbours; ca.n_neighbours = (uint32_t)nb.neighbours.size();
+    ca.thr = nb.thr; ca.n = nb.n_classes; ca.rows = nb.rows; ca.row_base = s.class_rows_whole ? 0u : s.lo;
+    ca.axis = h->axis; ca.rep = nb.acc.rep; ca.n_rep = nb.acc.n_rep;
+    nb.rows_frames = s.class_rows_whole ? s.a.n_frames : nf;
+    TIMING_MARK(h, "k_neighbour_counts");
+    hipLaunchKernelGGL(k_neighbour_counts, dim3((p.n_mol_total + 255u) / 256u, nf), dim3(256), 0, h->stream, ca, b.xyz, b.box9,
+                       b.n_atoms, p.n_mol_total, b.pbc, s.lo, h->d_err);
+    TIMING_MARK(h, s.route.label);
+    // the table of the widest tile, or the [2][256] u64 + [2][256] u32 of the direct route's reduction
+    const size_t lds = nb.direct ? (size_t)kBlock * 24u : nb.lds_bytes;
+    with_bool(literal_cosine(h), [&](auto AC) { with_bool(nb.direct, [&](auto DIRECT) {
+        hipLaunchKernelGGL((k_bonds_classes<AC(), DIRECT()>), dim3(nt * c.n_chunks), dim3(kBlock), lds, h->stream, b, ca, b.xyz, b.box9,
+                           b.aflags, b.arow, h->d_tiles, bond_items(h, s.route), h->d_tile_slots, nt);
+    }); });
+    return GORDER_OK;
+}
+
+int launch_shells(gorder_hip_handle *h, const SubRange &s, const ExtraArgs &e) {
+    const uint32_t nt = (uint32_t)h->plan.tiles.size();
+    const gorder::FrameChunks c = gorder::shells_chunks(s.nf(), nt, h->wg_target, h->wg_capacity, kShellChunkMax);
+    FrameArgs b = s.frames(c);
+    ShellArgs sa{};
+    sa.n = h->n_shells; sa.rep = h->shells.rep; sa.n_rep = h->shells.n_rep;
+    for (uint32_t k = 0; k < GORDER_RADIAL_MAX_SHELLS; k++) sa.thr[k] = k < h->n_shells ? h->shell_thr[k] : INFINITY;
+    // the table of the widest tile, or the [2][256] u64 + [2][256] u32 of the direct route's reduction
+    const size_t lds = h->shell_direct ? (size_t)kBlock * 24u : h->shell_lds_bytes;
+    TIMING_MARK(h, s.route.label);
+    with_bool(literal_cosine(h), [&](auto AC) { with_bool(h->shell_direct, [&](auto DIRECT) {
+        hipLaunchKernelGGL((k_bonds_shells<AC(), DIRECT()>), dim3(nt * c.n_chunks), dim3(kBlock), lds, h->stream, b, e, sa, b.xyz, b.box9,
+                           b.aflags, b.arow, h->d_tiles, bond_items(h, s.route), h->d_tile_slots, nt);
+    }); });
+    return GORDER_OK;
+}
+
+int launch_dist(gorder_hip_handle *h, const SubRange &s, const ExtraArgs &e) {
+    const uint32_t nt = (uint32_t)h->plan.tiles.size();
+    const gorder::FrameChunks c = gorder::dist_chunks(s.nf(), nt, h->wg_target, h->wg_capacity, h->hist_direct ? 0u : (uint32_t)h->hist_table_words,
+                                                      h->hist_samples_per_word, kDistChunkMax);
+    FrameArgs b = s.frames(c);
+    DistArgs da{};
+    da.n_edges = h->hist_edges; da.edges = h->d_hist_edges; da.rep = h->hist.rep; da.n_rep = h->hist.n_rep;
+    // the edges, then the table of the widest tile or the ordinary sums' reduction, whichever is larger
+    const size_t lds = kDistEdgeBytes + std::max<size_t>(kDistReduceBytes, h->hist_direct ? 0u : h->hist_table_words * sizeof(uint32_t));
+    TIMING_MARK(h, s.route.label);
+    with_bool(literal_cosine(h), [&](auto AC) { with_bool(h->hist_direct, [&](auto DIRECT) {
+        hipLaunchKernelGGL((k_bonds_dist<AC(), DIRECT()>), dim3(nt * c.n_chunks), dim3(kBlock), lds, h->stream, b, e, da, b.xyz, b.box9,
+                           b.aflags, b.arow, h->d_tiles, bond_items(h, s.route), h->d_tile_slots, nt);
+    }); });
+    return GORDER_OK;
+}
+
+// scatter-bound modes: the plain per-sample kernel (see "Extras" above)
+int launch_extras(gorder_hip_handle *h, const SubRange &s, const ExtraArgs &e) {
+    const uint32_t nt = (uint32_t)h->plan.tiles.size();
+    const gorder::FrameChunks c = gorder::extras_chunks(s.nf(), nt, h->wg_target, h->wg_capacity, s.route.map_accumulate, false);
+    FrameArgs b = s.frames(c);
+    TIMING_MARK(h, s.route.label);
+    with_bool(literal_cosine(h), [&](auto AC) { with_bool(s.route.maps_only, [&](auto MO) {
+        hipLaunchKernelGGL((k_bonds_extras<AC(), MO()>), dim3(nt * c.n_chunks), dim3(kBlock), 0, h->stream, b, e, b.xyz, b.box9, b.aflags,
+                           b.arow, h->d_tiles, bond_items(h, s.route), h->d_tile_slots, nt);
+    }); });
+    return GORDER_OK;
+}
+
+// TiledTw and TiledMaps: the tiled kernel with a second output, the stage's ticks (k_bonds_tiled_tw) or its map words (k_bonds_tiled_maps)
+int launch_tiled_out(gorder_hip_handle *h, const SubRange &s, const ExtraArgs &e) {
+    const gorder::OrderRoute &route = s.route;
+    const uint32_t nt = (uint32_t)h->plan.tiles.size();
+    const gorder::FrameChunks c = gorder::extras_chunks(s.nf(), nt, h->wg_target, h->wg_capacity, route.map_accumulate,
+                                                        route.family == gorder::BondFamily::TiledTw);
+    FrameArgs b = s.frames(c);
+    const dim3 g(nt * c.n_chunks), blk(kBlock);
+    const Item *items = bond_items(h, route);
+    TIMING_MARK(h, route.label);
+    with_npf(route.npf, [&](auto NPF) { with_bool(b.pbc, [&](auto PBC) { with_bool(b.leaflets, [&](auto LF) { with_axis(h->axis, [&](auto AX) {
+        if (route.family == gorder::BondFamily::TiledMaps)
+            hipLaunchKernelGGL((k_bonds_tiled_maps<NPF(), PBC(), LF(), AX()>), g, blk, h->lds_bytes, h->stream, b, e, b.xyz,
+                               b.box9, b.aflags, b.arow, h->d_tiles, items, h->d_tile_slots, nt, h->lw);
+        else with_bool(route.tw_maps, [&](auto MAPS) { with_bool(route.mom, [&](auto MOM) {
+            if constexpr (!MOM() || (LF() && !MAPS()))
+                hipLaunchKernelGGL((k_bonds_tiled_tw<NPF(), PBC(), LF(), AX(), MAPS(), MOM()>), g, blk, h->lds_bytes, h->stream, b, e,
+                                   b.xyz, b.box9, b.aflags, b.arow, h->d_tiles, items, h->d_tile_slots, nt, h->lw);
+        }); });
+    }); }); }); });
+    return GORDER_OK;
+}
+
+// second step of a staged pass: slot-major accumulation of the sub-range's staged samples in LDS (`per_item` samples an item)
+int launch_map_accumulate(gorder_hip_handle *h, const SubRange &s, uint32_t rec_stride, const gorder::MapRun *runs,
+                          const uint32_t *run_begin, uint32_t per_item) {
+    const uint32_t n_acc = h->plan.n_acc;
+    const uint32_t planes = h->tables.leaflets.method != GORDER_LEAFLETS_NONE ? 2u : 1u;
+    const uint32_t ntm = h->map_nx * h->map_ny, n_words = planes * ntm;
+    const char *ev = getenv("GORDER_HIP_MAP_CHUNKS");
+    const gorder::FrameChunks m = gorder::map_chunks(s.nf(), n_acc, ev ? (uint32_t)std::max(1, atoi(ev)) : 0u);
+    TIMING_MARK(h, "k_map_accumulate");
+    hipLaunchKernelGGL(k_map_accumulate, dim3(n_acc * m.n_chunks), dim3(1024), n_words * sizeof(unsigned long long), h->stream,
+                       h->d_map_rec, runs, run_begin, n_acc, s.nf(), rec_stride, m.frames_per_chunk, per_item, n_words, ntm,
+                       h->d_map_packed, n_acc);
+    return GORDER_OK;
+}
+
+// the bond tiles of a sub-range, by family
+int launch_bond_pass(gorder_hip_handle *h, const SubRange &s, ExtraArgs &e) {
+    using gorder::BondFamily;
+    e.item_run = h->d_item_run;      // (k_bonds_tiled_tw only)
+    switch (s.route.family) {
+    case BondFamily::Classes: ST_TRY(launch_classes(h, s)); break;
+    case BondFamily::Shells: ST_TRY(launch_shells(h, s, e)); break;
+    case BondFamily::Dist: ST_TRY(launch_dist(h, s, e)); break;
+    case BondFamily::Extras: ST_TRY(launch_extras(h, s, e)); break;
+    default: ST_TRY(launch_tiled_out(h, s, e)); break;
+    }
+    if (s.route.map_accumulate) ST_TRY(launch_map_accumulate(h, s, e.rec_stride, h->d_runs, h->d_run_begin, 1u));
+    HIP_TRY(h, hipGetLastError());
+    return GORDER_OK;
+}
+
+// ... and its united-atom tiles
+int launch_ua_pass(gorder_hip_handle *h, const SubRange &s, ExtraArgs &e) {
+    const gorder::OrderRoute &route = s.route;
+    const uint32_t nt = (uint32_t)h->plan.ua_tiles.size();
+    const gorder::FrameChunks c = gorder::extras_chunks(s.nf(), nt, h->wg_target, h->wg_capacity, route.map_accumulate, false);
+    FrameArgs b = s.frames(c);
+    e.item_run = h->d_ua_item_run;
+    const dim3 g((nt * c.n_chunks + 7u) / 8u * 8u), blk(kBlock);   // see the XCD mapping in k_ua_extras
+    TIMING_MARK(h, "k_ua_extras");
+    with_bool(literal_cosine(h), [&](auto AC) { with_bool(route.ua_fast, [&](auto FAST) { with_int<0, 1, 2, 3>(route.ua_mode, [&](auto MODE) {
+        if constexpr (FAST() && !AC())
+            hipLaunchKernelGGL((k_ua_extras_fast<MODE()>), g, blk, 0, h->stream, b, e, b.xyz, b.box9, b.aflags, b.arow,
+                               h->d_ua_tiles, h->d_ua_items, h->d_ua_tile_slots, nt, (const float *)e.inv_box);
+        else if constexpr (!FAST())
+            hipLaunchKernelGGL((k_ua_extras<AC(), MODE()>), g, blk, 0, h->stream, b, e, b.xyz, b.box9, b.aflags, b.arow,
+                               h->d_ua_tiles, h->d_ua_items, h->d_ua_tile_slots, nt, (const float *)nullptr);
+    }); }); });
+    if (route.map_accumulate) ST_TRY(launch_map_accumulate(h, s, e.rec_stride, h->d_ua_runs, h->d_ua_run_begin, 3u));
+    HIP_TRY(h, hipGetLastError());
+    return GORDER_OK;
+}
+
+// Everything that scatters (route.extras, or united atoms): the bond tiles, then the united-atom tiles, a sub-range of the
+// batch's frames at a time — as many as the packed map words, the staging block or the class rows hold
+int launch_scatter_passes(gorder_hip_handle *h, const FrameArgs &a, const gorder::OrderRoute &route) {
+    const Plan &p = h->plan;
+    ExtraArgs e = h->extra;
+    e.tw_sums = h->d_tw_sums; e.tw_cnts = h->d_tw_cnts; e.tw_row0 = h->n_frames;
+    e.shapes = h->d_shapes; e.inv_box = nullptr;
+    if (route.ua_fast && a.pbc) {      // 1 / box edge per frame, once per frame instead of once per lane and frame
+        ST_TRY(ensure(h, h->d_inv_box, (size_t)a.n_frames * 8));
+        hipLaunchKernelGGL(k_inv_box, dim3((4u * a.n_frames + 255u) / 256u), dim3(256), 0, h->stream, a.box9, a.n_frames, h->d_inv_box);
+        e.inv_box = h->d_inv_box;
+    }
+    e.dyn = (h->dyn || h->manual_active) ? h->d_dyn_normals : nullptr;
+    const bool staged = route.map_accumulate;
+    const size_t rec_per_frame = std::max(p.ua_tiles.size() * 3u, route.extras ? p.tiles.size() : (size_t)0) * kBlock;   // staged words per frame
+    uint32_t sub = gorder::map_subrange(a.n_frames, e.maps != 0, staged, h->map_fold_limit, h->map_max_mol, rec_per_frame);
+    // neighbour classes: the class rows hold the whole batch where it fits them (gorder_hip_neighbour_class_rows then returns
+    // it), else one sub-range at a time
+    bool class_rows_whole = false;
+    if (route.family == gorder::BondFamily::Classes) {
+        class_rows_whole = gorder::class_rows_whole(a.n_frames, p.n_mol_total, h->nb.row_bytes);
+        sub = gorder::class_subrange(a.n_frames, p.n_mol_total, h->nb.forced_subrange, h->nb.row_bytes);
+        ST_TRY(ensure(h, h->nb.rows, (size_t)(class_rows_whole ? a.n_frames : sub) * p.n_mol_total));
+    }
+    if (staged) ST_TRY(ensure(h, h->d_map_rec, rec_per_frame * (((size_t)sub + 15) / 16 * 16)));
+    e.map_rec = staged ? h->d_map_rec : nullptr;
+    for (uint32_t lo = 0; lo < a.n_frames; lo += sub) {
+        const SubRange s{a, route, lo, std::min(a.n_frames, lo + sub), class_rows_whole};
+        if (e.maps) {
+            const uint64_t cost = (uint64_t)s.nf() * h->map_max_mol;
+            if (h->map_pending + cost >= h->map_fold_limit) ST_TRY(fold_maps(h));
+            h->map_pending += cost;
+        }
+        e.rec_frame0 = lo; e.rec_stride = (s.nf() + 15u) / 16u * 16u;
+        if (route.extras && !p.tiles.empty()) ST_TRY(launch_bond_pass(h, s, e));
+        if (!p.ua_tiles.empty()) ST_TRY(launch_ua_pass(h, s, e));
+    }
+    return GORDER_OK;
+}
+
+int launch_bonds_direct(gorder_hip_handle *h, const FrameArgs &a) {
+    const uint32_t n_items = (uint32_t)h->plan.direct.size(), bpc = (n_items + kBlock - 1) / kBlock;
+    const gorder::FrameChunks c = gorder::direct_chunks(a.n_frames, bpc, h->wg_target);
+    FrameArgs b = a;
+    b.frames_per_chunk = c.frames_per_chunk;
+    TIMING_MARK(h, "k_bonds_direct");
+    with_bool(literal_cosine(h), [&](auto AC) { hipLaunchKernelGGL(k_bonds_direct<AC()>, dim3(bpc * c.n_chunks), dim3(kBlock), 0, h->stream, b, h->d_direct, n_items, bpc); });
+    HIP_TRY(h, hipGetLastError());
+    return GORDER_OK;
+}
+
+int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &route) {
+    using gorder::BondFamily;
+    if (h->dyn && !h->manual_active) ST_TRY(run_dynamic_normals(h, a));
+    if (h->extra.geom_kind) ST_TRY(launch_geometry_shapes(h, a));
+    if (route.family == BondFamily::Tiled || route.family == BondFamily::Gather) ST_TRY(launch_tiled(h, a, route));
+    if (route.family == BondFamily::TiledMol) ST_TRY(launch_molecule_rows(h, a, route));
+    if (route.extras || route.ua_mode >= 0) ST_TRY(launch_scatter_passes(h, a, route));
+    if (route.direct) ST_TRY(launch_bonds_direct(h, a));
     return GORDER_OK;       // (the frames are counted by k_batch_end, which also closes the batch's timing chain)
 }
 
@@ -1895,11 +1971,165 @@ static int run_clustering(gorder_hip_handle *h, const float *d_xyz, const float 
     return GORDER_OK;
 }
 
+// ---- the kernels of la.n_assign assignment frames, a function per method; `la` is what run_leaflets (below) filled in
+static int launch_global_leaflets(gorder_hip_handle *h, const LeafletArgs &la) {
+    // (behind a speculative batch nearly every frame is skipped: a few hundred workgroups take the frames in turn)
+    const dim3 g(la.skip ? std::min<uint32_t>(la.n_assign, 512u) : la.n_assign), b(1024);
+    TIMING_MARK(h, h->membrane_is_frame ? "k_leaflets_global_contig" : "k_leaflets_global");
+    if (h->membrane_is_frame) {
+        if (la.skip) hipLaunchKernelGGL(k_leaflets_global_contig<true>, g, dim3(256), 0, h->stream, la);
+        else hipLaunchKernelGGL(k_leaflets_global_contig<false>, g, dim3(256), 0, h->stream, la);
+    } else {
+        if (la.skip) hipLaunchKernelGGL(k_leaflets_global<true>, g, b, 0, h->stream, la);
+        else hipLaunchKernelGGL(k_leaflets_global<false>, g, b, 0, h->stream, la);
+    }
+    return GORDER_OK;
+}
+
+static int launch_individual_leaflets(gorder_hip_handle *h, const LeafletArgs &la) {
+    // gridDim.y <= 65535: launch in slabs
+    TIMING_MARK(h, "k_leaflets_individual");
+    for (uint32_t done = 0; done < la.n_assign;) {
+        const uint32_t ny = std::min<uint32_t>(la.n_assign - done, 65535u);
+        LeafletArgs lb = la;
+        lb.aframes = la.aframes + done;
+        lb.row0 = la.row0 + done;
+        // adist is only written by the last slab's last row
+        if (done + ny < la.n_assign) lb.adist = nullptr;
+        hipLaunchKernelGGL(k_leaflets_individual, dim3((la.n_mol_total + 255) / 256, ny), dim3(256), 0,
+                           h->stream, lb);
+        done += ny;
+    }
+    return GORDER_OK;
+}
+
+static int launch_spherical_leaflets(gorder_hip_handle *h, const LeafletArgs &la) {
+    // a workgroup per assignment frame; a group too large for the registers goes in slabs of frames (scratch rows)
+    TIMING_MARK(h, "k_leaflets_spherical");
+    SphArgs sa{};
+    sa.xyz = la.xyz; sa.box9 = la.box9; sa.n_atoms = la.n_atoms;
+    sa.aflags = la.aflags; sa.n_mol_total = la.n_mol_total; sa.heads = la.heads;
+    sa.group = la.membrane; sa.n_group = la.n_membrane;
+    sa.flip = la.flip; sa.pbc = la.pbc;
+    sa.spill = h->d_sph_spill; sa.n_spill = h->sph_spill; sa.err = la.err;
+    for (size_t done = 0; done < la.n_assign; done += h->sph_slab) {
+        const uint32_t ns = (uint32_t)std::min<size_t>(la.n_assign - done, h->sph_slab);
+        const bool last = done + ns == la.n_assign;
+        sa.aframes = la.aframes + done;
+        sa.row0 = la.row0 + (uint32_t)done;
+        sa.n_assign = ns;
+        sa.adist = last ? h->d_adist : nullptr;
+        sa.stats = last ? h->d_sph_stats : nullptr;
+        if (h->sph_threads == 256u) hipLaunchKernelGGL(k_leaflets_spherical<256>, dim3(ns), dim3(256), 0, h->stream, sa);
+        else hipLaunchKernelGGL(k_leaflets_spherical<1024>, dim3(ns), dim3(1024), 0, h->stream, sa);
+    }
+    return GORDER_OK;
+}
+
+// Local leaflets, what this submit runs.  decide: the bound first, a lane per head (k_local_decide), the rows kernel then only
+// for the frames with a head left open; sums: the table that kernel reads made from per-cell sums first (k_local_sums), the cell
+// list only for the frames left open; report: this submit writes {frames left open, frames} for a later one to read.
+struct LocalDecisions { bool decide, sums, report; };
+static LocalDecisions local_decisions(gorder_hip_handle *h, const LocalArgs &lo) {
+    LocalDecisions d{};
+    d.decide = lo.halo && lo.prune && lo.n_mol_total && !env_flag("GORDER_HIP_LOCAL_NO_DECIDE");
+    if (d.decide) {
+        if (h->lsummary_pending) {
+            if (hipEventQuery(h->lsummary_written) == hipSuccess) {
+                h->lsummary_pending = false;
+                if (2u * h->h_lsummary[0] > h->h_lsummary[1]) h->decide_pause = gorder_hip_handle::kDecidePause;
+            } else {
+                (void)hipGetLastError();        // (hipErrorNotReady is an answer, not a failure of this submit)
+            }
+        }
+        if (h->decide_pause) { h->decide_pause--; h->decide_paused_submits++; d.decide = false; }
+        else h->decide_submits++;
+    }
+    d.sums = d.decide && lo.n_membrane <= kLocalBuildMax && !env_flag("GORDER_HIP_LOCAL_THREE_KERNELS") &&
+             !env_flag("GORDER_HIP_LOCAL_NO_SUMS");
+    d.report = d.decide && !h->lsummary_pending;      // (one report in flight)
+    return d;
+}
+
+// ... and its kernels, local_slab assignment frames at a time
+static int launch_local_slabs(gorder_hip_handle *h, LocalArgs lo, uint32_t n_assign, uint32_t row0, bool report) {
+    const size_t ncell = (size_t)kLocalMaxCells1D * kLocalMaxCells1D;
+    for (size_t done = 0; done < n_assign; done += h->local_slab) {
+        const uint32_t ns = (uint32_t)std::min<size_t>(n_assign - done, h->local_slab);
+        lo.aframes = h->d_aframes + done;
+        lo.n_slab = ns;
+        lo.row0 = row0 + (uint32_t)done;
+        lo.write_dist_frame = (done + ns == n_assign) ? (int)ns - 1 : -1;
+        lo.summary_host = report && done + ns == n_assign ? h->h_lsummary : nullptr;
+        if (lo.n_membrane > kLocalBuildMax || env_flag("GORDER_HIP_LOCAL_THREE_KERNELS"))
+            HIP_TRY(h, hipMemsetAsync(h->d_lcell_fill, 0, ns * ncell * sizeof(uint32_t), h->stream));
+        if (lo.sums) {
+            HIP_TRY(h, hipMemsetAsync(h->d_lneed, 0, (ns + 1) * sizeof(uint32_t), h->stream));
+            TIMING_MARK(h, "k_local_sums");
+            hipLaunchKernelGGL(k_local_sums, dim3(ns), dim3(1024), kSumsLds, h->stream, lo);
+            TIMING_MARK(h, "k_local_decide");
+            hipLaunchKernelGGL(k_local_decide, dim3(ns), dim3(1024), kDecideLds, h->stream, lo);
+        }
+        ST_TRY(launch_cell_list(h, lo, ns, lo.n_membrane, h->d_lcell_count, ns * (ncell + 1) * sizeof(uint32_t)));
+        if (lo.halo) {
+            TIMING_MARK(h, "k_local_rowprefix");
+            hipLaunchKernelGGL(k_local_rowprefix, dim3(kLocalMaxCells1D / 4u, ns), dim3(256), 0, h->stream, lo);
+            lo.rows_groups = (lo.n_mol_total + 15u) / 16u;
+            if (lo.need && !lo.sums) {
+                TIMING_MARK(h, "k_local_decide");
+                hipLaunchKernelGGL(k_local_decide, dim3(ns), dim3(1024), kDecideLds, h->stream, lo);
+            }
+            TIMING_MARK(h, "k_local_flags_rows");
+            if (lo.need) hipLaunchKernelGGL(k_local_flags_rows_open, dim3(lo.rows_groups * 8u * kRowsSlots), dim3(256), 0, h->stream, lo);
+            else hipLaunchKernelGGL(k_local_flags_rows, dim3(lo.rows_groups * ((ns + 7u) / 8u * 8u)), dim3(256), 0, h->stream, lo);
+            // the heads the rows left over (normally none: the grid finds an empty list and leaves)
+            TIMING_MARK(h, "k_local_flags_todo");
+            hipLaunchKernelGGL(k_local_flags_todo, dim3(512), dim3(256), 0, h->stream, lo);
+        } else {
+            TIMING_MARK(h, "k_local_flags");
+            hipLaunchKernelGGL(k_local_flags, dim3((lo.n_mol_total + 3) / 4, ns), dim3(256), 0, h->stream, lo);
+        }
+    }
+    return GORDER_OK;
+}
+
+static int launch_local_leaflets(gorder_hip_handle *h, const LeafletArgs &la) {
+    const gorder_leaflets_t &lf = h->tables.leaflets;
+    LocalArgs lo{};
+    lo.xyz = la.xyz; lo.box9 = la.box9; lo.n_atoms = la.n_atoms;
+    lo.aflags = la.aflags; lo.adist = la.adist; lo.n_mol_total = la.n_mol_total;
+    lo.heads = la.heads; lo.mol_slot0 = h->d_mol_slot0; lo.n_membrane = la.n_membrane;
+    lo.membrane = h->membrane_is_frame ? nullptr : h->d_membrane;      // (the whole frame in order: no index list)
+    lo.dim = la.dim; lo.flip = la.flip; lo.pbc = la.pbc;
+    lo.radius = lf.radius;
+    lo.radius_thr = local_radius_threshold(lf.radius);
+    lo.cell_of = h->d_lcell_of; lo.trig = h->d_ltrig; lo.cell_count = h->d_lcell_count;
+    lo.cell_fill = h->d_lcell_fill; lo.err = la.err;
+    lo.grid = h->d_lgrid;
+    lo.halo = h->local_halo ? 1 : 0;
+    lo.prune = env_flag("GORDER_HIP_LOCAL_NO_PRUNE") ? 0 : (env_flag("GORDER_HIP_LOCAL_DECIDE_NOTHING") ? 2 : 1);
+    lo.rec_stride = (uint32_t)h->local_rec_stride;
+    lo.rowpre = h->d_lrowpre;
+    lo.edge = h->d_ledge;
+    lo.finfo = h->d_lfinfo;
+    lo.todo = h->d_ltodo;
+    const LocalDecisions d = local_decisions(h, lo);
+    lo.need = d.decide ? h->d_lneed : nullptr;
+    lo.sums = d.sums ? 1 : 0;
+    lo.summary = d.report ? h->d_lsummary : nullptr;
+    ST_TRY(launch_local_slabs(h, lo, la.n_assign, la.row0, d.report));
+    if (d.report) {
+        HIP_TRY(h, hipEventRecord(h->lsummary_written, h->stream));
+        h->lsummary_pending = true;
+    }
+    return GORDER_OK;
+}
+
+// The sides of the assignment frames `aframes` (positions in the batch) -> rows row0.. of d_aflags; `skip`: per frame, nothing to do
 static int run_leaflets(gorder_hip_handle *h, const float *d_xyz, const float *d_box,
                         const std::vector<uint32_t> &aframes, uint32_t row0, const uint8_t *skip = nullptr) {
     if (aframes.empty()) return GORDER_OK;
-    int st;
-    if ((st = upload_if_changed(h, h->d_aframes, h->up_aframes, h->up_aframes_valid, aframes)) != GORDER_OK) return st;
+    ST_TRY(upload_if_changed(h, h->d_aframes, h->up_aframes, h->up_aframes_valid, aframes));
     const gorder_leaflets_t &lf = h->tables.leaflets;
     LeafletArgs la{};
     la.xyz = d_xyz; la.box9 = d_box; la.n_atoms = h->plan.n_atoms;
@@ -1911,134 +2141,13 @@ static int run_leaflets(gorder_hip_handle *h, const float *d_xyz, const float *d
     la.err = h->d_err;
     la.skip = skip;
     la.n_assign = (uint32_t)aframes.size();
-    if (lf.method == GORDER_LEAFLETS_GLOBAL) {
-        // (behind a speculative batch nearly every frame is skipped: a few hundred workgroups take the frames in turn)
-        const dim3 g(skip ? std::min<uint32_t>((uint32_t)aframes.size(), 512u) : (uint32_t)aframes.size()), b(1024);
-        TIMING_MARK(h, h->membrane_is_frame ? "k_leaflets_global_contig" : "k_leaflets_global");
-        if (h->membrane_is_frame) {
-            if (skip) hipLaunchKernelGGL(k_leaflets_global_contig<true>, g, dim3(256), 0, h->stream, la);
-            else hipLaunchKernelGGL(k_leaflets_global_contig<false>, g, dim3(256), 0, h->stream, la);
-        } else {
-            if (skip) hipLaunchKernelGGL(k_leaflets_global<true>, g, b, 0, h->stream, la);
-            else hipLaunchKernelGGL(k_leaflets_global<false>, g, b, 0, h->stream, la);
-        }
-    } else if (lf.method == GORDER_LEAFLETS_INDIVIDUAL) {
-        // gridDim.y <= 65535: launch in slabs
-        TIMING_MARK(h, "k_leaflets_individual");
-        size_t done = 0;
-        while (done < aframes.size()) {
-            const uint32_t ny = (uint32_t)std::min<size_t>(aframes.size() - done, 65535);
-            LeafletArgs lb = la;
-            lb.aframes = h->d_aframes + done;
-            lb.row0 = row0 + (uint32_t)done;
-            // adist is only written by the last slab's last row
-            if (done + ny < aframes.size()) lb.adist = nullptr;
-            hipLaunchKernelGGL(k_leaflets_individual, dim3((la.n_mol_total + 255) / 256, ny), dim3(256), 0,
-                               h->stream, lb);
-            done += ny;
-        }
-    } else if (lf.method == GORDER_LEAFLETS_SPHERICAL) {
-        // a workgroup per assignment frame; a group too large for the registers goes in slabs of frames (scratch rows)
-        TIMING_MARK(h, "k_leaflets_spherical");
-        SphArgs sa{};
-        sa.xyz = d_xyz; sa.box9 = d_box; sa.n_atoms = h->plan.n_atoms;
-        sa.aflags = h->d_aflags; sa.n_mol_total = h->plan.n_mol_total; sa.heads = h->d_heads;
-        sa.group = h->d_membrane; sa.n_group = lf.n_membrane;
-        sa.flip = lf.flip ? 1 : 0; sa.pbc = h->tables.handle_pbc ? 1 : 0;
-        sa.spill = h->d_sph_spill; sa.n_spill = h->sph_spill; sa.err = h->d_err;
-        for (size_t done = 0; done < aframes.size(); done += h->sph_slab) {
-            const uint32_t ns = (uint32_t)std::min<size_t>(aframes.size() - done, h->sph_slab);
-            const bool last = done + ns == aframes.size();
-            sa.aframes = h->d_aframes + done;
-            sa.row0 = row0 + (uint32_t)done;
-            sa.n_assign = ns;
-            sa.adist = last ? h->d_adist : nullptr;
-            sa.stats = last ? h->d_sph_stats : nullptr;
-            if (h->sph_threads == 256u) hipLaunchKernelGGL(k_leaflets_spherical<256>, dim3(ns), dim3(256), 0, h->stream, sa);
-            else hipLaunchKernelGGL(k_leaflets_spherical<1024>, dim3(ns), dim3(1024), 0, h->stream, sa);
-        }
-    } else if (lf.method == GORDER_LEAFLETS_CLUSTERING) {
-        if ((st = run_clustering(h, d_xyz, d_box, aframes.size(), row0)) != GORDER_OK) return st;
-    } else if (lf.method == GORDER_LEAFLETS_LOCAL) {
-        const size_t ncell = (size_t)kLocalMaxCells1D * kLocalMaxCells1D;
-        LocalArgs lo{};
-        lo.xyz = d_xyz; lo.box9 = d_box; lo.n_atoms = h->plan.n_atoms;
-        lo.aflags = h->d_aflags; lo.adist = h->d_adist; lo.n_mol_total = h->plan.n_mol_total;
-        lo.heads = h->d_heads; lo.mol_slot0 = h->d_mol_slot0; lo.n_membrane = lf.n_membrane;
-        lo.membrane = h->membrane_is_frame ? nullptr : h->d_membrane;      // (the whole frame in order: no index list)
-        lo.dim = lf.normal_dim; lo.flip = lf.flip ? 1 : 0; lo.pbc = h->tables.handle_pbc ? 1 : 0;
-        lo.radius = lf.radius;
-        lo.radius_thr = local_radius_threshold(lf.radius);
-        lo.cell_of = h->d_lcell_of; lo.trig = h->d_ltrig; lo.cell_count = h->d_lcell_count;
-        lo.cell_fill = h->d_lcell_fill; lo.err = h->d_err;
-        lo.grid = h->d_lgrid;
-        lo.halo = h->local_halo ? 1 : 0;
-        lo.prune = env_flag("GORDER_HIP_LOCAL_NO_PRUNE") ? 0 : (env_flag("GORDER_HIP_LOCAL_DECIDE_NOTHING") ? 2 : 1);
-        lo.rec_stride = (uint32_t)h->local_rec_stride;
-        lo.rowpre = h->d_lrowpre;
-        lo.edge = h->d_ledge;
-        lo.finfo = h->d_lfinfo;
-        lo.todo = h->d_ltodo;
-        // the bound first, a lane per head (k_local_decide); the rows kernel then only for the frames with a head left open
-        bool decide = lo.halo && lo.prune && lo.n_mol_total && !env_flag("GORDER_HIP_LOCAL_NO_DECIDE");
-        if (decide) {
-            if (h->lsummary_pending) {
-                if (hipEventQuery(h->lsummary_written) == hipSuccess) {
-                    h->lsummary_pending = false;
-                    if (2u * h->h_lsummary[0] > h->h_lsummary[1]) h->decide_pause = gorder_hip_handle::kDecidePause;
-                } else {
-                    (void)hipGetLastError();        // (hipErrorNotReady is an answer, not a failure of this submit)
-                }
-            }
-            if (h->decide_pause) { h->decide_pause--; h->decide_paused_submits++; decide = false; }
-            else h->decide_submits++;
-        }
-        lo.need = decide ? h->d_lneed : nullptr;
-        // ... and the table that kernel reads made from per-cell sums first (k_local_sums): the cell list only for the frames left open
-        lo.sums = decide && lf.n_membrane <= kLocalBuildMax && !env_flag("GORDER_HIP_LOCAL_THREE_KERNELS") &&
-                  !env_flag("GORDER_HIP_LOCAL_NO_SUMS") ? 1 : 0;
-        const bool report = decide && !h->lsummary_pending;      // (one report in flight)
-        lo.summary = report ? h->d_lsummary : nullptr;
-        for (size_t done = 0; done < aframes.size(); done += h->local_slab) {
-            const uint32_t ns = (uint32_t)std::min<size_t>(aframes.size() - done, h->local_slab);
-            lo.aframes = h->d_aframes + done;
-            lo.n_slab = ns;
-            lo.row0 = row0 + (uint32_t)done;
-            lo.write_dist_frame = (done + ns == aframes.size()) ? (int)ns - 1 : -1;
-            lo.summary_host = report && done + ns == aframes.size() ? h->h_lsummary : nullptr;
-            if (lf.n_membrane > kLocalBuildMax || env_flag("GORDER_HIP_LOCAL_THREE_KERNELS"))
-                HIP_TRY(h, hipMemsetAsync(h->d_lcell_fill, 0, ns * ncell * sizeof(uint32_t), h->stream));
-            if (lo.sums) {
-                HIP_TRY(h, hipMemsetAsync(h->d_lneed, 0, (ns + 1) * sizeof(uint32_t), h->stream));
-                TIMING_MARK(h, "k_local_sums");
-                hipLaunchKernelGGL(k_local_sums, dim3(ns), dim3(1024), kSumsLds, h->stream, lo);
-                TIMING_MARK(h, "k_local_decide");
-                hipLaunchKernelGGL(k_local_decide, dim3(ns), dim3(1024), kDecideLds, h->stream, lo);
-            }
-            ST_TRY(launch_cell_list(h, lo, ns, lf.n_membrane, h->d_lcell_count, ns * (ncell + 1) * sizeof(uint32_t)));
-            if (lo.halo) {
-                TIMING_MARK(h, "k_local_rowprefix");
-                hipLaunchKernelGGL(k_local_rowprefix, dim3(kLocalMaxCells1D / 4u, ns), dim3(256), 0, h->stream, lo);
-                lo.rows_groups = (lo.n_mol_total + 15u) / 16u;
-                if (lo.need && !lo.sums) {
-                    TIMING_MARK(h, "k_local_decide");
-                    hipLaunchKernelGGL(k_local_decide, dim3(ns), dim3(1024), kDecideLds, h->stream, lo);
-                }
-                TIMING_MARK(h, "k_local_flags_rows");
-                if (lo.need) hipLaunchKernelGGL(k_local_flags_rows_open, dim3(lo.rows_groups * 8u * kRowsSlots), dim3(256), 0, h->stream, lo);
-                else hipLaunchKernelGGL(k_local_flags_rows, dim3(lo.rows_groups * ((ns + 7u) / 8u * 8u)), dim3(256), 0, h->stream, lo);
-                // the heads the rows left over (normally none: the grid finds an empty list and leaves)
-                TIMING_MARK(h, "k_local_flags_todo");
-                hipLaunchKernelGGL(k_local_flags_todo, dim3(512), dim3(256), 0, h->stream, lo);
-            } else {
-                TIMING_MARK(h, "k_local_flags");
-                hipLaunchKernelGGL(k_local_flags, dim3((lo.n_mol_total + 3) / 4, ns), dim3(256), 0, h->stream, lo);
-            }
-        }
-        if (report && !aframes.empty()) {
-            HIP_TRY(h, hipEventRecord(h->lsummary_written, h->stream));
-            h->lsummary_pending = true;
-        }
+    switch (lf.method) {
+    case GORDER_LEAFLETS_GLOBAL: ST_TRY(launch_global_leaflets(h, la)); break;
+    case GORDER_LEAFLETS_INDIVIDUAL: ST_TRY(launch_individual_leaflets(h, la)); break;
+    case GORDER_LEAFLETS_SPHERICAL: ST_TRY(launch_spherical_leaflets(h, la)); break;
+    case GORDER_LEAFLETS_CLUSTERING: ST_TRY(run_clustering(h, d_xyz, d_box, aframes.size(), row0)); break;
+    case GORDER_LEAFLETS_LOCAL: ST_TRY(launch_local_leaflets(h, la)); break;
+    default: break;
     }
     HIP_TRY(h, hipGetLastError());
     return GORDER_OK;
@@ -2080,65 +2189,84 @@ static int launch_bond_corr(gorder_hip_handle *h, const FrameArgs &a) {
     return GORDER_OK;
 }
 
-int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const float *d_box,
-                             const uint64_t *frame_index, uint32_t n_frames) {
-    if (!h || !d_xyz || !frame_index) return GORDER_ERR_INVALID_ARGUMENT;
-    const bool pbc = h->tables.handle_pbc != 0;
-    if (pbc && !d_box) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "box required when handle_pbc = 1");
-    if (((uintptr_t)d_xyz & 15u) != 0) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "d_xyz must be 16-byte aligned");
-    if (n_frames == 0) return GORDER_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    h->collect_locked = true;
-    const Plan &p = h->plan;
+// Room for `need` rows of n_mol_total flags in d_aflags.  A block that holds them stays; otherwise a block of `alloc_rows`
+// rows takes its place, with keep_row0 behind a stream-ordered copy of row 0 (the assignment earlier batches left).
+static int ensure_flag_rows(gorder_hip_handle *h, size_t need, size_t alloc_rows, bool keep_row0) {
+    if (need <= h->aflags_rows) return GORDER_OK;
+    const size_t n_mol = h->plan.n_mol_total;
+    DBuf<uint8_t> nb;      // (adopted once the copy is through)
+    ST_TRY(allocate(h, nb, alloc_rows * n_mol));
+    if (keep_row0 && h->d_aflags) {
+        // stream-ordered: the handle's stream is non-blocking, a null-stream copy would not be
+        HIP_TRY(h, hipMemcpyAsync(nb, h->d_aflags, n_mol, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    h->d_aflags.swap(nb);
+    h->aflags_rows = alloc_rows;
+    return GORDER_OK;
+}
+
+// ---- one batch: what the stages of gorder_hip_submit_device hand to one another.  It lives on that function's stack and
+// holds what used to be its locals; nothing in here outlives the call.
+namespace {
+struct Batch {
+    const float *d_xyz, *d_box;
+    const uint64_t *frame_index;
+    uint32_t n_frames;
+    bool pbc = false, leaflets = false;
+    bool ltable = false;                        // the flag rows come from the whole-trajectory manual table
+    gorder::ReplayLeafletBatch replay;          // ... as this plan has them
+    std::vector<uint32_t> normal_rows;          // manual normal table: the row of every frame
+    std::vector<uint32_t> arow, aframes;        // leaflet_rows.h
+    std::vector<uint32_t> spec_aframes;         // a speculative batch: the frames whose exact sides follow the order kernel
+    std::vector<uint64_t> collect_frames;       // collected leaflets: the assignment frames of this batch = rows 1.. of d_aflags
+    uint64_t last_assign_frame = 0;
+    size_t n_new_rows = 0;                      // flag rows this batch wrote behind row 0; the last becomes the carry
+    uint64_t mol_rows_before = 0;
+    gorder::OrderRouteIn ri;
+    gorder::OrderRoute route;                   // what the order pass runs (order_route.h), decided before the first kernel is queued
+    FrameArgs a{};
+
+    // The exit for a failure after the first kernel of the batch is queued: a key its kernels raised is not committed under
+    // the next batch's ordinal, and the batch appends no per-molecule rows.
+    int abort_batch(gorder_hip_handle *h, int status) const {
+        h->mol_store.truncate(mol_rows_before);
+        hipLaunchKernelGGL(k_batch_abort, dim3(1), dim3(1), 0, h->stream, h->d_err);
+        (void)hipGetLastError();
+        (void)timing_mark(h, nullptr);
+        return status;
+    }
+};
+// a stage's step behind the first kernel of the batch: a failure leaves through abort_batch (ST_TRY and HIP_TRY: it simply returns)
+#define BATCH_TRY(expr)                                                 \
+    do {                                                                \
+        const int bst_ = (expr);                                        \
+        if (bst_ != GORDER_OK) return b.abort_batch(h, bst_);           \
+    } while (0)
+}  // namespace
+
+// 1. what can refuse the batch before anything is queued: the overflow bound, the normals handed over for it, the tables' rows
+static int check_batch(gorder_hip_handle *h, Batch &b) {
     const gorder_leaflets_t &lf = h->tables.leaflets;
-    int st;
     // OrderValue is a checked i64 (order.rs:44-60 panics on overflow).  |tick| <= 1e6 and a slot receives at most one
     // sample per molecule of its type and frame, so no sum can overflow while frames * molecules stays below 2^63 / 1e6:
     // refuse the batch that would cross that bound instead of wrapping silently.
-    if ((h->n_frames + n_frames) > (uint64_t)(9223372036854775807ll / 1000000ll) / h->map_max_mol)
+    if ((h->n_frames + b.n_frames) > (uint64_t)(9223372036854775807ll / 1000000ll) / h->map_max_mol)
         return fail(h, GORDER_ERR_OVERFLOW, "order accumulators could overflow i64 (frames x molecules >= 2^63 / 1e6)");
-
-    // ---- leaflet assignment rows of this batch; row 0 = assignment carried over from earlier
-    // batches (AssignedLeaflets::local, leaflets.rs:1371-1380), rows 1.. = assignment frames here
-    const bool leaflets = lf.method != GORDER_LEAFLETS_NONE;
-    size_t n_new_rows = 0;
-    // what the order pass of this batch will run (order_route.h), decided here, before the first kernel is queued
-    gorder::OrderRouteIn ri;
-    ri.acos = (h->tables.flags & GORDER_FLAG_TRIG_ACOS_COS) != 0; ri.pbc = pbc; ri.leaflets = leaflets; ri.axis = h->axis;
-    ri.maps = h->extra.maps != 0; ri.map_staged = h->map_staged; ri.tw = h->extra.tw != 0; ri.geom = h->extra.geom_kind != 0;
-    ri.manual_frames = h->manual_frames != 0; ri.normal_table = h->d_ntable != nullptr;
-    ri.dyn_or_manual = h->dyn || ri.manual_frames || ri.normal_table;       // (manual_active is set further down)
-    ri.use_gather = h->use_gather; ri.item_run = h->d_item_run != nullptr; ri.frames_per_stage = h->frames_per_stage; ri.max_window = p.max_window;
-    ri.bond_tiles = !p.tiles.empty(); ri.ua_tiles = !p.ua_tiles.empty(); ri.direct_items = !p.direct.empty(); ri.ua_fast_flag = (h->tables.flags & GORDER_FLAG_UA_FAST_NORMALISE) != 0;
-    ri.global_leaflets = lf.method == GORDER_LEAFLETS_GLOBAL; ri.spec_enabled = h->spec_enabled && !h->corr.on(); ri.have_assignment = h->have_assignment;
-    ri.shells = h->n_shells != 0;
-    ri.dist = h->hist_edges != 0;
-    ri.classes = h->nb.on();
-    ri.mol_rows = h->mol.n_groups != 0 && !h->mol_failed;
-    ri.npf5 = env_flag("GORDER_HIP_NPF5"); ri.tw_gather = env_flag("GORDER_HIP_TW_GATHER"); ri.maps_gather = env_flag("GORDER_HIP_MAPS_GATHER");
-    std::vector<uint32_t> spec_aframes;
-    std::vector<uint64_t> collect_frames;       // collected leaflets: the assignment frames of this batch = rows 1.. of d_aflags
-    // argument errors come before the first kernel of the batch is queued (a batch that fails later leaves through
-    // abort_batch below, so that a key its kernels raised is not committed under the next batch's ordinal)
     if (h->manual_frames) {
-        if (h->manual_frames != n_frames) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_normals: frame count differs from the batch");
-        if (!p.direct.empty()) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "manual normals: a bond spans more than the LDS window");
+        if (h->manual_frames != b.n_frames) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_set_normals: frame count differs from the batch");
+        if (!h->plan.direct.empty()) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "manual normals: a bond spans more than the LDS window");
     }
     // whole-trajectory manual tables: every frame of the batch must have its row, or the batch is refused whole
-    const bool ltable = lf.method == GORDER_LEAFLETS_MANUAL && h->d_ltable;
-    gorder::ReplayLeafletBatch replay;
-    std::vector<uint32_t> normal_rows;
-    if (ltable) {
-        uint64_t bad = 0;
-        if (gorder::replay_plan_leaflets(lf.frequency, h->ltable_win, h->replay_have_carry, h->replay_carry_index, frame_index, n_frames,
-                                         replay, &bad) != gorder::kReplayOk) {
-            h->err_frame = bad;
-            return fail(h, GORDER_ERR_MANUAL_LEAFLET_FRAME, "manual leaflet table: no row for frame " + std::to_string(bad));
-        }
+    b.ltable = lf.method == GORDER_LEAFLETS_MANUAL && h->d_ltable;
+    uint64_t bad = 0;
+    if (b.ltable && gorder::replay_plan_leaflets(lf.frequency, h->ltable_win, h->replay_have_carry, h->replay_carry_index, b.frame_index,
+                                                 b.n_frames, b.replay, &bad) != gorder::kReplayOk) {
+        h->err_frame = bad;
+        return fail(h, GORDER_ERR_MANUAL_LEAFLET_FRAME, "manual leaflet table: no row for frame " + std::to_string(bad));
     }
     if (h->d_ntable) {
-        uint64_t bad = 0;
-        const gorder::ReplayStatus rs = gorder::replay_plan_normals(h->ntable_step, h->ntable_win, frame_index, n_frames, normal_rows, &bad);
+        const gorder::ReplayStatus rs = gorder::replay_plan_normals(h->ntable_step, h->ntable_win, b.frame_index, b.n_frames, b.normal_rows, &bad);
         if (rs != gorder::kReplayOk) {
             h->err_frame = bad;
             if (rs == gorder::kReplayBadStep)
@@ -2146,212 +2274,270 @@ int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const flo
             return fail(h, GORDER_ERR_MANUAL_NORMAL_FRAME, "manual normal table: no row for frame " + std::to_string(bad));
         }
     }
-    const uint64_t mol_rows_before = h->mol_store.n_rows();
-    auto abort_batch = [&](int status) {
-        h->mol_store.truncate(mol_rows_before);         // a batch that ends in an error appends no per-molecule rows
-        hipLaunchKernelGGL(k_batch_abort, dim3(1), dim3(1), 0, h->stream, h->d_err);
-        (void)hipGetLastError();
-        (void)timing_mark(h, nullptr);
-        return status;
-    };
-    std::vector<uint32_t> arow, aframes;
-    uint64_t last_assign_frame = h->assignment_frame;
-    if (leaflets) {
-        arow.resize(n_frames);
-        uint32_t cur = 0;
-        bool have = h->have_assignment;
-        if (ltable) {
-            arow = replay.arow;
-            last_assign_frame = replay.carry_index * lf.frequency;       // the assignment frame of the newest row
-        } else for (uint32_t f = 0; f < n_frames; f++) {
-            if (lf.method != GORDER_LEAFLETS_MANUAL && should_assign(lf.frequency, frame_index[f])) {
-                if (lf.method == GORDER_LEAFLETS_CLUSTERING) {
-                    // a later assignment frame is matched against the clusters the handle holds
-                    if (aframes.empty()) h->cl_is0.clear();
-                    if (aframes.empty() && frame_index[f] != 0 && !h->cl_have_carry)
-                        return fail(h, GORDER_ERR_LEAFLETS_NOT_PRIMED, "clustering: no clusters of an earlier assignment frame to match against");
-                    h->cl_is0.push_back(frame_index[f] == 0 ? 1 : 0);
-                }
-                aframes.push_back(f);
-                cur = (uint32_t)aframes.size();
-                have = true;
-                last_assign_frame = frame_index[f];
-            }
-            if (!have) return fail(h, GORDER_ERR_LEAFLETS_NOT_PRIMED, "no leaflet assignment for the first frame");
-            arow[f] = cur;
-        }
+    return GORDER_OK;
+}
+
+// 2. the row of the flag block every frame is routed by (leaflet_rows.h; a table: replay_rows.h has planned them in 1.)
+static int plan_batch_rows(gorder_hip_handle *h, Batch &b) {
+    const gorder_leaflets_t &lf = h->tables.leaflets;
+    b.last_assign_frame = h->assignment_frame;
+    if (!b.leaflets) return GORDER_OK;
+    if (b.ltable) {
+        b.arow = b.replay.arow;
+        b.last_assign_frame = b.replay.carry_index * lf.frequency;       // the assignment frame of the newest row
+        return GORDER_OK;
     }
-    // One read for global leaflets + order parameters (route.speculative): the order kernel then routes by row 0.
-    ri.every_frame_assigns = aframes.size() == n_frames;
-    gorder::OrderRoute route = gorder::choose_order_route(ri);
-    if (route.speculative) {
-        spec_poll(h, false);
-        const uint32_t slot = (uint32_t)(h->spec_batches % gorder_hip_handle::kSpecRing);
-        if (h->spec_ring_frames[slot]) (void)hipEventSynchronize(h->spec_counters_copied[slot]), spec_poll(h, false);
-        ri.spec_enabled = h->spec_enabled && !h->corr.on();
-        if (!ri.spec_enabled) route = gorder::choose_order_route(ri);      // the counters of an earlier batch turned it off
+    switch (gorder::plan_assignment_rows(lf.method, lf.frequency, h->have_assignment, h->cl_have_carry, b.frame_index, b.n_frames,
+                                         b.arow, b.aframes, h->cl_is0, b.last_assign_frame)) {
+    case gorder::kLeafletRowsNoClusters:
+        return fail(h, GORDER_ERR_LEAFLETS_NOT_PRIMED, "clustering: no clusters of an earlier assignment frame to match against");
+    case gorder::kLeafletRowsNotPrimed:
+        return fail(h, GORDER_ERR_LEAFLETS_NOT_PRIMED, "no leaflet assignment for the first frame");
+    default: return GORDER_OK;
     }
-    const bool spec = route.speculative;
-    if (leaflets) {
-        if (spec) std::fill(arow.begin(), arow.end(), 0u);
-        const size_t rows = (ltable ? replay.expand.size() : aframes.size()) + 1;   // (a speculative batch: row 0 and every frame's exact sides)
-        if (rows > h->aflags_rows) {       // grow and keep row 0: the new block is adopted once the copy is through
-            DBuf<uint8_t> nb;
-            const size_t nrows = rows + rows / 4;
-            ST_TRY(allocate(h, nb, nrows * (size_t)p.n_mol_total));
-            if (h->d_aflags) {
-                // stream-ordered: the handle's stream is non-blocking, a null-stream copy would not be
-                HIP_TRY(h, hipMemcpyAsync(nb, h->d_aflags, p.n_mol_total, hipMemcpyDeviceToDevice, h->stream));
-                HIP_TRY(h, hipStreamSynchronize(h->stream));
-            }
-            h->d_aflags.swap(nb);
-            h->aflags_rows = nrows;
-        }
-        ST_TRY(upload_if_changed(h, h->d_arow, h->up_arow, h->up_arow_valid, arow));
-        if (h->collect & GORDER_COLLECT_LEAFLETS)
-            for (uint32_t f : aframes) collect_frames.push_back(frame_index[f]);
-        if (spec) spec_aframes = aframes;
-        else if (ltable) { if ((st = replay_flag_rows(h, replay)) != GORDER_OK) return abort_batch(st); }
-        else if ((st = run_leaflets(h, d_xyz, d_box, aframes, 1)) != GORDER_OK) return abort_batch(st);
-        h->have_assignment = true;
-        h->assignment_frame = last_assign_frame;
-        n_new_rows = spec ? 0 : (ltable ? replay.expand.size() : aframes.size());
+}
+
+// 3. what the order pass will run.  One read for global leaflets + order parameters (route.speculative): the order kernel
+// then routes by row 0; the counters of earlier speculative batches are looked at first, and may turn it off.
+static void choose_batch_route(gorder_hip_handle *h, Batch &b) {
+    const Plan &p = h->plan;
+    gorder::OrderRouteIn &ri = b.ri;
+    ri.acos = (h->tables.flags & GORDER_FLAG_TRIG_ACOS_COS) != 0; ri.pbc = b.pbc; ri.leaflets = b.leaflets; ri.axis = h->axis;
+    ri.maps = h->extra.maps != 0; ri.map_staged = h->map_staged; ri.tw = h->extra.tw != 0; ri.geom = h->extra.geom_kind != 0;
+    ri.manual_frames = h->manual_frames != 0; ri.normal_table = h->d_ntable != nullptr;
+    ri.dyn_or_manual = h->dyn || ri.manual_frames || ri.normal_table;       // (manual_active is set in 6.)
+    ri.use_gather = h->use_gather; ri.item_run = h->d_item_run != nullptr; ri.frames_per_stage = h->frames_per_stage; ri.max_window = p.max_window;
+    ri.bond_tiles = !p.tiles.empty(); ri.ua_tiles = !p.ua_tiles.empty(); ri.direct_items = !p.direct.empty(); ri.ua_fast_flag = (h->tables.flags & GORDER_FLAG_UA_FAST_NORMALISE) != 0;
+    ri.global_leaflets = h->tables.leaflets.method == GORDER_LEAFLETS_GLOBAL; ri.spec_enabled = h->spec_enabled && !h->corr.on(); ri.have_assignment = h->have_assignment;
+    ri.shells = h->n_shells != 0;
+    ri.dist = h->hist_edges != 0;
+    ri.classes = h->nb.on();
+    ri.mol_rows = h->mol.n_groups != 0 && !h->mol_failed;
+    ri.npf5 = env_flag("GORDER_HIP_NPF5"); ri.tw_gather = env_flag("GORDER_HIP_TW_GATHER"); ri.maps_gather = env_flag("GORDER_HIP_MAPS_GATHER");
+    ri.every_frame_assigns = b.aframes.size() == b.n_frames;
+    b.route = gorder::choose_order_route(ri);
+    if (!b.route.speculative) return;
+    spec_poll(h, false);
+    const uint32_t slot = (uint32_t)(h->spec_batches % gorder_hip_handle::kSpecRing);
+    if (h->spec_ring_frames[slot]) (void)hipEventSynchronize(h->spec_counters_copied[slot]), spec_poll(h, false);
+    ri.spec_enabled = h->spec_enabled && !h->corr.on();
+    if (!ri.spec_enabled) b.route = gorder::choose_order_route(ri);      // the counters of an earlier batch turned it off
+}
+
+// 4. the flag rows: room for them, the frames' rows on the device, then the sides of the assignment frames (a speculative
+// batch: after the order kernel, in 8.).  The first kernel of the batch is queued here or in 6.
+static int fill_flag_rows(gorder_hip_handle *h, Batch &b) {
+    if (!b.leaflets) return GORDER_OK;
+    const bool spec = b.route.speculative;
+    if (spec) std::fill(b.arow.begin(), b.arow.end(), 0u);
+    const size_t rows = (b.ltable ? b.replay.expand.size() : b.aframes.size()) + 1;   // (a speculative batch: row 0 and every frame's exact sides)
+    ST_TRY(ensure_flag_rows(h, rows, rows + rows / 4, true));
+    ST_TRY(upload_if_changed(h, h->d_arow, h->up_arow, h->up_arow_valid, b.arow));
+    if (h->collect & GORDER_COLLECT_LEAFLETS)
+        for (uint32_t f : b.aframes) b.collect_frames.push_back(b.frame_index[f]);
+    if (spec) b.spec_aframes = b.aframes;
+    else if (b.ltable) BATCH_TRY(replay_flag_rows(h, b.replay));
+    else BATCH_TRY(run_leaflets(h, b.d_xyz, b.d_box, b.aframes, 1));
+    h->have_assignment = true;
+    h->assignment_frame = b.last_assign_frame;
+    b.n_new_rows = spec ? 0 : (b.ltable ? b.replay.expand.size() : b.aframes.size());
+    return GORDER_OK;
+}
+
+// 5. grow the per-frame rows (timewise.rs:183-186).  A failure in here returns without abort_batch, as it always has.
+static int grow_frame_rows(gorder_hip_handle *h, const Batch &b) {
+    if (!h->extra.tw || h->n_frames + b.n_frames <= h->tw_cap) return GORDER_OK;
+    const size_t row = 3 * (size_t)h->plan.n_acc;
+    const uint64_t ncap = (h->n_frames + b.n_frames) * 2;
+    DBuf<u64> ns, nc;      // (adopted once the copies are through)
+    ST_TRY(allocate(h, ns, ncap * row));
+    ST_TRY(allocate(h, nc, ncap * row));
+    // everything on the handle's own (non-blocking) stream: a null-stream memset / copy is NOT ordered
+    // with the kernels that follow and left stale rows behind (seen as a wrong error estimate)
+    HIP_TRY(h, hipMemsetAsync(ns, 0, ncap * row * sizeof(u64), h->stream));
+    HIP_TRY(h, hipMemsetAsync(nc, 0, ncap * row * sizeof(u64), h->stream));
+    if (h->d_tw_sums) {
+        HIP_TRY(h, hipMemcpyAsync(ns, h->d_tw_sums, h->n_frames * row * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(nc, h->d_tw_cnts, h->n_frames * row * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
-    // (check_box: k_batch_end, at the end of the batch)
-    if (h->extra.tw && h->n_frames + n_frames > h->tw_cap) {   // grow the per-frame rows (timewise.rs:183-186)
-        const size_t row = 3 * (size_t)p.n_acc;
-        const uint64_t ncap = (h->n_frames + n_frames) * 2;
-        DBuf<u64> ns, nc;      // (adopted once the copies are through)
-        ST_TRY(allocate(h, ns, ncap * row));
-        ST_TRY(allocate(h, nc, ncap * row));
-        // everything on the handle's own (non-blocking) stream: a null-stream memset / copy is NOT ordered
-        // with the kernels that follow and left stale rows behind (seen as a wrong error estimate)
-        HIP_TRY(h, hipMemsetAsync(ns, 0, ncap * row * sizeof(u64), h->stream));
-        HIP_TRY(h, hipMemsetAsync(nc, 0, ncap * row * sizeof(u64), h->stream));
-        if (h->d_tw_sums) {
-            HIP_TRY(h, hipMemcpyAsync(ns, h->d_tw_sums, h->n_frames * row * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
-            HIP_TRY(h, hipMemcpyAsync(nc, h->d_tw_cnts, h->n_frames * row * sizeof(u64), hipMemcpyDeviceToDevice, h->stream));
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-        }
-        h->d_tw_sums.swap(ns); h->d_tw_cnts.swap(nc); h->tw_cap = ncap;
-    }
-    FrameArgs a{};
-    a.xyz = d_xyz; a.box9 = d_box; a.n_atoms = p.n_atoms; a.n_frames = n_frames;
-    a.pbc = pbc ? 1 : 0;
+    h->d_tw_sums.swap(ns); h->d_tw_cnts.swap(nc); h->tw_cap = ncap;
+    return GORDER_OK;
+}
+
+// 6. the kernels' common arguments, and the normals supplied for this batch: handed over for exactly these frames
+// (gorder_hip_set_normals, checked in 1.) or the rows of the table, unpacked behind whatever still reads the buffer
+static int set_batch_normals(gorder_hip_handle *h, Batch &b) {
+    const Plan &p = h->plan;
+    FrameArgs &a = b.a;
+    a.xyz = b.d_xyz; a.box9 = b.d_box; a.n_atoms = p.n_atoms; a.n_frames = b.n_frames;
+    a.pbc = b.pbc ? 1 : 0;
     a.nx = h->tables.normal[0]; a.ny = h->tables.normal[1]; a.nz = h->tables.normal[2]; a.n2 = h->n2; a.n2sq = h->n2sq;
-    a.leaflets = leaflets ? 1 : 0; a.aflags = h->d_aflags; a.arow = h->d_arow; a.n_mol_total = p.n_mol_total;
+    a.leaflets = b.leaflets ? 1 : 0; a.aflags = h->d_aflags; a.arow = h->d_arow; a.n_mol_total = p.n_mol_total;
     a.acc = h->d_acc; a.rep = h->d_rep; a.n_rep = h->n_rep; a.n_acc = p.n_acc; a.err = h->d_err;
     h->manual_active = false;
-    if (h->manual_frames) {   // normals the host supplied for exactly this batch (arguments checked above)
-        const size_t n4 = (size_t)n_frames * p.n_mol_total;
-        if ((st = ensure(h, h->d_dyn_normals, n4)) != GORDER_OK) return abort_batch(st);
+    if (h->manual_frames) {
+        const size_t n4 = (size_t)b.n_frames * p.n_mol_total;
+        BATCH_TRY(ensure(h, h->d_dyn_normals, n4));
         if (hipStreamSynchronize(h->stream) != hipSuccess ||   // earlier batches may still read the buffer
             hipMemcpy(h->d_dyn_normals, h->manual_normals.data(), n4 * 4 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-            return abort_batch(fail(h, GORDER_ERR_DEVICE, "manual normals: copy to the device failed"));
+            return b.abort_batch(h, fail(h, GORDER_ERR_DEVICE, "manual normals: copy to the device failed"));
         h->manual_active = true;
         h->manual_frames = 0;
-    } else if (h->d_ntable) {   // ... or the rows of the table, unpacked behind whatever still reads the buffer
-        if ((st = replay_normal_rows(h, normal_rows)) != GORDER_OK) return abort_batch(st);
+    } else if (h->d_ntable) {
+        BATCH_TRY(replay_normal_rows(h, b.normal_rows));
         h->manual_active = true;
     }
-    const uint32_t n_tiles_all = (uint32_t)p.tiles.size();
-    if (spec) {
-        if ((st = ensure(h, h->d_mom, (size_t)n_frames * n_tiles_all)) != GORDER_OK) return abort_batch(st);
-        if ((st = ensure(h, h->d_head_z, (size_t)n_frames * p.n_mol_total)) != GORDER_OK) return abort_batch(st);
-        a.own = h->d_own; a.mom = h->d_mom; a.mom_dim = (int)lf.normal_dim;
+    return GORDER_OK;
+}
+
+// 7. the order kernels, with what a speculative batch and collected normals need them to write besides
+static int run_batch_orders(gorder_hip_handle *h, Batch &b) {
+    const Plan &p = h->plan;
+    FrameArgs &a = b.a;
+    if (b.route.speculative) {
+        BATCH_TRY(ensure(h, h->d_mom, (size_t)b.n_frames * p.tiles.size()));
+        BATCH_TRY(ensure(h, h->d_head_z, (size_t)b.n_frames * p.n_mol_total));
+        a.own = h->d_own; a.mom = h->d_mom; a.mom_dim = (int)h->tables.leaflets.normal_dim;
         a.own_head_begin = h->d_own_head_begin; a.own_heads = h->d_own_heads; a.head_z = h->d_head_z;
     }
     h->extra.touched = nullptr;
     if ((h->collect & GORDER_COLLECT_NORMALS) && h->extra.geom_kind && !p.tiles.empty() && p.ua_tiles.empty()) {
         // bond systems fetch a molecule's normal after the geometry test (bond.rs:424-431): k_bonds_extras marks who did
-        const size_t nt = (size_t)n_frames * p.n_mol_total;
-        if ((st = ensure(h, h->d_touched, nt)) != GORDER_OK) return abort_batch(st);
-        if (hipMemsetAsync(h->d_touched, 0, nt, h->stream) != hipSuccess) return abort_batch(fail(h, GORDER_ERR_DEVICE, "collect: hipMemsetAsync"));
+        const size_t nt = (size_t)b.n_frames * p.n_mol_total;
+        BATCH_TRY(ensure(h, h->d_touched, nt));
+        if (hipMemsetAsync(h->d_touched, 0, nt, h->stream) != hipSuccess) return b.abort_batch(h, fail(h, GORDER_ERR_DEVICE, "collect: hipMemsetAsync"));
         h->extra.touched = h->d_touched;
     }
-    h->mol_frame_index = frame_index;
-    st = launch_orders(h, a, route);
+    h->mol_frame_index = b.frame_index;
+    const int st = launch_orders(h, a, b.route);
     h->mol_frame_index = nullptr;
     h->manual_active = false;
-    if (st != GORDER_OK) return abort_batch(st);
+    BATCH_TRY(st);
     h->rep_dirty = true;
-    if (spec) {
-        // the exact centres from the order kernel's sums, the exact kernel for the frames they cannot vouch for, the sides
-        // of every (frame, molecule) against the prediction, the mispredicted ones moved
-        if ((st = ensure(h, h->d_spec_center, n_frames)) != GORDER_OK) return abort_batch(st);
-        if ((st = ensure(h, h->d_spec_ok, n_frames)) != GORDER_OK) return abort_batch(st);
-        uint32_t *cnt = h->d_spec_counters + 2u * (uint32_t)(h->spec_batches & 1u);
-        uint32_t *cnt_next = h->d_spec_counters + 2u * (uint32_t)((h->spec_batches + 1u) & 1u);
-        SpecArgs sa{};
-        sa.xyz = d_xyz; sa.box9 = d_box; sa.n_atoms = p.n_atoms; sa.n_frames = n_frames; sa.n_tiles = n_tiles_all;
-        sa.n_mol_total = p.n_mol_total; sa.n_membrane = lf.n_membrane; sa.dim = lf.normal_dim; sa.flip = lf.flip ? 1 : 0;
-        sa.pbc = pbc ? 1 : 0; sa.mom = h->d_mom; sa.head_z = h->d_head_z; sa.center = h->d_spec_center; sa.ok = h->d_spec_ok;
-        sa.aflags = h->d_aflags; sa.adist = h->d_adist; sa.counters = cnt; sa.counters_next = cnt_next;
-        const uint32_t ring_slot = (uint32_t)(h->spec_batches % gorder_hip_handle::kSpecRing);
-        sa.host_counters = h->h_spec_counters + 2u * ring_slot; sa.err = h->d_err;
-        (void)timing_mark(h, "k_spec_check + k_spec_fixup");
-        hipLaunchKernelGGL(k_spec_check, dim3(std::min<uint32_t>(n_frames, 2048u)), dim3(256), 0, h->stream, sa);
-        if ((st = run_leaflets(h, d_xyz, d_box, spec_aframes, 1, h->d_spec_ok)) != GORDER_OK) return abort_batch(st);
-        (void)timing_mark(h, "k_spec_check + k_spec_fixup");
-        const uint32_t fix_grid = (uint32_t)std::min<uint64_t>(((uint64_t)n_frames * p.n_mol_total + 63u) / 64u, 4096u);
-        with_bool(route.fixup_ac, [&](auto AC) { with_bool(route.fixup_tw, [&](auto TW) {
-            if constexpr (!AC() || !TW())      // (per-frame rows come out of the tiled kernel with the default cosine only)
-                hipLaunchKernelGGL((k_spec_fixup<AC(), TW()>), dim3(fix_grid), dim3(64), 0, h->stream, a, sa, h->d_spec_mol_begin,
-                                   h->d_spec_samples, TW() ? h->d_tw_sums : nullptr, TW() ? h->d_tw_cnts : nullptr,
-                                   TW() ? (uint64_t)h->n_frames : (uint64_t)0);
-        }); });
-        hipLaunchKernelGGL(k_spec_finish, dim3(1), dim3(256), 0, h->stream, sa);
-        HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipEventRecord(h->spec_counters_copied[ring_slot], h->stream));
-        h->spec_ring_frames[ring_slot] = n_frames;
-        h->spec_batches++;
-    }
-    // bond reorientation: an additional pass over the batch, behind everything that writes the flag rows
-    if (h->corr.on() && (st = launch_bond_corr(h, a)) != GORDER_OK) return abort_batch(st);
-    // the history a host asked for (rows 1.. of d_aflags hold every assignment frame's exact sides by now)
-    if ((st = collect_flag_rows(h, 1, collect_frames)) != GORDER_OK) return abort_batch(st);
-    if (ltable && (h->collect & GORDER_COLLECT_LEAFLETS)) {
+    return GORDER_OK;
+}
+
+// 8. behind a speculative order kernel: the exact centres from its sums (k_spec_check), the exact kernel for the frames they
+// cannot vouch for, the sides of every (frame, molecule) against the prediction, the mispredicted ones moved (k_spec_fixup)
+static int resolve_speculation(gorder_hip_handle *h, Batch &b) {
+    if (!b.route.speculative) return GORDER_OK;
+    const Plan &p = h->plan;
+    const gorder_leaflets_t &lf = h->tables.leaflets;
+    const uint32_t n_frames = b.n_frames;
+    BATCH_TRY(ensure(h, h->d_spec_center, n_frames));
+    BATCH_TRY(ensure(h, h->d_spec_ok, n_frames));
+    uint32_t *cnt = h->d_spec_counters + 2u * (uint32_t)(h->spec_batches & 1u);
+    uint32_t *cnt_next = h->d_spec_counters + 2u * (uint32_t)((h->spec_batches + 1u) & 1u);
+    SpecArgs sa{};
+    sa.xyz = b.d_xyz; sa.box9 = b.d_box; sa.n_atoms = p.n_atoms; sa.n_frames = n_frames; sa.n_tiles = (uint32_t)p.tiles.size();
+    sa.n_mol_total = p.n_mol_total; sa.n_membrane = lf.n_membrane; sa.dim = lf.normal_dim; sa.flip = lf.flip ? 1 : 0;
+    sa.pbc = b.pbc ? 1 : 0; sa.mom = h->d_mom; sa.head_z = h->d_head_z; sa.center = h->d_spec_center; sa.ok = h->d_spec_ok;
+    sa.aflags = h->d_aflags; sa.adist = h->d_adist; sa.counters = cnt; sa.counters_next = cnt_next;
+    const uint32_t ring_slot = (uint32_t)(h->spec_batches % gorder_hip_handle::kSpecRing);
+    sa.host_counters = h->h_spec_counters + 2u * ring_slot; sa.err = h->d_err;
+    (void)timing_mark(h, "k_spec_check + k_spec_fixup");
+    hipLaunchKernelGGL(k_spec_check, dim3(std::min<uint32_t>(n_frames, 2048u)), dim3(256), 0, h->stream, sa);
+    BATCH_TRY(run_leaflets(h, b.d_xyz, b.d_box, b.spec_aframes, 1, h->d_spec_ok));
+    (void)timing_mark(h, "k_spec_check + k_spec_fixup");
+    const uint32_t fix_grid = (uint32_t)std::min<uint64_t>(((uint64_t)n_frames * p.n_mol_total + 63u) / 64u, 4096u);
+    with_bool(b.route.fixup_ac, [&](auto AC) { with_bool(b.route.fixup_tw, [&](auto TW) {
+        if constexpr (!AC() || !TW())      // (per-frame rows come out of the tiled kernel with the default cosine only)
+            hipLaunchKernelGGL((k_spec_fixup<AC(), TW()>), dim3(fix_grid), dim3(64), 0, h->stream, b.a, sa, h->d_spec_mol_begin,
+                               h->d_spec_samples, TW() ? h->d_tw_sums : nullptr, TW() ? h->d_tw_cnts : nullptr,
+                               TW() ? (uint64_t)h->n_frames : (uint64_t)0);
+    }); });
+    hipLaunchKernelGGL(k_spec_finish, dim3(1), dim3(256), 0, h->stream, sa);
+    HIP_TRY(h, hipGetLastError());      // (this exit and the next return without abort_batch, as they always have)
+    HIP_TRY(h, hipEventRecord(h->spec_counters_copied[ring_slot], h->stream));
+    h->spec_ring_frames[ring_slot] = n_frames;
+    h->spec_batches++;
+    return GORDER_OK;
+}
+
+// 10. the history a host asked for (rows 1.. of d_aflags hold every assignment frame's exact sides by now)
+static int collect_batch(gorder_hip_handle *h, const Batch &b) {
+    BATCH_TRY(collect_flag_rows(h, 1, b.collect_frames));
+    if (b.ltable && (h->collect & GORDER_COLLECT_LEAFLETS)) {
         // a table: only the rows an assignment frame opened (a batch that starts inside an interval re-expands its row and
         // appends nothing, as priming does), in runs of consecutive rows
+        const gorder::ReplayLeafletBatch &replay = b.replay;
         for (size_t k = 0; k < replay.collect_rows.size();) {
             size_t e = k + 1;
             while (e < replay.collect_rows.size() && replay.collect_rows[e] == replay.collect_rows[e - 1] + 1u) e++;
             const std::vector<uint64_t> run(replay.collect_frames.begin() + k, replay.collect_frames.begin() + e);
-            if ((st = collect_flag_rows(h, replay.collect_rows[k], run)) != GORDER_OK) return abort_batch(st);
+            BATCH_TRY(collect_flag_rows(h, replay.collect_rows[k], run));
             k = e;
         }
     }
-    if ((h->collect & GORDER_COLLECT_NORMALS) && p.n_mol_total && !h->d_ntable &&
-        (st = collect_normal_rows(h, frame_index, n_frames, h->extra.touched)) != GORDER_OK) return abort_batch(st);
-    if (n_new_rows) {   // newest assignment becomes the carry row of the next batch
-        HIP_TRY(h, hipMemcpyAsync(h->d_aflags, h->d_aflags + n_new_rows * (size_t)p.n_mol_total, p.n_mol_total,
+    if ((h->collect & GORDER_COLLECT_NORMALS) && h->plan.n_mol_total && !h->d_ntable)
+        BATCH_TRY(collect_normal_rows(h, b.frame_index, b.n_frames, h->extra.touched));
+    return GORDER_OK;
+}
+
+// 11. what the next batch and a later error report find: the carry rows, the batch's frames under its ordinal, and — in one
+// launch behind the batch's kernels — check_box, total_frames and the batch's error key (it becomes the run's unless an
+// earlier batch had one).  No exit of this stage goes through abort_batch, as none ever has.
+static int close_batch(gorder_hip_handle *h, const Batch &b) {
+    const Plan &p = h->plan;
+    const uint64_t *frame_index = b.frame_index;
+    const uint32_t n_frames = b.n_frames;
+    if (b.n_new_rows) {   // newest assignment becomes the carry row of the next batch (a failure returns without abort_batch)
+        HIP_TRY(h, hipMemcpyAsync(h->d_aflags, h->d_aflags + b.n_new_rows * (size_t)p.n_mol_total, p.n_mol_total,
                                   hipMemcpyDeviceToDevice, h->stream));
     }
-    if (ltable) { h->replay_have_carry = replay.have_carry; h->replay_carry_index = replay.carry_index; }
-    // the batch's error key (if any) becomes the run's unless an earlier batch had one
-    {
-        gorder_hip_handle::BatchLog rec{h->n_submits, frame_index[0], n_frames > 1 ? frame_index[1] - frame_index[0] : 0, {}};
-        for (uint32_t f = 1; f < n_frames; f++)
-            if (frame_index[f] != rec.first + (uint64_t)f * rec.stride) { rec.list.assign(frame_index, frame_index + n_frames); break; }
-        if (h->batch_log.size() >= gorder_hip_handle::kBatchLog) h->batch_log.pop_front();
-        h->batch_log.push_back(std::move(rec));
-        if (ri.mol_rows) {
-            if (h->mol_batch_log.size() >= gorder_hip_handle::kBatchLog) h->mol_batch_log.pop_front();
-            h->mol_batch_log.push_back({h->n_submits, mol_rows_before});
-        }
-        // check_box, total_frames and the batch's error key in one launch behind the batch's kernels
-        TIMING_MARK(h, "k_batch_end");
-        hipLaunchKernelGGL(k_batch_end, dim3(pbc ? std::min<uint32_t>((n_frames + 255u) / 256u, 256u) : 1u), dim3(256), 0, h->stream,
-                           pbc ? d_box : nullptr, n_frames, h->d_err,
-                           h->d_acc + 4 * (size_t)p.n_acc, (unsigned long long)h->n_submits, h->decoder_key);
-        HIP_TRY(h, hipGetLastError());
-        TIMING_MARK(h, nullptr);          // the batch's chain of timed segments ends here
-        if (h->timing_on) h->timing_launches++;
-        h->n_submits++;
+    if (b.ltable) { h->replay_have_carry = b.replay.have_carry; h->replay_carry_index = b.replay.carry_index; }
+    gorder_hip_handle::BatchLog rec{h->n_submits, frame_index[0], n_frames > 1 ? frame_index[1] - frame_index[0] : 0, {}};
+    for (uint32_t f = 1; f < n_frames; f++)
+        if (frame_index[f] != rec.first + (uint64_t)f * rec.stride) { rec.list.assign(frame_index, frame_index + n_frames); break; }
+    if (h->batch_log.size() >= gorder_hip_handle::kBatchLog) h->batch_log.pop_front();
+    h->batch_log.push_back(std::move(rec));
+    if (b.ri.mol_rows) {
+        if (h->mol_batch_log.size() >= gorder_hip_handle::kBatchLog) h->mol_batch_log.pop_front();
+        h->mol_batch_log.push_back({h->n_submits, b.mol_rows_before});
     }
+    TIMING_MARK(h, "k_batch_end");        // (this exit and the two below return without abort_batch)
+    hipLaunchKernelGGL(k_batch_end, dim3(b.pbc ? std::min<uint32_t>((n_frames + 255u) / 256u, 256u) : 1u), dim3(256), 0, h->stream,
+                       b.pbc ? b.d_box : nullptr, n_frames, h->d_err,
+                       h->d_acc + 4 * (size_t)p.n_acc, (unsigned long long)h->n_submits, h->decoder_key);
+    HIP_TRY(h, hipGetLastError());
+    TIMING_MARK(h, nullptr);          // the batch's chain of timed segments ends here
+    if (h->timing_on) h->timing_launches++;
+    h->n_submits++;
     h->n_frames += n_frames;
     if (h->corr.on()) h->corr.seen += n_frames;
     return GORDER_OK;
+}
+
+// One batch of frames, stage by stage (the numbers are those of the stages' comments above).  Up to the first kernel — the
+// leaflet kernels of 4., or the table's normals in 6. — a failure simply returns; behind it, it leaves through
+// Batch::abort_batch.  The exits that do not, although kernels are queued (growing the per-frame rows in 5., behind the
+// speculation kernels in 8., the carry-row copy and k_batch_end in 11.), are kept as they were and say so where they stand:
+// what a failed submit leaves behind is not this function's to change.
+int gorder_hip_submit_device(gorder_hip_handle *h, const float *d_xyz, const float *d_box,
+                             const uint64_t *frame_index, uint32_t n_frames) {
+    if (!h || !d_xyz || !frame_index) return GORDER_ERR_INVALID_ARGUMENT;
+    Batch b{d_xyz, d_box, frame_index, n_frames};
+    b.pbc = h->tables.handle_pbc != 0;
+    b.leaflets = h->tables.leaflets.method != GORDER_LEAFLETS_NONE;
+    if (b.pbc && !d_box) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "box required when handle_pbc = 1");
+    if (((uintptr_t)d_xyz & 15u) != 0) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "d_xyz must be 16-byte aligned");
+    if (n_frames == 0) return GORDER_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    h->collect_locked = true;
+    b.mol_rows_before = h->mol_store.n_rows();
+    ST_TRY(check_batch(h, b));                  //  1. nothing is queued by 1. to 3.
+    ST_TRY(plan_batch_rows(h, b));              //  2.
+    choose_batch_route(h, b);                   //  3.
+    ST_TRY(fill_flag_rows(h, b));               //  4.
+    ST_TRY(grow_frame_rows(h, b));              //  5.
+    ST_TRY(set_batch_normals(h, b));            //  6.
+    ST_TRY(run_batch_orders(h, b));             //  7.
+    ST_TRY(resolve_speculation(h, b));          //  8.
+    // 9. bond reorientation: an additional pass over the batch, behind everything that writes the flag rows
+    if (h->corr.on()) BATCH_TRY(launch_bond_corr(h, b.a));
+    ST_TRY(collect_batch(h, b));                // 10.
+    return close_batch(h, b);                   // 11.
 }
 
 int gorder_hip_submit_host(gorder_hip_handle *h, const float *xyz, const float *box, const uint64_t *frame_index,
@@ -2401,12 +2587,7 @@ int gorder_hip_prime_leaflets(gorder_hip_handle *h, const float *d_xyz, const fl
         hipLaunchKernelGGL(k_check_box, dim3(1), dim3(256), 0, h->stream, d_box, 1u, h->d_err);
         HIP_TRY(h, hipGetLastError());
     }
-    if (h->aflags_rows < 2) {
-        DBuf<uint8_t> nb;
-        ST_TRY(allocate(h, nb, 2 * (size_t)h->plan.n_mol_total));
-        h->d_aflags.swap(nb);
-        h->aflags_rows = 2;
-    }
+    ST_TRY(ensure_flag_rows(h, 2, 2, false));
     std::vector<uint32_t> aframes(1, 0);
     if (lf.method == GORDER_LEAFLETS_CLUSTERING) {
         if (frame_index != 0 && !h->cl_have_carry)
@@ -2429,10 +2610,7 @@ int gorder_hip_set_manual_leaflets(gorder_hip_handle *h, const uint8_t *flags, u
     const uint32_t n = h->plan.n_mol_total;
     std::vector<uint8_t> tmp(n);
     for (uint32_t i = 0; i < n; i++) tmp[i] = (uint8_t)((flags[i] & 1) ^ (h->tables.leaflets.flip ? 1 : 0));
-    if (h->aflags_rows < 1) {
-        ST_TRY(allocate(h, h->d_aflags, 2 * (size_t)n));
-        h->aflags_rows = 2;
-    }
+    ST_TRY(ensure_flag_rows(h, 1, 2, false));      // (one row is read; the block is made with room for a batch's first)
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     HIP_TRY(h, hipMemcpy(h->d_aflags, tmp.data(), n, hipMemcpyHostToDevice));
     h->have_assignment = true;
