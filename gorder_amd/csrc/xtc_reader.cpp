@@ -257,7 +257,8 @@ int decode_ints(gorder_xtc_reader *r, const int minint[3], const int maxint[3], 
             br.ints(bitsize, sizeint, recip_big, cur);
         }
         i++;
-        for (int k = 0; k < 3; k++) cur[k] += minint[k];
+        // (in uint32_t: sizeint may exceed 2^31, and the number read is then no int until minint has come off)
+        for (int k = 0; k < 3; k++) cur[k] = (int)((uint32_t)cur[k] + (uint32_t)minint[k]);
         int prev[3] = {cur[0], cur[1], cur[2]};
         const uint32_t flag = br.bits(1);
         int is_smaller = 0;
@@ -273,7 +274,7 @@ int decode_ints(gorder_xtc_reader *r, const int minint[3], const int maxint[3], 
                 int d[3];
                 br.ints(smallidx, sizesmall, recip_small, d);
                 i++;
-                for (int c = 0; c < 3; c++) cur[c] = d[c] + prev[c] - smallnum;
+                for (int c = 0; c < 3; c++) cur[c] = (int)((uint32_t)d[c] + (uint32_t)prev[c] - (uint32_t)smallnum);
                 if (k == 0) {
                     // the first atom of a run is stored AFTER the second one (water: O after H)
                     for (int c = 0; c < 3; c++) { const int t = cur[c]; cur[c] = prev[c]; prev[c] = t; }

@@ -1,7 +1,7 @@
-"""k_xtc_decode (XTC frames decompressed on the device, one frame per lane) against the host decoder
-gorder_xtc_next, bit for bit — reference files, files of the repo's encoder at several precisions and box sizes
-(every field-width path of the format), groups with early stop, corrupt blocks — and the trajectory driver with
-device_decode against the host-decode route."""
+"""k_xtc_scan + k_xtc_chunks (XTC frames decompressed on the device: a wave per frame finds the chunks, a lane per
+chunk decodes) against the host decoder gorder_xtc_next, bit for bit — reference files, files of the repo's encoder
+at several precisions and box sizes (every field-width path of the format), groups with early stop, corrupt blocks —
+and the trajectory driver with device_decode against the host-decode route."""
 import os
 
 import numpy as np
@@ -10,6 +10,7 @@ import torch
 
 from gorder_amd import HipEngine, abi, xtc
 from golden_util import GOLDEN, METHODS, Fixture, cg_setup
+from xtc_streams import device_decode, same_bits
 
 pytestmark = pytest.mark.gpu
 CG3 = os.path.join(GOLDEN, "cg3.xtc")
@@ -24,29 +25,6 @@ def cg(built):
 def engine(built):
     mt = abi.MolType(n_molecules=1, bonds=np.array([[[0, 1]]], dtype=np.uint32))
     return HipEngine(abi.Tables(n_atoms=2, molecule_types=[mt]))
-
-
-def device_decode(engine, paths, group=None, chunk=64, **kw):
-    """-> xyz [F, n_out, 3] decoded by the device from packed windows"""
-    out = []
-    for w in xtc.pack_trajectory(paths, group=group, chunk=chunk, threads=2, **kw):
-        n = len(w["time"])
-        n_out = w["n_atoms_file"] if group is None else len(group)
-        blob = torch.from_numpy(w["blob"]).cuda()
-        frames = torch.from_numpy(w["frames"].view(np.uint8).reshape(-1).copy()).cuda()
-        slot = None if w["slot_of"] is None else torch.from_numpy(w["slot_of"]).cuda()
-        xyz = torch.full((n, n_out, 3), float("nan"), dtype=torch.float32, device="cuda")
-        torch.cuda.synchronize()
-        engine.xtc_decode(blob.data_ptr(), blob.numel(), frames.data_ptr(), n, w["n_atoms_file"],
-                          0 if slot is None else slot.data_ptr(), w["n_stop"], xyz.data_ptr(), n_out)
-        engine.synchronize()
-        out.append(xyz.cpu().numpy())
-    return np.concatenate(out) if out else np.zeros((0, 0, 3), np.float32)
-
-
-def same_bits(a, b):
-    assert a.shape == b.shape
-    np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def clustered(rng, n_atoms, n_frames, span, sigma=0.04, jitter=0.02):
@@ -192,8 +170,8 @@ def test_corrupt_block_is_reported(built, tmp_path):
 
 @pytest.mark.parametrize("batch_frames,threads", [(0, 4), (16, 2), (1, 1)])
 def test_driver_device_decode_matches_host_decode(cg, tmp_path, batch_frames, threads):
-    """the whole pipeline (pack -> copy -> k_xtc_decode -> analysis) against the host-decode pipeline: 101 CG frames
-    in two files with a duplicate boundary frame, a time window and a step"""
+    """the whole pipeline (pack -> copy -> k_xtc_scan + k_xtc_chunks -> analysis) against the host-decode pipeline:
+    101 CG frames in two files with a duplicate boundary frame, a time window and a step"""
     tables, labels, midx = cg_setup(cg, leaflets=METHODS["global"])
     a, b = str(tmp_path / "a.xtc"), str(tmp_path / "b.xtc")
     xtc.write_trajectory(a, cg.xyz[:60], cg.boxes[:60], times=cg.times[:60], precision=100.0)
