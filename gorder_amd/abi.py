@@ -47,6 +47,7 @@ COLLECT_LEAFLETS, COLLECT_NORMALS = 1, 2   # gorder_collect_t: what HipEngine.se
 FLAG_TRIG_ACOS_COS = 1
 FLAG_UA_FAST_NORMALISE = 2      # united atoms: tolerance-bounded hydrogen construction (include/gorder_hip.h)
 FLAG_CLUSTER_CUTOFF = 4         # LEAFLETS_CLUSTERING: 6 nm cut-off route for groups of up to 131072 atoms (include/gorder_hip.h)
+FLAG_UA_SAMPLES = 8             # set_order_histogram / set_molecule_rows accept united-atom molecule types (include/gorder_hip.h)
 UA_CH1_SAT, UA_CH2, UA_CH3, UA_CH1_UNSAT = 1, 2, 3, 4
 UA_N_H = {UA_CH1_SAT: 1, UA_CH2: 2, UA_CH3: 3, UA_CH1_UNSAT: 1}
 
@@ -328,7 +329,7 @@ _EXPORTS = [
     "gorder_hip_convergence", "gorder_hip_ordermaps",
     "gorder_hip_set_radial_shells", "gorder_hip_radial_shells", "gorder_hip_radial_thresholds",
     "gorder_hip_set_molecule_rows", "gorder_hip_molecule_rows_count", "gorder_hip_molecule_rows", "gorder_hip_molecule_rows_stats",
-    "gorder_hip_set_order_histogram", "gorder_hip_order_histogram",
+    "gorder_hip_set_order_histogram", "gorder_hip_order_histogram", "gorder_hip_order_histogram_route",
     "gorder_hip_set_bond_correlation", "gorder_hip_bond_correlation",
     "gorder_hip_set_neighbour_classes", "gorder_hip_neighbour_classes", "gorder_hip_neighbour_class_rows",
 ]
@@ -440,6 +441,7 @@ def load_library() -> C.CDLL:
     lib.gorder_hip_molecule_rows_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u32), C.POINTER(u32)]
     lib.gorder_hip_set_order_histogram.argtypes = [vp, vp, u32]
     lib.gorder_hip_order_histogram.argtypes = [vp, vp, C.POINTER(u32)]
+    lib.gorder_hip_order_histogram_route.argtypes = [vp, C.POINTER(u32), C.POINTER(u64)]
     lib.gorder_hip_set_bond_correlation.argtypes = [vp, vp, u32]
     lib.gorder_hip_bond_correlation.argtypes = [vp, vp, vp, C.POINTER(u32)]
     lib.gorder_hip_set_neighbour_classes.argtypes = [vp, vp, vp, u32, C.c_float, u32]
@@ -913,6 +915,13 @@ class HipEngine:
             raise ValueError("the edges are int32 ticks")
         e = np.ascontiguousarray(e, dtype=np.int32)
         self._check(self.lib.gorder_hip_set_order_histogram(self._h, e.ctypes.data_as(C.c_void_p) if e.size else None, e.size))
+
+    def order_histogram_route(self) -> dict:
+        """Which route the histogram takes (gorder_hip_order_histogram_route): "direct" — per-sample global atomics, because the
+        LDS table of the widest tile does not fit or GORDER_HIP_DIST_DIRECT is set — and the table's size in bytes."""
+        d, b = C.c_uint32(), C.c_uint64()
+        self._check(self.lib.gorder_hip_order_histogram_route(self._h, C.byref(d), C.byref(b)))
+        return {"direct": bool(d.value), "table_bytes": int(b.value)}
 
     def order_histogram(self) -> np.ndarray:
         """Sample counts uint64 [n_bins, 3, n_acc] (total, upper, lower) of the frames analysed so far: raw integers, the

@@ -44,6 +44,7 @@
 #include "ordermap_final.h"
 #include "order_route.h"
 #include "molecule_rows.h"
+#include "ua_molecule_rows.h"
 #include "order_hist.h"
 #include "bond_corr.h"
 #include "neighbour_classes.h"
@@ -64,6 +65,7 @@ using gorder::Tile;
 #include "kernels_radial.h"
 #include "kernels_neighbours.h"
 #include "kernels_hist.h"
+#include "kernels_ua_samples.h"
 #include "kernels_corr.h"
 #include "kernels_leaflets.h"
 #include "kernels_cluster.h"
@@ -394,6 +396,9 @@ struct gorder_hip_handle {
     DBuf<Item> d_mol_items;
     DBuf<gorder::MolRun> d_mol_runs;
     DBuf<uint32_t> d_mol_run_begin;
+    gorder::UaMolRows ua_mol;                   // GORDER_FLAG_UA_SAMPLES: the united-atom tiles' word lists (ua_molecule_rows.h; k_ua_mol)
+    DBuf<gorder::UaLaneWords> d_ua_mol_lanes;
+    DBuf<uint32_t> d_ua_mol_words, d_ua_mol_word_begin;
     DBuf<u64> d_mol_stage;
     size_t mol_stage_bytes = (size_t)1 << 30;   // GORDER_HIP_MOL_ROWS_STAGING, read once at gorder_hip_create
     gorder::CollectStore mol_store;             // rows of n_groups x n_mol_total u64
@@ -683,7 +688,8 @@ static_assert(gorder::kStageFrames == kRecFrames && gorder::kStageFrames == (uin
 int collect_copy_out(gorder_hip_handle *h, gorder::CollectStore &store, const void *d_block, const uint64_t *frames, size_t n_rows);
 int launch_molecule_rows(gorder_hip_handle *h, const FrameArgs &a, const gorder::OrderRoute &route) {
     const Plan &p = h->plan;
-    const uint32_t n_tiles = (uint32_t)p.tiles.size();
+    const bool bonds = route.family == gorder::BondFamily::TiledMol, ua = route.ua_kernel == gorder::UaKernel::Mol;
+    const uint32_t n_tiles = (uint32_t)p.tiles.size(), n_ua = (uint32_t)p.ua_tiles.size();
     const bool ac = (h->tables.flags & GORDER_FLAG_TRIG_ACOS_COS) != 0;
     const size_t wpf = (size_t)h->mol.n_groups * p.n_mol_total;
     const uint32_t sub = gorder::molecule_rows_subrange(a.n_frames, wpf, h->mol_stage_bytes);
@@ -691,26 +697,46 @@ int launch_molecule_rows(gorder_hip_handle *h, const FrameArgs &a, const gorder:
     if ((st = ensure(h, h->d_mol_stage, wpf * sub)) != GORDER_OK) return st;
     MolRowArgs mr{};
     mr.runs = h->d_mol_runs; mr.run_begin = h->d_mol_run_begin; mr.stage = h->d_mol_stage; mr.words_per_frame = (uint32_t)wpf;
+    UaMolArgs um{};
+    um.word_begin = h->d_ua_mol_word_begin; um.words = h->d_ua_mol_words; um.lane_words = h->d_ua_mol_lanes; um.stage = h->d_mol_stage;
+    um.words_per_frame = (uint32_t)wpf; um.list_bytes = (uint32_t)gorder::ua_mol_list_bytes(h->ua_mol.max_local);
+    um.n_buf = gorder::ua_mol_buffers(h->ua_mol.max_local);
+    const ExtraArgs e = h->extra;       // (the hydrogen construction's constants and the axis; no geometry, maps or rows: the setter refuses them)
     for (uint32_t lo = 0; lo < a.n_frames; lo += sub) {
         const uint32_t hi = std::min(a.n_frames, lo + sub), nf = hi - lo;
-        const gorder::FrameChunks c = gorder::extras_chunks(nf, n_tiles, h->wg_target, h->wg_capacity, false, true);
-        const uint64_t grid = (uint64_t)n_tiles * c.n_chunks;
-        if (grid > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "batch too large");
         FrameArgs b = a;
-        b.frame0 = lo; b.n_frames = hi; b.frames_per_chunk = c.frames_per_chunk;
-        TIMING_MARK(h, route.label);
+        b.frame0 = lo; b.n_frames = hi;
+        TIMING_MARK(h, bonds ? route.label : "k_ua_mol");
         HIP_TRY(h, hipMemsetAsync(h->d_mol_stage, 0, wpf * nf * sizeof(unsigned long long), h->stream));
-        const dim3 g((uint32_t)grid), blk(kBlock);
-        with_npf(route.npf, [&](auto NPF) { with_bool(b.pbc, [&](auto PBC) { with_bool(b.leaflets, [&](auto LF) {
-            if (ac)     // (the literal cosine: the general normal's code for every axis)
-                hipLaunchKernelGGL((k_bonds_tiled_mol<NPF(), true, PBC(), LF(), -1>), g, blk, h->lds_bytes, h->stream, b, mr, b.xyz, b.box9,
-                                   b.aflags, b.arow, h->d_tiles, h->d_mol_items, h->d_tile_slots, n_tiles, h->lw);
-            else with_int<2, -1>(h->axis, [&](auto AX) {      // (a normal along z, or the general code: exact for x and y as well)
-                hipLaunchKernelGGL((k_bonds_tiled_mol<NPF(), false, PBC(), LF(), AX()>), g, blk, h->lds_bytes, h->stream, b, mr, b.xyz, b.box9,
-                                   b.aflags, b.arow, h->d_tiles, h->d_mol_items, h->d_tile_slots, n_tiles, h->lw);
+        if (bonds) {
+            const gorder::FrameChunks c = gorder::extras_chunks(nf, n_tiles, h->wg_target, h->wg_capacity, false, true);
+            const uint64_t grid = (uint64_t)n_tiles * c.n_chunks;
+            if (grid > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "batch too large");
+            b.frames_per_chunk = c.frames_per_chunk;
+            const dim3 g((uint32_t)grid), blk(kBlock);
+            with_npf(route.npf, [&](auto NPF) { with_bool(b.pbc, [&](auto PBC) { with_bool(b.leaflets, [&](auto LF) {
+                if (ac)     // (the literal cosine: the general normal's code for every axis)
+                    hipLaunchKernelGGL((k_bonds_tiled_mol<NPF(), true, PBC(), LF(), -1>), g, blk, h->lds_bytes, h->stream, b, mr, b.xyz, b.box9,
+                                       b.aflags, b.arow, h->d_tiles, h->d_mol_items, h->d_tile_slots, n_tiles, h->lw);
+                else with_int<2, -1>(h->axis, [&](auto AX) {      // (a normal along z, or the general code: exact for x and y as well)
+                    hipLaunchKernelGGL((k_bonds_tiled_mol<NPF(), false, PBC(), LF(), AX()>), g, blk, h->lds_bytes, h->stream, b, mr, b.xyz, b.box9,
+                                       b.aflags, b.arow, h->d_tiles, h->d_mol_items, h->d_tile_slots, n_tiles, h->lw);
+                });
+            }); }); });
+            HIP_TRY(h, hipGetLastError());
+        }
+        if (ua) {       // the united-atom tiles add into the same block (GORDER_FLAG_UA_SAMPLES)
+            const gorder::FrameChunks c = gorder::extras_chunks(nf, n_ua, h->wg_target, h->wg_capacity, false, true);
+            const uint64_t grid = ((uint64_t)n_ua * c.n_chunks + 7u) / 8u * 8u;      // see the XCD mapping in k_ua_extras
+            if (grid > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "batch too large");
+            b.frames_per_chunk = c.frames_per_chunk;
+            if (bonds) TIMING_MARK(h, "k_ua_mol");
+            with_bool(ac, [&](auto AC) {
+                hipLaunchKernelGGL((k_ua_mol<AC()>), dim3((uint32_t)grid), dim3(kBlock), gorder::ua_mol_lds_bytes(h->ua_mol.max_local), h->stream, b, e,
+                                   um, b.xyz, b.box9, b.aflags, b.arow, h->d_ua_tiles, h->d_ua_items, h->d_ua_tile_slots, n_ua);
             });
-        }); }); });
-        HIP_TRY(h, hipGetLastError());
+            HIP_TRY(h, hipGetLastError());
+        }
         if ((st = collect_copy_out(h, h->mol_store, h->d_mol_stage, h->mol_frame_index + lo, nf)) != GORDER_OK) return st;
     }
     return GORDER_OK;
@@ -902,9 +928,30 @@ int launch_bond_pass(gorder_hip_handle *h, const SubRange &s, ExtraArgs &e) {
     return GORDER_OK;
 }
 
+// the order histogram over the united-atom tiles (GORDER_FLAG_UA_SAMPLES): k_bonds_dist's replicas, k_ua_extras' grid
+int launch_ua_dist(gorder_hip_handle *h, const SubRange &s, const ExtraArgs &e) {
+    const uint32_t nt = (uint32_t)h->plan.ua_tiles.size();
+    const gorder::FrameChunks c = gorder::dist_chunks(s.nf(), nt, h->wg_target, h->wg_capacity, h->hist_direct ? 0u : (uint32_t)h->hist_table_words,
+                                                      h->hist_samples_per_word, kDistChunkMax);
+    FrameArgs b = s.frames(c);
+    DistArgs da{};
+    da.n_edges = h->hist_edges; da.edges = h->d_hist_edges; da.rep = h->hist.rep; da.n_rep = h->hist.n_rep;
+    // the edges, then the table of the widest tile or the epilogue's sums, whichever is larger
+    const size_t lds = kDistEdgeBytes + std::max<size_t>(kUaSumBytes, h->hist_direct ? 0u : h->hist_table_words * sizeof(uint32_t));
+    const dim3 g((nt * c.n_chunks + 7u) / 8u * 8u), blk(kBlock);   // see the XCD mapping in k_ua_extras
+    TIMING_MARK(h, "k_ua_dist");
+    with_bool(literal_cosine(h), [&](auto AC) { with_bool(h->hist_direct, [&](auto DIRECT) {
+        hipLaunchKernelGGL((k_ua_dist<AC(), DIRECT()>), g, blk, lds, h->stream, b, e, da, b.xyz, b.box9, b.aflags, b.arow, h->d_ua_tiles,
+                           h->d_ua_items, h->d_ua_tile_slots, nt);
+    }); });
+    HIP_TRY(h, hipGetLastError());
+    return GORDER_OK;
+}
+
 // ... and its united-atom tiles
 int launch_ua_pass(gorder_hip_handle *h, const SubRange &s, ExtraArgs &e) {
     const gorder::OrderRoute &route = s.route;
+    if (route.ua_kernel == gorder::UaKernel::Dist) return launch_ua_dist(h, s, e);
     const uint32_t nt = (uint32_t)h->plan.ua_tiles.size();
     const gorder::FrameChunks c = gorder::extras_chunks(s.nf(), nt, h->wg_target, h->wg_capacity, route.map_accumulate, false);
     FrameArgs b = s.frames(c);
@@ -959,7 +1006,7 @@ int launch_scatter_passes(gorder_hip_handle *h, const FrameArgs &a, const gorder
         }
         e.rec_frame0 = lo; e.rec_stride = (s.nf() + 15u) / 16u * 16u;
         if (route.extras && !p.tiles.empty()) ST_TRY(launch_bond_pass(h, s, e));
-        if (!p.ua_tiles.empty()) ST_TRY(launch_ua_pass(h, s, e));
+        if (!p.ua_tiles.empty() && route.ua_kernel != gorder::UaKernel::Mol) ST_TRY(launch_ua_pass(h, s, e));
     }
     return GORDER_OK;
 }
@@ -980,8 +1027,9 @@ int launch_orders(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &
     if (h->dyn && !h->manual_active) ST_TRY(run_dynamic_normals(h, a));
     if (h->extra.geom_kind) ST_TRY(launch_geometry_shapes(h, a));
     if (route.family == BondFamily::Tiled || route.family == BondFamily::Gather) ST_TRY(launch_tiled(h, a, route));
-    if (route.family == BondFamily::TiledMol) ST_TRY(launch_molecule_rows(h, a, route));
-    if (route.extras || route.ua_mode >= 0) ST_TRY(launch_scatter_passes(h, a, route));
+    const bool ua_mol = route.ua_kernel == gorder::UaKernel::Mol;      // (k_ua_mol is the united-atom pass of such a handle)
+    if (route.family == BondFamily::TiledMol || ua_mol) ST_TRY(launch_molecule_rows(h, a, route));
+    if (route.extras || (route.ua_mode >= 0 && !ua_mol)) ST_TRY(launch_scatter_passes(h, a, route));
     if (route.direct) ST_TRY(launch_bonds_direct(h, a));
     return GORDER_OK;       // (the frames are counted by k_batch_end, which also closes the batch's timing chain)
 }
@@ -2313,6 +2361,7 @@ static void choose_batch_route(gorder_hip_handle *h, Batch &b) {
     ri.dist = h->hist_edges != 0;
     ri.classes = h->nb.on();
     ri.mol_rows = h->mol.n_groups != 0 && !h->mol_failed;
+    ri.ua_samples_flag = (h->tables.flags & GORDER_FLAG_UA_SAMPLES) != 0;
     ri.npf5 = env_flag("GORDER_HIP_NPF5"); ri.tw_gather = env_flag("GORDER_HIP_TW_GATHER"); ri.maps_gather = env_flag("GORDER_HIP_MAPS_GATHER");
     ri.every_frame_assigns = b.aframes.size() == b.n_frames;
     b.route = gorder::choose_order_route(ri);
@@ -3107,8 +3156,11 @@ int gorder_hip_set_order_histogram(gorder_hip_handle *h, const int32_t *edges, u
     auto refuse = [&](const char *why) { return fail(h, GORDER_ERR_INVALID_ARGUMENT, std::string(who) + why); };
     if (h->collect_locked) return refuse("only before the first submit or prime, or right after gorder_hip_reset");
     const Plan &p = h->plan;
+    const bool ua_samples = (h->tables.flags & GORDER_FLAG_UA_SAMPLES) != 0;
     if (n_edges) {
-        if (!p.ua_tiles.empty()) return refuse("united-atom molecule types");
+        if (!p.ua_tiles.empty() && !ua_samples) return refuse("united-atom molecule types");
+        if (!p.ua_tiles.empty() && (h->tables.flags & GORDER_FLAG_UA_FAST_NORMALISE))
+            return refuse("united-atom molecule types with GORDER_FLAG_UA_FAST_NORMALISE (the fast hydrogen construction is not covered)");
         if (h->extra.maps) return refuse("ordermaps are on");
         if (h->extra.tw) return refuse("timewise is on");
         if (h->dyn) return refuse("dynamic membrane normals");
@@ -3118,7 +3170,7 @@ int gorder_hip_set_order_histogram(gorder_hip_handle *h, const int32_t *edges, u
         if (h->mol.n_groups) return refuse("the handle has molecule rows");
         if (h->nb.on()) return refuse("the handle has neighbour classes");
         if (!p.direct.empty()) return refuse("a bond spans more than the LDS window");
-        if (!p.n_acc || p.tiles.empty()) return refuse("no bond samples");
+        if (!p.n_acc || (p.tiles.empty() && p.ua_tiles.empty())) return refuse("no bond samples");
         if (const char *why = gorder::hist_edges_check(edges, n_edges)) return refuse(why);
     }
     HIP_TRY(h, hipSetDevice(h->device));
@@ -3133,10 +3185,19 @@ int gorder_hip_set_order_histogram(gorder_hip_handle *h, const int32_t *edges, u
     ST_TRY(alloc_zeroed(h, h->hist, (size_t)n_bins * 2u * p.n_acc));
     uint32_t max_slots = 1;
     for (const Tile &tile : p.tiles) max_slots = std::max(max_slots, tile.n_slots);
+    for (const Tile &tile : p.ua_tiles) max_slots = std::max(max_slots, tile.n_slots);     // (only with GORDER_FLAG_UA_SAMPLES: refused above otherwise)
     const uint32_t planes = h->tables.leaflets.method != GORDER_LEAFLETS_NONE ? 2u : 1u;
     h->hist_table_words = (size_t)planes * n_bins * max_slots;
     h->hist_direct = h->hist_force_direct || kDistEdgeBytes + h->hist_table_words * sizeof(uint32_t) > 64u * 1024u;
     h->hist_edges = n_edges;
+    return GORDER_OK;
+}
+
+int gorder_hip_order_histogram_route(gorder_hip_handle *h, uint32_t *direct, uint64_t *table_bytes) {
+    if (!h) return GORDER_ERR_INVALID_ARGUMENT;
+    if (!h->hist_edges) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "gorder_hip_order_histogram_route: the histogram is off");
+    if (direct) *direct = h->hist_direct ? 1u : 0u;
+    if (table_bytes) *table_bytes = (uint64_t)h->hist_table_words * sizeof(uint32_t);
     return GORDER_OK;
 }
 
@@ -3316,8 +3377,11 @@ int gorder_hip_set_molecule_rows(gorder_hip_handle *h, const uint32_t *group_beg
     if (h->collect_locked) return refuse("only before the first submit or prime, or right after gorder_hip_reset");
     const Plan &p = h->plan;
     gorder::MolRows mol;
+    gorder::UaMolRows ua_mol;
     if (n_groups) {
-        if (!p.ua_tiles.empty()) return refuse("united-atom molecule types");
+        if (!p.ua_tiles.empty() && !(h->tables.flags & GORDER_FLAG_UA_SAMPLES)) return refuse("united-atom molecule types");
+        if (!p.ua_tiles.empty() && (h->tables.flags & GORDER_FLAG_UA_FAST_NORMALISE))
+            return refuse("united-atom molecule types with GORDER_FLAG_UA_FAST_NORMALISE (the fast hydrogen construction is not covered)");
         if (h->extra.maps) return refuse("ordermaps are on");
         if (h->extra.tw) return refuse("timewise is on");
         if (h->n_shells) return refuse("the handle has radial shells");
@@ -3328,15 +3392,26 @@ int gorder_hip_set_molecule_rows(gorder_hip_handle *h, const uint32_t *group_beg
         if (h->d_ntable) return refuse("a manual normal table is set");
         if (h->manual_frames) return refuse("normals were supplied by gorder_hip_set_normals");
         if (!p.direct.empty()) return refuse("a bond spans more than the LDS window");
-        if (!p.n_acc || p.tiles.empty() || !p.n_mol_total) return refuse("no bond samples");
+        if (!p.n_acc || (p.tiles.empty() && p.ua_tiles.empty()) || !p.n_mol_total) return refuse("no bond samples");
         std::vector<uint32_t> group_of_slot;
         if (const char *why = gorder::molecule_groups_check(group_begin, slots, n_groups, p.n_acc, group_of_slot)) return refuse(why);
         if ((uint64_t)n_groups * p.n_mol_total > 0xffffffffull) return refuse("groups x molecules exceed 2^32 words a frame");
         gorder::build_molecule_rows(p.tiles, p.items, p.tile_slots, group_of_slot, n_groups, p.n_mol_total, mol);
+        if (!p.ua_tiles.empty()) {      // (GORDER_FLAG_UA_SAMPLES) the united-atom tiles' word lists, and their share of the statistics
+            std::map<uint32_t, uint32_t> tiles_of_word;
+            for (const gorder::MolRun &r : mol.runs) tiles_of_word[r.word]++;       // (a run is one (tile, word) pair)
+            gorder::build_ua_molecule_rows(p.ua_tiles, p.ua_items, p.ua_tile_slots, group_of_slot, p.n_mol_total, tiles_of_word, ua_mol);
+            mol.n_runs += ua_mol.words.size();
+            mol.max_runs_per_tile = std::max(mol.max_runs_per_tile, ua_mol.max_local);
+            mol.max_tiles_per_word = 0;
+            for (const auto &kv : tiles_of_word) mol.max_tiles_per_word = std::max(mol.max_tiles_per_word, kv.second);
+        }
     }
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));       // (copies of a run before the reset may still be writing the chunks)
     h->d_mol_items.reset(); h->d_mol_runs.reset(); h->d_mol_run_begin.reset();
+    h->d_ua_mol_lanes.reset(); h->d_ua_mol_words.reset(); h->d_ua_mol_word_begin.reset();
+    h->ua_mol = gorder::UaMolRows();
     h->mol = gorder::MolRows();
     h->mol_store.release();
     h->mol_failed = false;
@@ -3346,6 +3421,12 @@ int gorder_hip_set_molecule_rows(gorder_hip_handle *h, const uint32_t *group_beg
     if ((st = upload(h, h->d_mol_items, mol.items)) != GORDER_OK) return st;
     if ((st = upload(h, h->d_mol_runs, mol.runs)) != GORDER_OK) return st;
     if ((st = upload(h, h->d_mol_run_begin, mol.run_begin)) != GORDER_OK) return st;
+    if (ua_mol.on()) {
+        if ((st = upload(h, h->d_ua_mol_lanes, ua_mol.lane_words)) != GORDER_OK) return st;
+        if ((st = upload(h, h->d_ua_mol_words, ua_mol.words)) != GORDER_OK) return st;
+        if ((st = upload(h, h->d_ua_mol_word_begin, ua_mol.word_begin)) != GORDER_OK) return st;
+        h->ua_mol = std::move(ua_mol);
+    }
     h->mol_store.configure((size_t)n_groups * p.n_mol_total * sizeof(uint64_t), gorder::CollectAlloc{PinnedMem::alloc, PinnedMem::release});
     h->mol = std::move(mol);
     return GORDER_OK;

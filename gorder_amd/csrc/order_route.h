@@ -10,6 +10,8 @@
 //   per-molecule rows (gorder_hip_set_molecule_rows: bond tiles, no other extra, either cosine)  -> TiledMol
 //   order distributions (gorder_hip_set_order_histogram: bond tiles, at most a geometry selection, either cosine) -> Dist
 //   neighbour classes (gorder_hip_set_neighbour_classes: bond tiles, no other extra, either cosine)              -> Classes
+//   united-atom tiles with GORDER_FLAG_UA_SAMPLES and per-molecule rows / an order histogram -> k_ua_mol / k_ua_dist
+//     (UaKernel; the bond tiles of the same handle take TiledMol / Dist as above)
 // A batch speculates (one read for global leaflets and order parameters) only where Tiled or the unstaged TiledTw runs:
 // those are the kernels with a MOM variant, and k_spec_check / k_spec_fixup read what that variant wrote.  TiledMol has
 // none, and no gather variant either: GORDER_HIP_KERNEL=gather does not apply to a handle with rows (the rows need the lanes'
@@ -40,13 +42,18 @@ struct OrderRouteIn {
     bool npf5 = false, tw_gather = false, maps_gather = false;
     // radial shells are set on the handle (they come with a geometry selection and exclude every other extra)
     bool shells = false;
-    // per-molecule rows are set on the handle (they exclude every extra, united atoms and direct items)
+    // per-molecule rows are set on the handle (they exclude every extra, direct items, and united atoms unless ua_samples_flag)
     bool mol_rows = false;
-    // an order histogram is set on the handle (it excludes every extra but a geometry selection, united atoms and direct items)
+    // an order histogram is set on the handle (it excludes every extra but a geometry selection, direct items, and united atoms
+    // unless ua_samples_flag)
     bool dist = false;
     // neighbour classes are set on the handle (they exclude every extra, united atoms and direct items)
     bool classes = false;
+    // GORDER_FLAG_UA_SAMPLES: the two setters above accepted united-atom tiles (without it they refuse them, and mol_rows /
+    // dist never meet ua_tiles)
+    bool ua_samples_flag = false;
 };
+enum class UaKernel { None, Extras, Dist, Mol };    // what runs over the united-atom tiles
 enum class BondFamily { None, Tiled, Gather, TiledTw, TiledMaps, Extras, Shells, TiledMol, Dist, Classes };
 
 struct OrderRoute {
@@ -60,6 +67,9 @@ struct OrderRoute {
     int ua_mode = -1; bool ua_fast = false; // MODE of k_ua_extras, -1: no united-atom pass; k_ua_extras_fast
     bool map_accumulate = false, direct = false;   // k_map_accumulate behind every extras pass; k_bonds_direct
     bool speculative = false, fixup_ac = false, fixup_tw = false;   // k_spec_check + k_spec_fixup<AC, TW> follow
+    // k_ua_extras<ua_mode> (+ _fast) as ever, or with GORDER_FLAG_UA_SAMPLES k_ua_dist (from the extras' loop, beside Dist) /
+    // k_ua_mol (from the molecule rows' sub-range loop, beside TiledMol); ua_mode and ua_fast are then not read
+    UaKernel ua_kernel = UaKernel::None;
 };
 
 inline OrderRoute choose_order_route(const OrderRouteIn &in) {
@@ -86,6 +96,7 @@ inline OrderRoute choose_order_route(const OrderRouteIn &in) {
     r.items_by_slot = r.family == BondFamily::TiledTw || r.family == BondFamily::TiledMaps || (r.family == BondFamily::Extras && staged);
     r.ua_mode = !in.ua_tiles ? -1 : r.maps_only ? 1 : in.tw && !in.maps && rows_or_maps_only ? 3 : r.extras ? 2 : 0;
     r.ua_fast = in.ua_tiles && in.ua_fast_flag && !in.acos;     // (the two flags exclude each other at gorder_hip_create)
+    r.ua_kernel = !in.ua_tiles ? UaKernel::None : in.ua_samples_flag && in.mol_rows ? UaKernel::Mol : in.ua_samples_flag && in.dist ? UaKernel::Dist : UaKernel::Extras;
     r.map_accumulate = staged; r.direct = in.direct_items;
     r.speculative = (r.family == BondFamily::Tiled || (r.family == BondFamily::TiledTw && !r.tw_maps)) && in.leaflets && in.global_leaflets &&
                     in.spec_enabled && in.have_assignment && in.every_frame_assigns && !in.manual_frames && !in.normal_table;

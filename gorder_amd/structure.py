@@ -604,20 +604,22 @@ def class_profile(classes, groups, analysis: str, min_samples: int = 1) -> np.nd
 # ---- per-molecule order rows (HipEngine.molecule_rows): this project's own output, the reference has none ----------
 def molecule_groups(labels, analysis: str):
     """One group per molecule type — all its bonds — for HipEngine.set_molecule_rows: (groups: lists of accumulator slots,
-    names: the molecule types' names).  (`analysis` as elsewhere: "aa" or "cg"; united-atom labels have no molecule rows.)"""
-    if labels and hasattr(labels[0], "carbons"):
-        raise ValueError("molecule rows cover all-atom and coarse-grained analyses only")
-    if analysis not in ("aa", "cg"):
-        raise ValueError(f"analysis {analysis!r}")
-    groups = [list(range(ml.slot0, ml.slot0 + len(ml.bonds))) for ml in labels if len(ml.bonds)]
-    names = [ml.name for ml in labels if len(ml.bonds)]
+    names: the molecule types' names).  `analysis` as elsewhere: "aa" or "cg" for bond labels, "ua" for united-atom labels
+    (build_tables_ua) — a type's group is then the slots of every virtual hydrogen of its carbons, and the handle needs
+    FLAG_UA_SAMPLES.  A list that mixes both kinds of labels (a handle with bond-based and united-atom types) takes "ua"."""
+    n_slots = [sum(c.n_h for c in ml.carbons) if hasattr(ml, "carbons") else len(ml.bonds) for ml in labels]
+    has_ua = any(hasattr(ml, "carbons") for ml in labels)
+    if analysis not in ("aa", "cg", "ua") or (analysis == "ua") != has_ua:
+        raise ValueError(f"analysis {analysis!r} for {'united-atom' if has_ua else 'bond'} labels")
+    groups = [list(range(ml.slot0, ml.slot0 + n)) for ml, n in zip(labels, n_slots) if n]
+    names = [ml.name for ml, n in zip(labels, n_slots) if n]
     return groups, names
 
 
 def molecule_order(sums, counts, analysis: str, min_samples: int = 1) -> np.ndarray:
     """Order parameter of every (frame, group, molecule): float32 of the shape of `sums` / `counts` as
     HipEngine.molecule_rows() gives them, each entry by calc_order's truncating division (_mean_ticks), negated for "aa"
-    like every all-atom output; NaN below min_samples (a molecule whose type has no slot in the group: always)."""
+    and "ua" like every atomistic output; NaN below min_samples (a molecule whose type has no slot in the group: always)."""
     s, n = np.asarray(sums, dtype=np.int64), np.asarray(counts, dtype=np.int64)
     if s.shape != n.shape:
         raise ValueError("sums and counts differ in shape")
@@ -626,7 +628,7 @@ def molecule_order(sums, counts, analysis: str, min_samples: int = 1) -> np.ndar
     q[ok] = (np.abs(s[ok]) // n[ok]) * np.sign(s[ok])          # Rust i64 `/` truncates toward zero
     out = np.full(s.shape, np.nan, dtype=np.float32)
     out[ok] = (q[ok].astype(np.float64) / 1e6).astype(np.float32)
-    if analysis == "aa":
+    if analysis in ("aa", "ua"):
         out[ok] = -out[ok]
     return out
 

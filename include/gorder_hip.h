@@ -240,11 +240,19 @@ typedef struct {
  *   handle_pbc over the heads' bounding box), every row of S v is summed over the cells around its own in a fixed order, and
  *   a frame is spread over the whole device, one launch per Lanczos step and kind of work: a frame's flags and statistics
  *   depend on the frame alone.  Sums are associated in another order than on the dense route, so statistics agree with it
- *   to rounding, not bit for bit.  Without the flag nothing changes, the refusal above 8192 atoms included. */
+ *   to rounding, not bit for bit.  Without the flag nothing changes, the refusal above 8192 atoms included.
+ * GORDER_FLAG_UA_SAMPLES (opt-in): gorder_hip_set_order_histogram and gorder_hip_set_molecule_rows accept united-atom
+ *   molecule types, alone or beside bond-based types, and book every virtual C-H sample of the exact hydrogen construction
+ *   (k_ua_dist, k_ua_mol; see the two setters).  The two setters then refuse GORDER_FLAG_UA_FAST_NORMALISE: the
+ *   tolerance-bounded construction is not covered.  Without the flag nothing changes (the setters refuse united atoms);
+ *   with the flag on a handle that calls neither setter nothing changes either: the plan, the kernels queued and
+ *   gorder_hip_kernel_time_names are those of a handle without it.  Radial shells, bond correlation and neighbour classes
+ *   refuse united atoms with or without the flag. */
 typedef enum {
     GORDER_FLAG_TRIG_ACOS_COS = 1u,
     GORDER_FLAG_UA_FAST_NORMALISE = 2u,
-    GORDER_FLAG_CLUSTER_CUTOFF = 4u
+    GORDER_FLAG_CLUSTER_CUTOFF = 4u,
+    GORDER_FLAG_UA_SAMPLES = 8u
 } gorder_flags_t;
 
 typedef struct {
@@ -589,8 +597,17 @@ int gorder_hip_radial_thresholds(const float *radii, uint32_t n, float *thr);
  * gorder_hip_reset clears the rows and keeps the groups.
  * gorder_hip_molecule_rows_stats: facts of the lane order built at set time — n_runs: (tile, group, molecule) runs = global
  *   atomics per frame; max_runs_per_tile; max_tiles_per_word: how many tiles add into one (group, molecule) word.
- * Not covered: united atoms; rows together with ordermaps, timewise, geometry selections, dynamic or manual normals or radial
- *   shells; per-molecule error estimates and time averages on the device. */
+ * United atoms (GORDER_FLAG_UA_SAMPLES in tables.flags; without it the setter refuses united-atom molecule types as above):
+ *   the united-atom tiles run as k_ua_mol (its name in gorder_hip_kernel_time_names / _group) in place of k_ua_extras — the
+ *   exact hydrogen construction and the ticks of k_ua_extras bit for bit, so gorder_hip_finish is unchanged — and every
+ *   virtual C-H sample adds into the word of (frame, group of the hydrogen's slot, molecule) of the same staging block; the
+ *   hydrogens of one carbon may sit in different groups or in none.  Bond-based types on the same handle keep
+ *   k_bonds_tiled_mol; the block is copied out behind both kernels.  The setter then refuses GORDER_FLAG_UA_FAST_NORMALISE
+ *   (the message names the fast construction); every other refusal above stands.  gorder_hip_molecule_rows_stats counts the
+ *   united-atom tiles' (tile, group, molecule) words in n_runs, max_runs_per_tile and max_tiles_per_word: a molecule's
+ *   carbons are spread over the tiles of its group of 64 molecules, so a whole-lipid word is fed by several tiles.
+ * Not covered: the fast hydrogen construction; rows together with ordermaps, timewise, geometry selections, dynamic or manual
+ *   normals or radial shells; per-molecule error estimates and time averages on the device. */
 int gorder_hip_set_molecule_rows(gorder_hip_handle *h, const uint32_t *group_begin, const uint32_t *slots, uint32_t n_groups);
 int gorder_hip_molecule_rows_count(gorder_hip_handle *h, uint64_t *n_rows);
 int gorder_hip_molecule_rows(gorder_hip_handle *h, int32_t *sums, uint32_t *counts, uint64_t *frames, uint64_t capacity_rows);
@@ -627,11 +644,23 @@ int gorder_hip_molecule_rows_stats(gorder_hip_handle *h, uint64_t *n_runs, uint3
  *   pointer may be NULL.  After a batch that ended in an error the counts have the standing of the ordinary accumulators.
  *   Shards add their arrays on the host; gorder_hip_allreduce does NOT carry them.
  * gorder_hip_reset zeroes the counts and keeps the edges.
- * Not covered: united atoms; a histogram per frame or per molecule; sums per bin; histograms together with ordermaps, timewise
- *   rows, radial shells, molecule rows, or dynamic or manual normals. */
+ * United atoms (GORDER_FLAG_UA_SAMPLES in tables.flags; without it the setter refuses united-atom molecule types as above):
+ *   the united-atom tiles run as k_ua_dist (its name in gorder_hip_kernel_time_names / _group) in place of k_ua_extras — the
+ *   exact hydrogen construction and the ticks of k_ua_extras bit for bit, a geometry selection tested on the virtual bond's
+ *   position as k_ua_extras tests it — and every virtual C-H sample is counted in its bin, into the same replicas as
+ *   k_bonds_dist's, which keeps the bond-based types of the same handle.  The LDS table is sized by the widest tile of either
+ *   kind (a united-atom tile cut from a small molecule group holds many slots: 62 for six Berger POPC), and
+ *   GORDER_HIP_DIST_DIRECT applies to both kernels.  The setter then refuses GORDER_FLAG_UA_FAST_NORMALISE (the message names
+ *   the fast construction) and a plan with neither bond nor united-atom samples; every other refusal above stands.
+ * gorder_hip_order_histogram_route: which route the histogram set on the handle takes — *direct = 1: per-sample global
+ *   atomics (the table of the widest tile does not fit, or GORDER_HIP_DIST_DIRECT), 0: the LDS table —, and *table_bytes,
+ *   the size of that table.  Either pointer may be NULL; GORDER_ERR_INVALID_ARGUMENT with the histogram off.
+ * Not covered: the fast hydrogen construction; a histogram per frame or per molecule; sums per bin; histograms together with
+ *   ordermaps, timewise rows, radial shells, molecule rows, or dynamic or manual normals. */
 #define GORDER_HIST_MAX_BINS 256
 int gorder_hip_set_order_histogram(gorder_hip_handle *h, const int32_t *edges, uint32_t n_edges);
 int gorder_hip_order_histogram(gorder_hip_handle *h, uint64_t *counts, uint32_t *n_bins);
+int gorder_hip_order_histogram_route(gorder_hip_handle *h, uint32_t *direct, uint64_t *table_bytes);
 
 /* ---- bond reorientation: the second-rank autocorrelation of every bond vector, in the same pass over the frames ------------
  * Everything above says how ordered a bond is; this says how fast it reorients:  C(lag) = < P2( u(t) . u(t + lag) ) >  over t
