@@ -61,6 +61,7 @@ using gorder::Tile;
 #include "kernels_tile.h"
 #include "kernels_bonds.h"
 #include "kernels_extras.h"
+#include "kernels_ua.h"
 #include "kernels_molrows.h"
 #include "kernels_radial.h"
 #include "kernels_neighbours.h"
@@ -682,6 +683,8 @@ template <class F> void with_bool(bool v, F &&f) { if (v) f(std::true_type{}); e
 template <class F> void with_axis(int axis, F &&f) { with_int<2, 1, 0, -1>(axis, f); }
 template <class F> void with_npf(int npf, F &&f) { with_int<4, 5>(npf, f); }
 static_assert(gorder::kStageFrames == kRecFrames && gorder::kStageFrames == (uint32_t)kFramesPerStage, "order_route.h: frames of a stage");
+// the grid of the united-atom tile kernels: a workgroup per (chunk, tile), padded to a multiple of 8 (ua_tile_work, kernels_ua.h)
+uint64_t ua_grid(uint32_t n_tiles, uint32_t n_chunks) { return ((uint64_t)n_tiles * n_chunks + 7u) / 8u * 8u; }
 
 // k_bonds_tiled_mol over the frames of the batch, in sub-ranges the staging block holds: zero the block, run the order pass,
 // queue the copy of the sub-range's rows into the pinned chunks — stream-ordered, nothing waits
@@ -727,7 +730,7 @@ int launch_molecule_rows(gorder_hip_handle *h, const FrameArgs &a, const gorder:
         }
         if (ua) {       // the united-atom tiles add into the same block (GORDER_FLAG_UA_SAMPLES)
             const gorder::FrameChunks c = gorder::extras_chunks(nf, n_ua, h->wg_target, h->wg_capacity, false, true);
-            const uint64_t grid = ((uint64_t)n_ua * c.n_chunks + 7u) / 8u * 8u;      // see the XCD mapping in k_ua_extras
+            const uint64_t grid = ua_grid(n_ua, c.n_chunks);
             if (grid > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "batch too large");
             b.frames_per_chunk = c.frames_per_chunk;
             if (bonds) TIMING_MARK(h, "k_ua_mol");
@@ -938,7 +941,7 @@ int launch_ua_dist(gorder_hip_handle *h, const SubRange &s, const ExtraArgs &e) 
     da.n_edges = h->hist_edges; da.edges = h->d_hist_edges; da.rep = h->hist.rep; da.n_rep = h->hist.n_rep;
     // the edges, then the table of the widest tile or the epilogue's sums, whichever is larger
     const size_t lds = kDistEdgeBytes + std::max<size_t>(kUaSumBytes, h->hist_direct ? 0u : h->hist_table_words * sizeof(uint32_t));
-    const dim3 g((nt * c.n_chunks + 7u) / 8u * 8u), blk(kBlock);   // see the XCD mapping in k_ua_extras
+    const dim3 g((uint32_t)ua_grid(nt, c.n_chunks)), blk(kBlock);
     TIMING_MARK(h, "k_ua_dist");
     with_bool(literal_cosine(h), [&](auto AC) { with_bool(h->hist_direct, [&](auto DIRECT) {
         hipLaunchKernelGGL((k_ua_dist<AC(), DIRECT()>), g, blk, lds, h->stream, b, e, da, b.xyz, b.box9, b.aflags, b.arow, h->d_ua_tiles,
@@ -956,7 +959,7 @@ int launch_ua_pass(gorder_hip_handle *h, const SubRange &s, ExtraArgs &e) {
     const gorder::FrameChunks c = gorder::extras_chunks(s.nf(), nt, h->wg_target, h->wg_capacity, route.map_accumulate, false);
     FrameArgs b = s.frames(c);
     e.item_run = h->d_ua_item_run;
-    const dim3 g((nt * c.n_chunks + 7u) / 8u * 8u), blk(kBlock);   // see the XCD mapping in k_ua_extras
+    const dim3 g((uint32_t)ua_grid(nt, c.n_chunks)), blk(kBlock);
     TIMING_MARK(h, "k_ua_extras");
     with_bool(literal_cosine(h), [&](auto AC) { with_bool(route.ua_fast, [&](auto FAST) { with_int<0, 1, 2, 3>(route.ua_mode, [&](auto MODE) {
         if constexpr (FAST() && !AC())

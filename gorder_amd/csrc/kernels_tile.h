@@ -45,8 +45,8 @@
 //                      helpers it changed the VGPR count of nine of the twelve instantiations by up to six, in every
 //                      parameter shape that was tried (a walk object, plain local arrays handed to free functions, box
 //                      edges returned or loaded at the geometry, scalars instead of FrameArgs).
-//   ua_extras_body     three slots per lane, an LS stride and a strided slot loop: a helper that served it and the bond
-//                      tiles would branch on its caller.
+//   the united-atom tiles     three slots per lane, a kUaLS stride and a strided slot loop: a helper that served them and the
+//                      bond tiles would branch on its caller.  They share among themselves: kernels_ua.h.
 //   k_bonds_direct     has no tile (a thread per sample, global atomics straight away).
 //   TiledStage, bond_sample     are the shared per-sample arithmetic already.
 //   the host side (launch_orders, the handle), kernel names, timing labels, order_route.h, the ABI.

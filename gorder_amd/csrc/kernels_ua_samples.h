@@ -1,20 +1,14 @@
 // kernels_ua_samples.h — united-atom tiles with every virtual C-H sample booked a second time (GORDER_FLAG_UA_SAMPLES):
 // k_ua_dist, the order histogram (gorder_hip_set_order_histogram), and k_ua_mol, the per-molecule rows
 // (gorder_hip_set_molecule_rows; ua_molecule_rows.h has the tables).  Part of the single translation unit
-// gorder_hip.hip, behind kernels_hist.h; device code for gfx950 only.
+// gorder_hip.hip, behind kernels_ua.h and kernels_hist.h (DistArgs); device code for gfx950 only.
 //
-// Both are k_ua_extras' exact path — ua_extras_body of kernels_extras.h, which stays as it is: a lane per carbon, the same
-// gather of its 3-4 atoms, ua_carbon_pairs / ua_carbon / ua_carbon_slow, the same tick per hydrogen, the same error keys,
-// the same epilogue into the same replicas — with the sample lambda restated here (ua_sample_tick) and a second output.
+// Both are k_ua_extras' exact path through the shared pieces of kernels_ua.h — ua_tile_work, ua_tile_lane, ua_fetch,
+// ua_raise_undefined, ua_carbon_exact, ua_tick, ua_fold_sums — with a second output, which is all this file holds.
 // gorder_hip_finish of a handle with either feature returns what it returns without.
 #pragma once
 
 namespace {
-
-constexpr uint32_t kUaLS = 3u * kBlock;                     // local slots of a united-atom tile (<= 3 hydrogens per carbon)
-constexpr uint32_t kUaSumBytes = 2u * kUaLS * 12u;          // the epilogue's [2][kUaLS] u64 sums + [2][kUaLS] u32 counts
-// (the chunks of a molecule-rows sub-range are whole stages of k_bonds_tiled_mol, extras_chunks; k_ua_mol's stage loop takes
-// any chunk length, its last stage the tail)
 
 struct UaMolArgs {
     const uint32_t *word_begin;             // [n_ua_tiles + 1] (UaMolRows::word_begin)
@@ -25,21 +19,6 @@ struct UaMolArgs {
     uint32_t list_bytes;                    // ua_mol_list_bytes(max_local): where the word buffers begin in the dynamic LDS
     uint32_t n_buf;                         // ua_mol_buffers(max_local)
 };
-
-// the tick of one virtual hydrogen: the sample lambda of ua_extras_body (exact path, no per-molecule normals), restated —
-// the axis short form under its guards, gm_calc_sch otherwise
-template <bool ACOS_COS>
-__device__ __forceinline__ int ua_sample_tick(const V3 v, const FrameArgs &a, const ExtraArgs &e, float axis_x, float axis_y, float axis_z) {
-    float sch;
-    const float s2 = (v.x * v.x + v.y * v.y) + v.z * v.z;
-    if (!ACOS_COS && e.axis >= 0 && s2 >= 0x1p-40f && s2 <= 0x1p+40f) {
-        const float prod = __builtin_fmaf(v.z, axis_z, __builtin_fmaf(v.y, axis_y, v.x * axis_x));
-        sch = (1.5f * gm_div_core(prod * prod, s2)) - 0.5f;
-    } else {
-        sch = gm_calc_sch<ACOS_COS>(v.x, v.y, v.z, a.nx, a.ny, a.nz, a.n2, a.n2sq);
-    }
-    return gm_tick(sch);
-}
 
 // MOL = false: k_ua_dist.  Dynamic LDS: the edges (kDistEdgeBytes), then the table u32 [planes][n bins][t.n_slots] — local
 // slot it.lslot0 + k the minor index — whose place serves the epilogue's sums once it has been sent out (DIRECT: from the
@@ -52,28 +31,18 @@ __device__ __forceinline__ int ua_sample_tick(const V3 v, const FrameArgs &a, co
 // barrier (the buffer they go to was zeroed before the barrier of the stage in between); with one buffer a second
 // barrier ends the stage.  The frame loop is not unrolled over the stage: no per-frame register arrays, no scratch from it.
 template <bool ACOS_COS, bool MOL, bool DIRECT>
-__device__ __forceinline__ void ua_samples_body(FrameArgs a_in, ExtraArgs e, DistArgs s, UaMolArgs m, const float *__restrict__ xyz,
-                                                const float *__restrict__ box9, const uint8_t *__restrict__ aflags,
-                                                const uint32_t *__restrict__ arow, const Tile *__restrict__ tiles,
-                                                const gorder::UaItem *__restrict__ items, const uint32_t *__restrict__ tile_slots,
-                                                uint32_t n_tiles, unsigned char *l_dyn, unsigned long long *l_s, uint32_t *l_n) {
+__device__ __forceinline__ void ua_samples_body(FrameArgs a_in, ExtraArgs e, DistArgs s, UaMolArgs m, GORDER_UA_KERNEL_ARGS, unsigned char *l_dyn,
+                                                unsigned long long *l_s, uint32_t *l_n) {
     constexpr uint32_t LS = kUaLS, G = gorder::kUaMolStage;
     FrameArgs a = a_in;
     a.xyz = xyz; a.box9 = box9; a.aflags = aflags; a.arow = arow;
-    // the XCD mapping of k_ua_extras (the host pads the grid to a multiple of 8)
-    const uint32_t per_xcd = gridDim.x / 8u, work = (blockIdx.x % 8u) * per_xcd + blockIdx.x / 8u;
-    const uint32_t tile_id = work % n_tiles, chunk = work / n_tiles;
-    if ((size_t)chunk * a_in.frames_per_chunk >= a_in.n_frames - a_in.frame0) return;    // padding workgroup
-    const Tile t = tiles[tile_id];
-    const uint32_t tid = threadIdx.x;
-    const bool active = tid < t.n_items;
-    gorder::UaItem it{};
-    if (active) it = items[t.item0 + tid];
-    const uint32_t kind = it.kind;
-    const int nh = kind == GORDER_UA_CH3 ? 3 : (kind == GORDER_UA_CH2 ? 2 : 1);
-    const uint32_t gslot0 = active ? tile_slots[t.slot0 + it.lslot0] : 0;
-    const uint32_t f_begin = a.frame0 + chunk * a.frames_per_chunk;
-    const uint32_t f_end = min(a.n_frames, f_begin + a.frames_per_chunk);
+    const UaWork wk = ua_tile_work(n_tiles, a_in.frame0, a_in.frames_per_chunk, a_in.n_frames);
+    if (wk.padding) return;
+    const UaLane tc = ua_tile_lane(tiles, items, tile_slots, wk.tile_id);
+    const Tile t = tc.t;
+    const gorder::UaItem it = tc.it;
+    const uint32_t tile_id = wk.tile_id, tid = tc.tid, gslot0 = tc.gslot0, f_begin = wk.f_begin, f_end = wk.f_end;
+    const bool active = tc.active;
     const size_t fstride = (size_t)a.n_atoms * 3u;
     // ---- the second output's LDS
     int32_t *const l_edges = reinterpret_cast<int32_t *>(l_dyn);
@@ -98,62 +67,34 @@ __device__ __forceinline__ void ua_samples_body(FrameArgs a_in, ExtraArgs e, Dis
         for (uint32_t k = tid; k < 2 * LS; k += kBlock) { l_s[k] = 0; l_n[k] = 0; }
     __syncthreads();
     unsigned long long *const dist_rep = MOL ? nullptr : s.rep + (size_t)(blockIdx.x % s.n_rep) * n_bins * 2u * a.n_acc;
-    long long s_tot[3] = {0, 0, 0}, s_up[3] = {0, 0, 0};
-    uint32_t n_tot[3] = {0, 0, 0}, n_up[3] = {0, 0, 0};
+    UaAcc acc;
     int bad = 0;
     const bool pbc = a.pbc != 0;
     const UaConsts uc{e.sin_tet, e.cos_tet, e.sin_ch3, e.cos_ch3, e.sin_half, e.cos_half};
     const float axis_x = e.axis == 0 ? 1.0f : 0.0f, axis_y = e.axis == 1 ? 1.0f : 0.0f, axis_z = e.axis == 2 ? 1.0f : 0.0f;
     const float *src[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) src[q] = xyz + ((size_t)t.atom0 + (active ? it.l[q] : 0u)) * 3u;
+    ua_sources(src, xyz, tc);
     // one frame of this lane's carbon; book(k, tick, leaflet) is the second output of hydrogen k
     auto frame = [&](const uint32_t f, auto &&book) {
         V3 bx3{1.0f, 1.0f, 1.0f};
-        if (pbc) {
-            const float *b = a.box9 + 9 * (size_t)f;
-            bx3 = {b[0], b[4], b[8]};
-        }
+        if (pbc) bx3 = ua_box_edges(a.box9, f);
         uint8_t lf_raw = 0;
         if (a.leaflets) lf_raw = a.aflags[(size_t)a.arow[f] * a.n_mol_total + it.mol];
-        UaCarbon c;
-        const size_t o = (size_t)f * fstride;
-        c.p0 = {src[0][o], src[0][o + 1], src[0][o + 2]};
-        c.p1 = {src[1][o], src[1][o + 1], src[1][o + 2]};
-        c.p2 = {src[2][o], src[2][o + 1], src[2][o + 2]};
-        c.p3 = {src[3][o], src[3][o + 1], src[3][o + 2]};
-        // the atoms are checked in index order (uaorder.rs:400-437); the smallest key wins
-        if (__builtin_expect((int)__builtin_isunordered(c.p0.x, c.p1.x) | (int)__builtin_isunordered(c.p2.x, c.p3.x), 0)) {
-            if (c.p0.x != c.p0.x) raise_error(a.err, GORDER_ERR_UNDEFINED_POSITION, f, kStageTypes, gslot0, 1, it.mol, 0);
-            else if (c.p1.x != c.p1.x) raise_error(a.err, GORDER_ERR_UNDEFINED_POSITION, f, kStageTypes, gslot0, 1, it.mol, 1);
-            else if (c.p2.x != c.p2.x) raise_error(a.err, GORDER_ERR_UNDEFINED_POSITION, f, kStageTypes, gslot0, 1, it.mol, 2);
-            else if (c.p3.x != c.p3.x) raise_error(a.err, GORDER_ERR_UNDEFINED_POSITION, f, kStageTypes, gslot0, 1, it.mol, 3);
-        }
-        bool slow = false;
-        UaBonds ub;
-        if (kind == GORDER_UA_CH2 || kind == GORDER_UA_CH3) {       // the two common kinds: paired arithmetic
-            ub = ua_carbon_pairs(kind, c, uc, bx3, pbc, slow);
-        } else {
-            PbcStep ps{bx3, pbc};
-            ub = ua_carbon(kind, c, uc, ps);
-            slow = ps.slow;
-        }
-        if (__builtin_expect(slow, 0)) {
-            ub = ua_carbon_slow(kind, c, uc, bx3, pbc);
-            bad |= ub.bad;
-        }
+        const UaCarbon c = ua_fetch(src, f, fstride);
+        ua_raise_undefined(a.err, c, f, gslot0, it.mol);
+        const UaBonds ub = ua_carbon_exact(tc.kind, c, uc, bx3, pbc, bad);
         int leaflet = -1;
         if (a.leaflets) leaflet = lf_raw ? 1 : 0;
         auto sample = [&](const int k, const V3 v, const V3 b) {
-            if (k >= nh) return;
-            const int tick = ua_sample_tick<ACOS_COS>(v, a, e, axis_x, axis_y, axis_z);
+            if (k >= tc.nh) return;
+            const int tick = ua_tick<ACOS_COS>(v, e.axis >= 0, axis_x, axis_y, axis_z, a.nx, a.ny, a.nz, a.n2, a.n2sq);
             if (!MOL) {
                 const float box[3] = {bx3.x, bx3.y, bx3.z};
                 if (e.geom_kind && !geom_inside(e, e.shapes + 8 * (size_t)f, b.x, b.y, b.z, box, pbc, bad)) return;
             }
-            s_tot[k] += tick;
-            n_tot[k] += 1;
-            if (leaflet == 0) { s_up[k] += tick; n_up[k] += 1; }
+            acc.s_tot[k] += tick;
+            acc.n_tot[k] += 1;
+            if (leaflet == 0) { acc.s_up[k] += tick; acc.n_up[k] += 1; }
             book(k, tick, leaflet);
         };
         sample(0, ub.v0, ub.b0);
@@ -214,59 +155,32 @@ __device__ __forceinline__ void ua_samples_body(FrameArgs a_in, ExtraArgs e, Dis
         for (uint32_t k = tid; k < 2 * LS; k += kBlock) { l_s[k] = 0; l_n[k] = 0; }
         __syncthreads();
     }
-    // ---- the ordinary sums: k_ua_extras' epilogue
-    if (active) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            if (!n_tot[k]) continue;
-            atomicAdd(&l_s[it.lslot0 + k], (unsigned long long)s_tot[k]);
-            atomicAdd(&l_n[it.lslot0 + k], n_tot[k]);
-            if (n_up[k]) {
-                atomicAdd(&l_s[LS + it.lslot0 + k], (unsigned long long)s_up[k]);
-                atomicAdd(&l_n[LS + it.lslot0 + k], n_up[k]);
-            }
-        }
-    }
-    __syncthreads();
-    unsigned long long *accp = a.rep + (size_t)(blockIdx.x % a.n_rep) * 4u * a.n_acc;
-    for (uint32_t ls = tid; ls < t.n_slots; ls += kBlock) {
-        if (!l_n[ls]) continue;
-        const uint32_t slot = tile_slots[t.slot0 + ls];
-        atomicAdd(&accp[slot], l_s[ls]);
-        atomicAdd(&accp[2u * a.n_acc + slot], (unsigned long long)l_n[ls]);
-        if (l_n[LS + ls]) {
-            atomicAdd(&accp[a.n_acc + slot], l_s[LS + ls]);
-            atomicAdd(&accp[3u * a.n_acc + slot], (unsigned long long)l_n[LS + ls]);
-        }
-    }
+    // ---- the ordinary sums.  l_s, l_n: zeroed before the first barrier of this body and untouched since (k_ua_mol, DIRECT), or
+    // the table's place: the barrier behind the read-out above ended its last reads, the one behind the zeroing the zeroing
+    ua_fold_sums(a.rep, a.n_rep, a.n_acc, t, tile_slots, active, it.lslot0, tid, acc, l_s, l_n);
 }
-
-#define GORDER_UA_SAMPLE_ARGS                                                                                              \
-    const float *__restrict__ xyz, const float *__restrict__ box9, const uint8_t *__restrict__ aflags,                        \
-        const uint32_t *__restrict__ arow, const Tile *__restrict__ tiles, const gorder::UaItem *__restrict__ items,          \
-        const uint32_t *__restrict__ tile_slots, uint32_t n_tiles
 
 // grid = n_ua_tiles * n_chunks padded to a multiple of 8 (dist_chunks with the united-atom tile count); dynamic LDS =
 // kDistEdgeBytes + max(kUaSumBytes, the table of the widest tile)
 template <bool ACOS_COS, bool DIRECT>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_ua_dist(FrameArgs a_in, ExtraArgs e, DistArgs s,
-                                                                                               GORDER_UA_SAMPLE_ARGS) {
+                                                                                               GORDER_UA_KERNEL_ARGS) {
     extern __shared__ __attribute__((aligned(16))) unsigned char l_ua_dyn[];
     unsigned long long *const l_s = reinterpret_cast<unsigned long long *>(l_ua_dyn + kDistEdgeBytes);
     ua_samples_body<ACOS_COS, false, DIRECT>(a_in, e, s, UaMolArgs{}, xyz, box9, aflags, arow, tiles, items, tile_slots, n_tiles, l_ua_dyn,
                                              l_s, reinterpret_cast<uint32_t *>(l_s + 2u * kUaLS));
 }
 
-// grid likewise (extras_chunks in whole stages per staging sub-range, a.frame0 = the sub-range's first frame); dynamic LDS =
-// ua_mol_lds_bytes(max_local)
+// grid likewise (extras_chunks in whole stages of k_bonds_tiled_mol per staging sub-range — the stage loop here takes any chunk
+// length, its last stage the tail —, a.frame0 = the sub-range's first frame); dynamic LDS = ua_mol_lds_bytes(max_local)
 template <bool ACOS_COS>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_ua_mol(FrameArgs a_in, ExtraArgs e, UaMolArgs m,
-                                                                                              GORDER_UA_SAMPLE_ARGS) {
+                                                                                              GORDER_UA_KERNEL_ARGS) {
     extern __shared__ __attribute__((aligned(16))) unsigned char l_ua_dyn[];
     __shared__ unsigned long long l_s[2 * kUaLS];
     __shared__ uint32_t l_n[2 * kUaLS];
     ua_samples_body<ACOS_COS, true, false>(a_in, e, DistArgs{}, m, xyz, box9, aflags, arow, tiles, items, tile_slots, n_tiles, l_ua_dyn, l_s, l_n);
 }
-#undef GORDER_UA_SAMPLE_ARGS
+#undef GORDER_UA_KERNEL_ARGS
 
 }  // namespace

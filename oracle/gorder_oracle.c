@@ -424,7 +424,7 @@ static int predict_hydrogens_mode(uint32_t kind, const float pos[4][3], const fl
     return -2;
 }
 /* ---- GORDER_FLAG_UA_FAST_NORMALISE: restatement of the DEVICE's tolerance-bounded construction
- * (gorder_amd/csrc/kernels_extras.h: ua_fast_rsqrt, PbcFast, ua_carbon_fast), operation for operation — every step
+ * (gorder_amd/csrc/kernels_ua.h: ua_fast_rsqrt, PbcFast, ua_carbon_fast), operation for operation — every step
  * there is an IEEE mul / add / fma, rint or floor, so the bits are reproducible here.  Not the reference's arithmetic:
  * the LIBM mode never takes this path; tools/ua_fast_fidelity.py measures one against the other. */
 static inline float fast_rsqrt(float x) {

@@ -616,3 +616,60 @@ def test_ua(built, monkeypatch, mode, pbc, flags):
         assert 0 < got.counts[0].sum() < N * len(label[0]) * tables.n_acc
     if tables.ordermap.enabled:
         assert 0 < got.map_counts[0].sum() < got.counts[0].sum()                # the NaN hydrogens are on no tile
+
+
+# ---- UA, every sample booked a second time -------------------------------------------------------------------------------------
+import functools        # noqa: E402
+
+import test_ua_samples_gpu as uas        # noqa: E402
+
+UA_SAMPLE_FLAGS = {"exact": abi.FLAG_UA_SAMPLES, "exact acos": abi.FLAG_UA_SAMPLES | FLAG_TRIG_ACOS_COS}
+
+
+@functools.lru_cache(maxsize=None)
+def ua_samples_reference(pbc, flags):
+    """The degenerate carbons with GORDER_FLAG_UA_SAMPLES -> (tables, xyz, box9, the split oracle's per-sample ticks, the
+    unsplit oracle's leaflet flags and its finish())."""
+    tables, xyz, box9, _ = ua_case(pbc, leaflets=LEAFLETS_GLOBAL, flags=UA_SAMPLE_FLAGS[flags])
+    o = oracle.OracleEngine(dataclasses.replace(tables, flags=tables.flags & FLAG_TRIG_ACOS_COS), trig=trig_of(tables))
+    o.submit(xyz, box9, FRAMES)
+    return (tables, xyz, box9, uas.oracle_samples(tables, xyz, box9, trig_of(tables), FRAMES), uas.oracle_flags(tables, xyz, box9, FRAMES),
+            o.finish())
+
+
+@pytest.mark.parametrize("output", ["histogram lds", "histogram direct", "rows"])
+@pytest.mark.parametrize("flags", list(UA_SAMPLE_FLAGS))
+@pytest.mark.parametrize("pbc", [True, False])
+def test_ua_samples(built, monkeypatch, pbc, flags, output):
+    """k_ua_dist (the LDS table and the direct route) and k_ua_mol on test_ua's carbons: the same hand-over to ua_carbon_slow
+    and the same guard of the tick as k_ua_extras, so the NaN hydrogens are tick 0, counted, in the bin [0, 1) and in their
+    molecule's word.  Expected: the split oracle of test_ua_samples_gpu.py; finish() is the unsplit oracle's."""
+    set_route(monkeypatch, {"GORDER_HIP_DIST_DIRECT": "1"} if output == "histogram direct" else {})
+    tables, xyz, box9, samples, sides_, want = ua_samples_reference(pbc, flags)
+    assert samples.present.all() and (samples.tick == 0).any() and 0 < int(sides_.sum()) < sides_.size
+    eng = HipEngine(tables)
+    eng.kernel_time()
+    groups = [[s] for s in range(tables.n_acc)]
+    if output == "rows":
+        eng.set_molecule_rows(groups)
+    else:
+        eng.set_order_histogram(EDGES)
+        assert eng.order_histogram_route()["direct"] == (output == "histogram direct")
+    for a, b in CUTS:
+        eng.submit_host(xyz[a:b], None if box9 is None else box9[a:b], FRAMES[a:b])
+    if output == "rows":
+        sums, counts, frames = eng.molecule_rows()
+        want_s, want_c = uas.want_rows(samples, groups, tables.n_molecules_total)
+        np.testing.assert_array_equal(frames, FRAMES)
+        np.testing.assert_array_equal(counts.astype(np.int64), want_c)
+        np.testing.assert_array_equal(sums.astype(np.int64), want_s)
+        assert counts.sum() == N * tables.n_samples_per_frame
+    else:
+        got = eng.order_histogram()
+        hist = uas.want_hist(samples, EDGES, sides_, tables.n_acc)
+        assert got.dtype == np.uint64 and got.shape == hist.shape
+        np.testing.assert_array_equal(got, hist)
+        assert EDGES[2] == 0 and int(got[2, 0].sum()) == int((samples.tick == 0).sum()) > 0     # the bin [0, 1): the NaN hydrogens
+    res = eng.finish()
+    ran(eng, "k_ua_mol" if output == "rows" else "k_ua_dist", never=["k_ua_extras", "k_bonds_tiled", "k_bonds_extras"])
+    same_results(res, want)

@@ -55,10 +55,10 @@ class Samples:
     mol: np.ndarray         # [samples] molecule (molecule-type-major, as the leaflet flags)
 
 
-def oracle_samples(tables, xyz, box, trig):
+def oracle_samples(tables, xyz, box, trig, frames=FRAMES):
     split, slot0 = split_tables(tables)
     ref = oracle.OracleEngine(split, trig=trig)
-    ref.submit(xyz, box, FRAMES[:len(xyz)])
+    ref.submit(xyz, box, frames[:len(xyz)])
     tw_s, tw_c = ref.timewise(len(xyz))
     assert int(tw_c[:, 0].max()) == 1                                    # a slot of the split tables is one sample
     cols, slots, mols = [], [], []
@@ -72,14 +72,14 @@ def oracle_samples(tables, xyz, box, trig):
     return Samples(tw_s[:, 0, cols].astype(np.int64), tw_c[:, 0, cols] == 1, np.array(slots), np.array(mols))
 
 
-def oracle_flags(tables, xyz, box):
+def oracle_flags(tables, xyz, box, frames=FRAMES):
     """uint8 [frames, molecules]: the side (Upper = 0) every frame's samples are booked on, or None without leaflets."""
     if tables.leaflets.method == LEAFLETS_NONE:
         return None
     ref = oracle.OracleEngine(dataclasses.replace(tables, flags=0), trig=oracle.TRIG_DIRECT)
     rows = []
     for f in range(len(xyz)):
-        ref.submit(xyz[f:f + 1], None if box is None else box[f:f + 1], FRAMES[f:f + 1])
+        ref.submit(xyz[f:f + 1], None if box is None else box[f:f + 1], frames[f:f + 1])
         rows.append(ref.leaflets()[0].copy())
     return np.array(rows)
 
