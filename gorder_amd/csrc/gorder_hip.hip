@@ -48,6 +48,7 @@
 #include "order_hist.h"
 #include "bond_corr.h"
 #include "neighbour_classes.h"
+#include "switches.h"
 
 #pragma clang fp contract(off)
 
@@ -148,8 +149,6 @@ struct BondCorr {
     uint32_t plane_items = 0;                   // n_tiles * kBlock
     uint64_t seen = 0;                          // analysed frames since create / reset: frame g lives in plane g mod R
     RepAcc acc;
-    uint32_t forced_subrange = 0;               // GORDER_HIP_CORR_SUBRANGE, read once at gorder_hip_create
-    bool chunk_major = false;                   // GORDER_HIP_CORR_GRID=chunks, read once likewise: a workgroup walks every group of lags
     bool on() const { return !lags.empty(); }
 };
 
@@ -166,14 +165,12 @@ struct NeighbourClasses {
     uint32_t rows_frames = 0;                   // frames the rows hold right now (the last batch, or its last sub-range)
     RepAcc acc;
     size_t lds_bytes = 0;                       // the LDS table of the widest tile
-    bool direct = false;                        // per-sample global atomics: the table does not fit, or ...
-    bool force_direct = false;                  // ... GORDER_HIP_NB_DIRECT, read once at gorder_hip_create
-    uint32_t forced_subrange = 0;               // GORDER_HIP_NB_SUBRANGE, read once likewise
-    uint64_t row_bytes = gorder::kClassRowBytes;    // the most the class rows take; GORDER_HIP_NB_ROW_BYTES, read once likewise (tests set it small)
+    bool direct = false;                        // per-sample global atomics: the table does not fit, or GORDER_HIP_NB_DIRECT
     bool on() const { return n_classes != 0; }
 };
 
 struct gorder_hip_handle {
+    gorder::Switches sw;                // the GORDER_HIP_* switches as gorder_hip_create found them; nothing writes them afterwards
     // staging buffers of gorder_hip_run_trajectory, kept between calls (trajectory_driver.h: TrajCache)
     void *traj_cache = nullptr;
     void (*traj_cache_free)(gorder_hip_handle *) = nullptr;
@@ -219,7 +216,6 @@ struct gorder_hip_handle {
     size_t map_lds_bytes = 0;
     bool map_staged = false;       // the packed map of one slot fits LDS: stage + accumulate instead of one atomic per sample
     uint64_t map_pending = 0;      // upper bound of the samples one packed word may hold since the last fold
-    uint64_t map_fold_limit = kMapFoldLimit;   // GORDER_HIP_MAP_FOLD_LIMIT lowers it (tests)
     uint32_t map_max_mol = 1;      // most molecules of one type = most samples per tile and frame
     DBuf<u64> d_tw_sums, d_tw_cnts;
     uint64_t tw_cap = 0;               // rows (frames) those two hold
@@ -254,8 +250,7 @@ struct gorder_hip_handle {
     DBuf<uint32_t> d_err;
     u64 *d_acc = nullptr;              // [4][n_acc] + total_frames: a view of own_acc, or of the memory gorder_hip_bind_accumulators bound
     DBuf<u64> own_acc;                 // the block the handle allocated itself (empty once external memory is bound)
-    DBuf<u64> d_rep;                   // [n_rep][4][n_acc] (see k_fold_replicas)
-    uint32_t n_rep = 32;
+    DBuf<u64> d_rep;                   // [sw.replicas][4][n_acc] (see k_fold_replicas; GORDER_HIP_REPLICAS)
     bool rep_dirty = false;
     size_t acc_words = 0;
     // leaflets
@@ -274,7 +269,6 @@ struct gorder_hip_handle {
     DBuf<uint8_t> d_cl_carry, d_cl_is0;
     DBuf<float> d_cl_stats;
     uint32_t cl_slab = 1, cl_m_max = 0;
-    bool cl_stored_w = false;              // GORDER_HIP_CLUSTER_STORED_W: S v reads W stored once a frame instead of recomputing it
     bool cl_have_carry = false;
     bool cl_cut = false;                   // GORDER_FLAG_CLUSTER_CUTOFF: kernels_cluster_cutoff.h, its own scratch layout
     uint32_t cl_tiles = 0, cl_sort = 0;    // row tiles and counting-sort blocks of a frame (cut-off route)
@@ -316,9 +310,7 @@ struct gorder_hip_handle {
     int axis = -1;   // 0/1/2 when the static normal is exactly that unit axis (kernel specialisation)
     int frames_per_stage = kFramesPerStage;   // G = 4 frames staged per pass (8 was measured at 26 % and spilled: removed in round 4)
     bool membrane_is_frame = false;            // the membrane group is every atom of the frame, in order
-    bool use_gather = false;                   // GORDER_HIP_KERNEL=gather: L1-gather kernel instead of LDS staging
     uint32_t wg_capacity = 256u * 6u;          // co-resident workgroups of the tiled kernel on this device
-    uint32_t wg_target = 0;                    // GORDER_HIP_WG_TARGET: force the workgroup count aimed at
     uint32_t lw = 0;
     size_t lds_bytes = 0;
     uint64_t n_frames = 0;
@@ -378,17 +370,14 @@ struct gorder_hip_handle {
     float shell_thr[GORDER_RADIAL_MAX_SHELLS] = {};          // local_radius_threshold of the radii
     RepAcc shells;
     size_t shell_lds_bytes = 0;                 // the LDS table of the widest tile
-    bool shell_direct = false;                  // per-sample global atomics: the table does not fit, or ...
-    bool shell_force_direct = false;            // ... GORDER_HIP_RADIAL_DIRECT, read once at gorder_hip_create
+    bool shell_direct = false;                  // per-sample global atomics: the table does not fit, or GORDER_HIP_RADIAL_DIRECT
     // order distributions (gorder_hip_set_order_histogram; kernels_hist.h): the counts [n_bins][2][n_acc] (total, upper), their
     // replicas [hist.n_rep][n_bins][2][n_acc] (k_bonds_dist adds into them), the edges on the device
     uint32_t hist_edges = 0;                    // n_edges, 0 = off
     DBuf<int32_t> d_hist_edges;
     RepAcc hist;
     size_t hist_table_words = 0;                // the LDS table of the widest tile, in u32 words
-    bool hist_direct = false;                   // per-sample global atomics: the table does not fit, or ...
-    bool hist_force_direct = false;             // ... GORDER_HIP_DIST_DIRECT, read once at gorder_hip_create
-    uint32_t hist_samples_per_word = gorder::kDistSamplesPerWord;       // dist_chunks; GORDER_HIP_DIST_SAMPLES_PER_WORD, read once likewise
+    bool hist_direct = false;                   // per-sample global atomics: the table does not fit, or GORDER_HIP_DIST_DIRECT
     BondCorr corr;
     NeighbourClasses nb;
     // per-molecule rows (gorder_hip_set_molecule_rows; molecule_rows.h, kernels_molrows.h): the lane order and the run tables,
@@ -401,7 +390,6 @@ struct gorder_hip_handle {
     DBuf<gorder::UaLaneWords> d_ua_mol_lanes;
     DBuf<uint32_t> d_ua_mol_words, d_ua_mol_word_begin;
     DBuf<u64> d_mol_stage;
-    size_t mol_stage_bytes = (size_t)1 << 30;   // GORDER_HIP_MOL_ROWS_STAGING, read once at gorder_hip_create
     gorder::CollectStore mol_store;             // rows of n_groups x n_mol_total u64
     const uint64_t *mol_frame_index = nullptr;  // the batch being submitted: its frames' labels
     bool mol_failed = false;                    // a device error ended the run: its batch and the later ones append nothing
@@ -460,7 +448,7 @@ int ensure(gorder_hip_handle *h, DBuf<T> &buf, size_t need, bool *grew = nullptr
 // an accumulator block of `words` words and its replicas (as many as the ordinary sums have, gorder::replica_count), zeroed
 // in the order of the handle's stream
 int alloc_zeroed(gorder_hip_handle *h, RepAcc &r, size_t words) {
-    if (!r.alloc(words, h->n_rep)) {
+    if (!r.alloc(words, h->sw.replicas)) {
         r.reset();
         return alloc_failed(h, "hipMalloc");
     }
@@ -590,17 +578,12 @@ int timing_mark(gorder_hip_handle *h, const char *label) {
         if (tm_ != GORDER_OK) return tm_;                       \
     } while (0)
 
-bool env_flag(const char *name) {
-    const char *v = getenv(name);
-    return v && *v && strcmp(v, "0") != 0;
-}
-
 // Launch the order kernels of one batch (internal).
 // fold the replicas into the accumulator block (stream-ordered; cheap: 4 * n_acc threads)
 int fold_replicas(gorder_hip_handle *h) {
     if (!h->rep_dirty || !h->d_rep) return GORDER_OK;
     const uint32_t n = 4u * h->plan.n_acc;
-    hipLaunchKernelGGL(k_fold_replicas, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_acc, h->d_rep, h->n_rep, n);
+    hipLaunchKernelGGL(k_fold_replicas, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_acc, h->d_rep, h->sw.replicas, n);
     HIP_TRY(h, hipGetLastError());
     h->rep_dirty = false;
     return GORDER_OK;
@@ -621,7 +604,7 @@ int fold_maps(gorder_hip_handle *h) {
 // the cell list of `ns` slab frames (k_local_build, or bin / scan / scatter for very large atom sets); `counts` are the
 // lo.cell_count and lo.cell_fill words the three-kernel form needs zeroed
 int launch_cell_list(gorder_hip_handle *h, const LocalArgs &lo, uint32_t ns, uint32_t n_list, void *counts, size_t count_bytes) {
-    const bool three = env_flag("GORDER_HIP_LOCAL_THREE_KERNELS");   // A/B switch; also what membranes beyond kLocalBuildMax take
+    const bool three = h->sw.local_three_kernels;    // GORDER_HIP_LOCAL_THREE_KERNELS, an A/B switch; also what membranes beyond kLocalBuildMax take
     TIMING_MARK(h, n_list <= kLocalBuildMax && !three ? "k_local_build" : "k_local_bin + k_local_scan + k_local_scatter");
     if (n_list <= kLocalBuildMax && !three) {
         // (a thread keeps a byte per atom it places: the kernel compiled for 2, 5 or 8 trips of eight atoms per thread)
@@ -695,7 +678,7 @@ int launch_molecule_rows(gorder_hip_handle *h, const FrameArgs &a, const gorder:
     const uint32_t n_tiles = (uint32_t)p.tiles.size(), n_ua = (uint32_t)p.ua_tiles.size();
     const bool ac = (h->tables.flags & GORDER_FLAG_TRIG_ACOS_COS) != 0;
     const size_t wpf = (size_t)h->mol.n_groups * p.n_mol_total;
-    const uint32_t sub = gorder::molecule_rows_subrange(a.n_frames, wpf, h->mol_stage_bytes);
+    const uint32_t sub = gorder::molecule_rows_subrange(a.n_frames, wpf, h->sw.mol_rows_staging);      // (GORDER_HIP_MOL_ROWS_STAGING)
     int st;
     if ((st = ensure(h, h->d_mol_stage, wpf * sub)) != GORDER_OK) return st;
     MolRowArgs mr{};
@@ -712,7 +695,7 @@ int launch_molecule_rows(gorder_hip_handle *h, const FrameArgs &a, const gorder:
         TIMING_MARK(h, bonds ? route.label : "k_ua_mol");
         HIP_TRY(h, hipMemsetAsync(h->d_mol_stage, 0, wpf * nf * sizeof(unsigned long long), h->stream));
         if (bonds) {
-            const gorder::FrameChunks c = gorder::extras_chunks(nf, n_tiles, h->wg_target, h->wg_capacity, false, true);
+            const gorder::FrameChunks c = gorder::extras_chunks(nf, n_tiles, h->sw.wg_target, h->wg_capacity, false, true);
             const uint64_t grid = (uint64_t)n_tiles * c.n_chunks;
             if (grid > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "batch too large");
             b.frames_per_chunk = c.frames_per_chunk;
@@ -729,7 +712,7 @@ int launch_molecule_rows(gorder_hip_handle *h, const FrameArgs &a, const gorder:
             HIP_TRY(h, hipGetLastError());
         }
         if (ua) {       // the united-atom tiles add into the same block (GORDER_FLAG_UA_SAMPLES)
-            const gorder::FrameChunks c = gorder::extras_chunks(nf, n_ua, h->wg_target, h->wg_capacity, false, true);
+            const gorder::FrameChunks c = gorder::extras_chunks(nf, n_ua, h->sw.wg_target, h->wg_capacity, false, true);
             const uint64_t grid = ua_grid(n_ua, c.n_chunks);
             if (grid > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "batch too large");
             b.frames_per_chunk = c.frames_per_chunk;
@@ -770,7 +753,7 @@ int launch_geometry_shapes(gorder_hip_handle *h, const FrameArgs &a) {
 // Tiled and Gather: one launch over the whole batch (its chunking stays in `a`)
 int launch_tiled(gorder_hip_handle *h, FrameArgs &a, const gorder::OrderRoute &route) {
     const uint32_t n_tiles = (uint32_t)h->plan.tiles.size();
-    const gorder::FrameChunks c = gorder::tiled_chunks(a.n_frames, (uint32_t)h->frames_per_stage, n_tiles, h->wg_target, h->wg_capacity);
+    const gorder::FrameChunks c = gorder::tiled_chunks(a.n_frames, (uint32_t)h->frames_per_stage, n_tiles, h->sw.wg_target, h->wg_capacity);
     a.frames_per_chunk = c.frames_per_chunk;
     const uint64_t grid = (uint64_t)n_tiles * c.n_chunks;
     if (grid > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "batch too large");
@@ -810,7 +793,7 @@ int launch_classes(gorder_hip_handle *h, const SubRange &s) {
     const Plan &p = h->plan;
     NeighbourClasses &nb = h->nb;
     const uint32_t nt = (uint32_t)p.tiles.size(), nf = s.nf();
-    const gorder::FrameChunks c = gorder::shells_chunks(nf, nt, h->wg_target, h->wg_capacity, kShellChunkMax);
+    const gorder::FrameChunks c = gorder::shells_chunks(nf, nt, h->sw.wg_target, h->wg_capacity, kShellChunkMax);
     FrameArgs b = s.frames(c);
     ClassArgs ca{};
     ca.centres = nb.d_centres; ca.neighbours = nb.d_neighbours; ca.n_neighbours = (uint32_t)nb.neighbours.size();
@@ -832,7 +815,7 @@ int launch_classes(gorder_hip_handle *h, const SubRange &s) {
 
 int launch_shells(gorder_hip_handle *h, const SubRange &s, const ExtraArgs &e) {
     const uint32_t nt = (uint32_t)h->plan.tiles.size();
-    const gorder::FrameChunks c = gorder::shells_chunks(s.nf(), nt, h->wg_target, h->wg_capacity, kShellChunkMax);
+    const gorder::FrameChunks c = gorder::shells_chunks(s.nf(), nt, h->sw.wg_target, h->wg_capacity, kShellChunkMax);
     FrameArgs b = s.frames(c);
     ShellArgs sa{};
     sa.n = h->n_shells; sa.rep = h->shells.rep; sa.n_rep = h->shells.n_rep;
@@ -849,8 +832,8 @@ int launch_shells(gorder_hip_handle *h, const SubRange &s, const ExtraArgs &e) {
 
 int launch_dist(gorder_hip_handle *h, const SubRange &s, const ExtraArgs &e) {
     const uint32_t nt = (uint32_t)h->plan.tiles.size();
-    const gorder::FrameChunks c = gorder::dist_chunks(s.nf(), nt, h->wg_target, h->wg_capacity, h->hist_direct ? 0u : (uint32_t)h->hist_table_words,
-                                                      h->hist_samples_per_word, kDistChunkMax);
+    const gorder::FrameChunks c = gorder::dist_chunks(s.nf(), nt, h->sw.wg_target, h->wg_capacity, h->hist_direct ? 0u : (uint32_t)h->hist_table_words,
+                                                      h->sw.dist_samples_per_word, kDistChunkMax);
     FrameArgs b = s.frames(c);
     DistArgs da{};
     da.n_edges = h->hist_edges; da.edges = h->d_hist_edges; da.rep = h->hist.rep; da.n_rep = h->hist.n_rep;
@@ -867,7 +850,7 @@ int launch_dist(gorder_hip_handle *h, const SubRange &s, const ExtraArgs &e) {
 // scatter-bound modes: the plain per-sample kernel (see "Extras" above)
 int launch_extras(gorder_hip_handle *h, const SubRange &s, const ExtraArgs &e) {
     const uint32_t nt = (uint32_t)h->plan.tiles.size();
-    const gorder::FrameChunks c = gorder::extras_chunks(s.nf(), nt, h->wg_target, h->wg_capacity, s.route.map_accumulate, false);
+    const gorder::FrameChunks c = gorder::extras_chunks(s.nf(), nt, h->sw.wg_target, h->wg_capacity, s.route.map_accumulate, false);
     FrameArgs b = s.frames(c);
     TIMING_MARK(h, s.route.label);
     with_bool(literal_cosine(h), [&](auto AC) { with_bool(s.route.maps_only, [&](auto MO) {
@@ -881,7 +864,7 @@ int launch_extras(gorder_hip_handle *h, const SubRange &s, const ExtraArgs &e) {
 int launch_tiled_out(gorder_hip_handle *h, const SubRange &s, const ExtraArgs &e) {
     const gorder::OrderRoute &route = s.route;
     const uint32_t nt = (uint32_t)h->plan.tiles.size();
-    const gorder::FrameChunks c = gorder::extras_chunks(s.nf(), nt, h->wg_target, h->wg_capacity, route.map_accumulate,
+    const gorder::FrameChunks c = gorder::extras_chunks(s.nf(), nt, h->sw.wg_target, h->wg_capacity, route.map_accumulate,
                                                         route.family == gorder::BondFamily::TiledTw);
     FrameArgs b = s.frames(c);
     const dim3 g(nt * c.n_chunks), blk(kBlock);
@@ -906,8 +889,7 @@ int launch_map_accumulate(gorder_hip_handle *h, const SubRange &s, uint32_t rec_
     const uint32_t n_acc = h->plan.n_acc;
     const uint32_t planes = h->tables.leaflets.method != GORDER_LEAFLETS_NONE ? 2u : 1u;
     const uint32_t ntm = h->map_nx * h->map_ny, n_words = planes * ntm;
-    const char *ev = getenv("GORDER_HIP_MAP_CHUNKS");
-    const gorder::FrameChunks m = gorder::map_chunks(s.nf(), n_acc, ev ? (uint32_t)std::max(1, atoi(ev)) : 0u);
+    const gorder::FrameChunks m = gorder::map_chunks(s.nf(), n_acc, h->sw.map_chunks);       // (GORDER_HIP_MAP_CHUNKS)
     TIMING_MARK(h, "k_map_accumulate");
     hipLaunchKernelGGL(k_map_accumulate, dim3(n_acc * m.n_chunks), dim3(1024), n_words * sizeof(unsigned long long), h->stream,
                        h->d_map_rec, runs, run_begin, n_acc, s.nf(), rec_stride, m.frames_per_chunk, per_item, n_words, ntm,
@@ -934,8 +916,8 @@ int launch_bond_pass(gorder_hip_handle *h, const SubRange &s, ExtraArgs &e) {
 // the order histogram over the united-atom tiles (GORDER_FLAG_UA_SAMPLES): k_bonds_dist's replicas, k_ua_extras' grid
 int launch_ua_dist(gorder_hip_handle *h, const SubRange &s, const ExtraArgs &e) {
     const uint32_t nt = (uint32_t)h->plan.ua_tiles.size();
-    const gorder::FrameChunks c = gorder::dist_chunks(s.nf(), nt, h->wg_target, h->wg_capacity, h->hist_direct ? 0u : (uint32_t)h->hist_table_words,
-                                                      h->hist_samples_per_word, kDistChunkMax);
+    const gorder::FrameChunks c = gorder::dist_chunks(s.nf(), nt, h->sw.wg_target, h->wg_capacity, h->hist_direct ? 0u : (uint32_t)h->hist_table_words,
+                                                      h->sw.dist_samples_per_word, kDistChunkMax);
     FrameArgs b = s.frames(c);
     DistArgs da{};
     da.n_edges = h->hist_edges; da.edges = h->d_hist_edges; da.rep = h->hist.rep; da.n_rep = h->hist.n_rep;
@@ -956,7 +938,7 @@ int launch_ua_pass(gorder_hip_handle *h, const SubRange &s, ExtraArgs &e) {
     const gorder::OrderRoute &route = s.route;
     if (route.ua_kernel == gorder::UaKernel::Dist) return launch_ua_dist(h, s, e);
     const uint32_t nt = (uint32_t)h->plan.ua_tiles.size();
-    const gorder::FrameChunks c = gorder::extras_chunks(s.nf(), nt, h->wg_target, h->wg_capacity, route.map_accumulate, false);
+    const gorder::FrameChunks c = gorder::extras_chunks(s.nf(), nt, h->sw.wg_target, h->wg_capacity, route.map_accumulate, false);
     FrameArgs b = s.frames(c);
     e.item_run = h->d_ua_item_run;
     const dim3 g((uint32_t)ua_grid(nt, c.n_chunks)), blk(kBlock);
@@ -989,13 +971,15 @@ int launch_scatter_passes(gorder_hip_handle *h, const FrameArgs &a, const gorder
     e.dyn = (h->dyn || h->manual_active) ? h->d_dyn_normals : nullptr;
     const bool staged = route.map_accumulate;
     const size_t rec_per_frame = std::max(p.ua_tiles.size() * 3u, route.extras ? p.tiles.size() : (size_t)0) * kBlock;   // staged words per frame
-    uint32_t sub = gorder::map_subrange(a.n_frames, e.maps != 0, staged, h->map_fold_limit, h->map_max_mol, rec_per_frame);
+    const long forced_limit = h->sw.map_fold_limit;    // GORDER_HIP_MAP_FOLD_LIMIT lowers the limit (tests)
+    const uint64_t fold_limit = forced_limit >= 2 && (unsigned long long)forced_limit <= kMapFoldLimit ? (uint64_t)forced_limit : kMapFoldLimit;
+    uint32_t sub = gorder::map_subrange(a.n_frames, e.maps != 0, staged, fold_limit, h->map_max_mol, rec_per_frame);
     // neighbour classes: the class rows hold the whole batch where it fits them (gorder_hip_neighbour_class_rows then returns
     // it), else one sub-range at a time
     bool class_rows_whole = false;
     if (route.family == gorder::BondFamily::Classes) {
-        class_rows_whole = gorder::class_rows_whole(a.n_frames, p.n_mol_total, h->nb.row_bytes);
-        sub = gorder::class_subrange(a.n_frames, p.n_mol_total, h->nb.forced_subrange, h->nb.row_bytes);
+        class_rows_whole = gorder::class_rows_whole(a.n_frames, p.n_mol_total, h->sw.nb_row_bytes);
+        sub = gorder::class_subrange(a.n_frames, p.n_mol_total, h->sw.nb_subrange, h->sw.nb_row_bytes);     // (GORDER_HIP_NB_SUBRANGE, GORDER_HIP_NB_ROW_BYTES)
         ST_TRY(ensure(h, h->nb.rows, (size_t)(class_rows_whole ? a.n_frames : sub) * p.n_mol_total));
     }
     if (staged) ST_TRY(ensure(h, h->d_map_rec, rec_per_frame * (((size_t)sub + 15) / 16 * 16)));
@@ -1004,7 +988,7 @@ int launch_scatter_passes(gorder_hip_handle *h, const FrameArgs &a, const gorder
         const SubRange s{a, route, lo, std::min(a.n_frames, lo + sub), class_rows_whole};
         if (e.maps) {
             const uint64_t cost = (uint64_t)s.nf() * h->map_max_mol;
-            if (h->map_pending + cost >= h->map_fold_limit) ST_TRY(fold_maps(h));
+            if (h->map_pending + cost >= fold_limit) ST_TRY(fold_maps(h));
             h->map_pending += cost;
         }
         e.rec_frame0 = lo; e.rec_stride = (s.nf() + 15u) / 16u * 16u;
@@ -1016,7 +1000,7 @@ int launch_scatter_passes(gorder_hip_handle *h, const FrameArgs &a, const gorder
 
 int launch_bonds_direct(gorder_hip_handle *h, const FrameArgs &a) {
     const uint32_t n_items = (uint32_t)h->plan.direct.size(), bpc = (n_items + kBlock - 1) / kBlock;
-    const gorder::FrameChunks c = gorder::direct_chunks(a.n_frames, bpc, h->wg_target);
+    const gorder::FrameChunks c = gorder::direct_chunks(a.n_frames, bpc, h->sw.wg_target);
     FrameArgs b = a;
     b.frames_per_chunk = c.frames_per_chunk;
     TIMING_MARK(h, "k_bonds_direct");
@@ -1380,7 +1364,7 @@ int gorder_hip_selftest_wave_ops(int device, uint32_t block, const double *f64, 
 int gorder_hip_plan_tables(const gorder_tables_t *tables, gorder_hip_plan_t *out, int *selfcheck) {
     if (!tables || !out) return GORDER_ERR_INVALID_ARGUMENT;
     Plan p;
-    ST_TRY(gorder::build_plan(*tables, env_flag("GORDER_HIP_FORCE_DIRECT"), p));
+    ST_TRY(gorder::build_plan(*tables, gorder::read_switches(::getenv).force_direct, p));     // (GORDER_HIP_FORCE_DIRECT, as at create)
     out->n_tiles = (uint32_t)p.tiles.size();
     out->block_threads = kBlock;
     out->max_window_atoms = p.max_window;
@@ -1423,7 +1407,7 @@ static int create_ordermaps(gorder_hip_handle *h, const gorder_tables_t *t) {
     // united atoms: stage + accumulate in LDS when one slot's packed map (x2 with leaflets) fits
     const size_t lds_bytes = npk / p.n_acc * sizeof(u64);
     h->map_lds_bytes = lds_bytes;
-    if (lds_bytes <= 150u * 1024u && !env_flag("GORDER_HIP_MAP_DIRECT")) {
+    if (lds_bytes <= 150u * 1024u && !h->sw.map_direct) {      // (GORDER_HIP_MAP_DIRECT)
         ST_TRY(upload(h, h->d_ua_runs, p.ua_runs));
         ST_TRY(upload(h, h->d_ua_run_begin, p.ua_run_begin));
         ST_TRY(upload(h, h->d_runs, p.runs));
@@ -1475,15 +1459,7 @@ static int create_accumulators(gorder_hip_handle *h) {
     h->acc_words = 4 * (size_t)p.n_acc + 1;
     ST_TRY(allocate(h, h->own_acc, h->acc_words, 0));
     h->d_acc = h->own_acc;
-    if (const char *e = getenv("GORDER_HIP_MAP_FOLD_LIMIT")) {
-        const long v = atol(e);
-        if (v >= 2 && (unsigned long long)v <= kMapFoldLimit) h->map_fold_limit = (uint64_t)v;
-    }
-    if (const char *e = getenv("GORDER_HIP_REPLICAS")) {
-        const int r = atoi(e);
-        if (r >= 1 && r <= 1024) h->n_rep = (uint32_t)r;
-    }
-    return p.n_acc ? allocate(h, h->d_rep, (size_t)h->n_rep * 4u * p.n_acc, 0) : GORDER_OK;
+    return p.n_acc ? allocate(h, h->d_rep, (size_t)h->sw.replicas * 4u * p.n_acc, 0) : GORDER_OK;
 }
 
 // k_local_build (dynamic normals, local leaflets) takes more dynamic LDS than a kernel gets unasked
@@ -1516,7 +1492,7 @@ static int create_dynamic_normals(gorder_hip_handle *h, const gorder_tables_t *t
     ST_TRY(upload(h, h->d_dyn_heads, nheads));
     h->host_dyn_heads = nheads;
     const size_t nm = dn.n_cloud, ncell = (size_t)kLocalMaxCells1D * kLocalMaxCells1D;
-    const size_t sl = h->dyn_slab = local_slab_frames(nm);
+    const size_t sl = h->dyn_slab = local_slab_frames(nm, h->sw.local_slab);
     ST_TRY(local_build_attributes(h));
     ST_TRY(allocate(h, h->d_dyn_cell_of, sl * nm));
     ST_TRY(allocate(h, h->d_dyn_rec, sl * nm * 4));
@@ -1571,7 +1547,7 @@ static int create_leaflet_tables(gorder_hip_handle *h, const gorder_tables_t *t,
         for (uint32_t a : mem)
             if (a >= t->n_atoms) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "membrane index out of range");
         ST_TRY(upload(h, h->d_membrane, mem));
-        h->membrane_is_frame = lf.n_membrane == t->n_atoms && !env_flag("GORDER_HIP_LEAFLETS_GENERIC");
+        h->membrane_is_frame = lf.n_membrane == t->n_atoms && !h->sw.leaflets_generic;       // (GORDER_HIP_LEAFLETS_GENERIC)
         for (uint32_t i = 0; i < lf.n_membrane && h->membrane_is_frame; i++) h->membrane_is_frame = mem[i] == i;
     }
     return GORDER_OK;
@@ -1612,8 +1588,7 @@ static int create_spherical(gorder_hip_handle *h, const gorder_tables_t *t, cons
     h->sph_spill = lf.n_membrane > resident ? lf.n_membrane - resident : 0u;
     if (h->sph_spill) {
         h->sph_slab = (uint32_t)std::min<size_t>(std::max<size_t>(((size_t)64 << 20) / (h->sph_spill * sizeof(float)), 1), 4096);
-        if (const char *ev = getenv("GORDER_HIP_SPHERICAL_SLAB"))      // (tests: frames per launch; only lowers the cap)
-            h->sph_slab = std::min(h->sph_slab, (uint32_t)std::max(1, atoi(ev)));
+        if (h->sw.spherical_slab) h->sph_slab = std::min(h->sph_slab, h->sw.spherical_slab);      // (GORDER_HIP_SPHERICAL_SLAB, tests: only lowers the cap)
         ST_TRY(allocate(h, h->d_sph_spill, (size_t)h->sph_slab * h->sph_spill));
     }
     return allocate(h, h->d_sph_stats, 12, 0);
@@ -1636,11 +1611,10 @@ static int create_clustering(gorder_hip_handle *h, const gorder_tables_t *t, con
     const uint32_t n = lf.n_membrane;
     h->cl_m_max = std::min<uint32_t>(n - 1u, (uint32_t)kClMaxSteps);
     // at most 512 MiB of scratch whatever the batch, at most 1024 frames a launch
-    h->cl_stored_w = env_flag("GORDER_HIP_CLUSTER_STORED_W");
     h->cl_tiles = (n + kClCutTile - 1u) / kClCutTile;
     h->cl_sort = (n + kClCutSort - 1u) / kClCutSort;
     const size_t per_frame = h->cl_cut ? clcut_frame_bytes(n, h->cl_m_max)
-                                       : cl_frame_bytes(n, h->cl_m_max) + (h->cl_stored_w ? (size_t)n * n * 4 : 0);
+                                       : cl_frame_bytes(n, h->cl_m_max) + (h->sw.cluster_stored_w ? (size_t)n * n * 4 : 0);     // (GORDER_HIP_CLUSTER_STORED_W)
     h->cl_slab = (uint32_t)std::min<size_t>(std::max<size_t>(((size_t)512 << 20) / per_frame, 1), 1024);
     ST_TRY(allocate(h, h->d_cl_scratch, (size_t)h->cl_slab * per_frame));
     ST_TRY(allocate(h, h->d_cl_carry, n));
@@ -1679,11 +1653,11 @@ static int create_speculation(gorder_hip_handle *h) {
 static int create_local_leaflets(gorder_hip_handle *h, const gorder_tables_t *t) {
     const Plan &p = h->plan;
     const size_t nm = t->leaflets.n_membrane, ncell = (size_t)kLocalMaxCells1D * kLocalMaxCells1D;
-    const size_t sl = h->local_slab = local_slab_frames(nm);
+    const size_t sl = h->local_slab = local_slab_frames(nm, h->sw.local_slab);
     ST_TRY(local_build_attributes(h));
     // rows of cells with a halo (periodic boxes, k_local_flags_rows): the first cells of a row are there twice,
     // records included — room for twice the membrane
-    h->local_halo = t->handle_pbc && !env_flag("GORDER_HIP_LOCAL_ATOMS_ONLY");
+    h->local_halo = t->handle_pbc && !h->sw.local_atoms_only;
     h->local_rec_stride = (h->local_halo ? 2u : 1u) * nm;
     ST_TRY(allocate(h, h->d_lcell_of, sl * nm));
     ST_TRY(allocate(h, h->d_ltrig, sl * h->local_rec_stride * (sizeof(LocalRec) / sizeof(float))));
@@ -1714,6 +1688,7 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
 
     gorder_hip_handle *h = new (std::nothrow) gorder_hip_handle();
     if (!h) return GORDER_ERR_DEVICE;
+    h->sw = gorder::read_switches(::getenv);      // the one look at the environment: whatever follows reads h->sw
     *out = h;   // returned even on failure so that the caller can read the message; destroy() is safe
     h->tables = *t;
     h->tables.molecule_types = nullptr;
@@ -1727,7 +1702,8 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
     // united atoms: a wave = 4 slots x 16 molecules (plan.h) — except for per-frame rows and nothing else, where a wave of
     // ONE slot sends a fourth of the atomics (0.433 against 0.449 ms per 3 000 frames of the 256-lipid membrane)
     const bool ua_rows_only = t->timewise && !t->ordermap.enabled && t->geometry.kind == GORDER_GEOM_NONE && !t->dynamic_normal.enabled;
-    const int st = gorder::build_plan(*t, env_flag("GORDER_HIP_FORCE_DIRECT"), h->plan, !env_flag("GORDER_HIP_UA_SLOT_WAVES") && !ua_rows_only);
+    // (GORDER_HIP_FORCE_DIRECT, GORDER_HIP_UA_SLOT_WAVES)
+    const int st = gorder::build_plan(*t, h->sw.force_direct, h->plan, !h->sw.ua_slot_waves && !ua_rows_only);
     if (st != GORDER_OK) return fail(h, st, "invalid bond tables");
     const Plan &p = h->plan;
     for (uint32_t m = 0; m < t->n_molecule_types; m++)
@@ -1765,26 +1741,6 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
             if (n[d] == 1.0f && n[(d + 1) % 3] == 0.0f && n[(d + 2) % 3] == 0.0f) h->axis = d;
         h->extra.axis = h->axis;
     }
-    if (const char *e = getenv("GORDER_HIP_KERNEL")) h->use_gather = strcmp(e, "gather") == 0;
-    h->shell_force_direct = env_flag("GORDER_HIP_RADIAL_DIRECT");
-    h->hist_force_direct = env_flag("GORDER_HIP_DIST_DIRECT");
-    h->nb.force_direct = env_flag("GORDER_HIP_NB_DIRECT");
-    if (const char *ev = getenv("GORDER_HIP_NB_SUBRANGE")) h->nb.forced_subrange = (uint32_t)std::max(0, atoi(ev));
-    if (const char *ev = getenv("GORDER_HIP_NB_ROW_BYTES")) {
-        const long long v = atoll(ev);
-        if (v > 0) h->nb.row_bytes = (uint64_t)v;
-    }
-    if (const char *ev = getenv("GORDER_HIP_CORR_SUBRANGE")) h->corr.forced_subrange = (uint32_t)std::max(0, atoi(ev));
-    if (const char *ev = getenv("GORDER_HIP_CORR_GRID")) h->corr.chunk_major = strcmp(ev, "chunks") == 0;
-    if (const char *ev = getenv("GORDER_HIP_DIST_SAMPLES_PER_WORD")) h->hist_samples_per_word = (uint32_t)std::min(std::max(0, atoi(ev)), 1 << 16);
-    if (const char *e = getenv("GORDER_HIP_MOL_ROWS_STAGING")) {      // bytes of the per-molecule rows' device staging (tests set it small)
-        const long long v = atoll(e);
-        if (v > 0) h->mol_stage_bytes = (size_t)v;
-    }
-    if (const char *e = getenv("GORDER_HIP_WG_TARGET")) {
-        const int w = atoi(e);
-        if (w > 0) h->wg_target = (uint32_t)w;
-    }
     h->lw = ((3u * p.max_window + 3u + 3u) / 4u) * 4u;
     h->lds_bytes = (size_t)h->frames_per_stage * h->lw * sizeof(float);
     if (h->lds_bytes < (size_t)kBlock * 24) h->lds_bytes = (size_t)kBlock * 24;
@@ -1805,7 +1761,7 @@ int gorder_hip_create(const gorder_tables_t *t, gorder_hip_handle **out) {
         ST_TRY(create_leaflet_tables(h, t, heads));
         if (lf.method == GORDER_LEAFLETS_SPHERICAL) ST_TRY(create_spherical(h, t, heads));
         if (lf.method == GORDER_LEAFLETS_CLUSTERING) ST_TRY(create_clustering(h, t, heads));
-        if (lf.method == GORDER_LEAFLETS_GLOBAL && p.spec_ok && !env_flag("GORDER_HIP_NO_SPECULATE")) ST_TRY(create_speculation(h));
+        if (lf.method == GORDER_LEAFLETS_GLOBAL && p.spec_ok && !h->sw.no_speculate) ST_TRY(create_speculation(h));
         if (lf.method == GORDER_LEAFLETS_LOCAL) ST_TRY(create_local_leaflets(h, t));
         ST_TRY(allocate(h, h->d_adist, p.n_mol_total ? p.n_mol_total : 1));
     }
@@ -1994,7 +1950,7 @@ static int run_clustering(gorder_hip_handle *h, const float *d_xyz, const float 
     ca.meta = (float *)carve(cl_round(kClMeta * 4));
     ca.fail = (uint32_t *)carve(16);
     ca.lab = (uint8_t *)carve(cl_round(n));
-    ca.W = h->cl_stored_w ? (float *)carve((size_t)n * n * 4) : nullptr;
+    ca.W = h->sw.cluster_stored_w ? (float *)carve((size_t)n * n * 4) : nullptr;
     // (the arrays are indexed [slot][..] with their exact sizes: the rounding only pads the ends)
     ClOrientArgs oa{};
     oa.n = n; oa.lab = ca.lab; oa.emb = ca.emb; oa.meta = ca.meta; oa.fail = ca.fail; oa.carry = h->d_cl_carry;
@@ -2083,7 +2039,7 @@ static int launch_spherical_leaflets(gorder_hip_handle *h, const LeafletArgs &la
 struct LocalDecisions { bool decide, sums, report; };
 static LocalDecisions local_decisions(gorder_hip_handle *h, const LocalArgs &lo) {
     LocalDecisions d{};
-    d.decide = lo.halo && lo.prune && lo.n_mol_total && !env_flag("GORDER_HIP_LOCAL_NO_DECIDE");
+    d.decide = lo.halo && lo.prune && lo.n_mol_total && !h->sw.local_no_decide;      // (GORDER_HIP_LOCAL_NO_DECIDE)
     if (d.decide) {
         if (h->lsummary_pending) {
             if (hipEventQuery(h->lsummary_written) == hipSuccess) {
@@ -2096,8 +2052,7 @@ static LocalDecisions local_decisions(gorder_hip_handle *h, const LocalArgs &lo)
         if (h->decide_pause) { h->decide_pause--; h->decide_paused_submits++; d.decide = false; }
         else h->decide_submits++;
     }
-    d.sums = d.decide && lo.n_membrane <= kLocalBuildMax && !env_flag("GORDER_HIP_LOCAL_THREE_KERNELS") &&
-             !env_flag("GORDER_HIP_LOCAL_NO_SUMS");
+    d.sums = d.decide && lo.n_membrane <= kLocalBuildMax && !h->sw.local_three_kernels && !h->sw.local_no_sums;      // (GORDER_HIP_LOCAL_NO_SUMS)
     d.report = d.decide && !h->lsummary_pending;      // (one report in flight)
     return d;
 }
@@ -2112,7 +2067,7 @@ static int launch_local_slabs(gorder_hip_handle *h, LocalArgs lo, uint32_t n_ass
         lo.row0 = row0 + (uint32_t)done;
         lo.write_dist_frame = (done + ns == n_assign) ? (int)ns - 1 : -1;
         lo.summary_host = report && done + ns == n_assign ? h->h_lsummary : nullptr;
-        if (lo.n_membrane > kLocalBuildMax || env_flag("GORDER_HIP_LOCAL_THREE_KERNELS"))
+        if (lo.n_membrane > kLocalBuildMax || h->sw.local_three_kernels)
             HIP_TRY(h, hipMemsetAsync(h->d_lcell_fill, 0, ns * ncell * sizeof(uint32_t), h->stream));
         if (lo.sums) {
             HIP_TRY(h, hipMemsetAsync(h->d_lneed, 0, (ns + 1) * sizeof(uint32_t), h->stream));
@@ -2158,7 +2113,7 @@ static int launch_local_leaflets(gorder_hip_handle *h, const LeafletArgs &la) {
     lo.cell_fill = h->d_lcell_fill; lo.err = la.err;
     lo.grid = h->d_lgrid;
     lo.halo = h->local_halo ? 1 : 0;
-    lo.prune = env_flag("GORDER_HIP_LOCAL_NO_PRUNE") ? 0 : (env_flag("GORDER_HIP_LOCAL_DECIDE_NOTHING") ? 2 : 1);
+    lo.prune = h->sw.local_no_prune ? 0 : (h->sw.local_decide_nothing ? 2 : 1);
     lo.rec_stride = (uint32_t)h->local_rec_stride;
     lo.rowpre = h->d_lrowpre;
     lo.edge = h->d_ledge;
@@ -2211,7 +2166,7 @@ static int launch_bond_corr(gorder_hip_handle *h, const FrameArgs &a) {
     const uint32_t n_tiles = (uint32_t)p.tiles.size(), n_lags = (uint32_t)bc.lags.size(), max_lag = bc.lags.back();
     if (!bc.ring) {      // the first batch: the sub-range is fixed here (the setter has checked that one frame fits)
         const uint64_t fit = gorder::corr_subrange_fit(gorder::corr_plane_bytes(n_tiles, kBlock), max_lag, gorder::kCorrRingBudget);
-        bc.subrange = gorder::corr_subrange(fit, a.n_frames, bc.forced_subrange);
+        bc.subrange = gorder::corr_subrange(fit, a.n_frames, h->sw.corr_subrange);      // (GORDER_HIP_CORR_SUBRANGE)
         bc.ring_planes = gorder::corr_ring_planes(max_lag, bc.subrange);
         bc.plane_items = n_tiles * kBlock;
         ST_TRY(allocate(h, bc.ring, (size_t)bc.ring_planes * bc.plane_items));
@@ -2225,11 +2180,11 @@ static int launch_bond_corr(gorder_hip_handle *h, const FrameArgs &a) {
     c.xyz = a.xyz; c.box9 = a.box9; c.n_atoms = a.n_atoms; c.pbc = a.pbc;
     for (uint32_t lo = 0; lo < a.n_frames; lo += bc.subrange) {
         const uint32_t hi = (uint32_t)std::min<uint64_t>(a.n_frames, (uint64_t)lo + bc.subrange), nf = hi - lo;
-        const gorder::CorrChunks ch = gorder::corr_chunks(nf, n_tiles, h->wg_target, h->wg_capacity);
+        const gorder::CorrChunks ch = gorder::corr_chunks(nf, n_tiles, h->sw.wg_target, h->wg_capacity);
         const uint32_t n_groups = (n_lags + gorder::kCorrLagBlock - 1u) / gorder::kCorrLagBlock;
-        const uint64_t grid = (uint64_t)n_tiles * ch.n_chunks * (bc.chunk_major ? 1u : n_groups);
+        const uint64_t grid = (uint64_t)n_tiles * ch.n_chunks * (h->sw.corr_grid_chunks ? 1u : n_groups);
         if ((uint64_t)n_tiles * nf > 0x7fffffffull || grid > 0x7fffffffull) return fail(h, GORDER_ERR_INVALID_ARGUMENT, "batch too large");
-        c.frame0 = lo; c.n_frames = hi; c.frames_per_chunk = ch.frames_per_chunk; c.n_chunks = bc.chunk_major ? 0u : ch.n_chunks;
+        c.frame0 = lo; c.n_frames = hi; c.frames_per_chunk = ch.frames_per_chunk; c.n_chunks = h->sw.corr_grid_chunks ? 0u : ch.n_chunks;
         TIMING_MARK(h, "k_bond_units");
         hipLaunchKernelGGL(k_bond_units, dim3(n_tiles * nf), dim3(kBlock), 0, h->stream, c, h->d_tiles, h->d_items, n_tiles);
         TIMING_MARK(h, "k_bond_corr");
@@ -2357,7 +2312,7 @@ static void choose_batch_route(gorder_hip_handle *h, Batch &b) {
     ri.maps = h->extra.maps != 0; ri.map_staged = h->map_staged; ri.tw = h->extra.tw != 0; ri.geom = h->extra.geom_kind != 0;
     ri.manual_frames = h->manual_frames != 0; ri.normal_table = h->d_ntable != nullptr;
     ri.dyn_or_manual = h->dyn || ri.manual_frames || ri.normal_table;       // (manual_active is set in 6.)
-    ri.use_gather = h->use_gather; ri.item_run = h->d_item_run != nullptr; ri.frames_per_stage = h->frames_per_stage; ri.max_window = p.max_window;
+    ri.use_gather = h->sw.kernel_gather; ri.item_run = h->d_item_run != nullptr; ri.frames_per_stage = h->frames_per_stage; ri.max_window = p.max_window;
     ri.bond_tiles = !p.tiles.empty(); ri.ua_tiles = !p.ua_tiles.empty(); ri.direct_items = !p.direct.empty(); ri.ua_fast_flag = (h->tables.flags & GORDER_FLAG_UA_FAST_NORMALISE) != 0;
     ri.global_leaflets = h->tables.leaflets.method == GORDER_LEAFLETS_GLOBAL; ri.spec_enabled = h->spec_enabled && !h->corr.on(); ri.have_assignment = h->have_assignment;
     ri.shells = h->n_shells != 0;
@@ -2365,7 +2320,7 @@ static void choose_batch_route(gorder_hip_handle *h, Batch &b) {
     ri.classes = h->nb.on();
     ri.mol_rows = h->mol.n_groups != 0 && !h->mol_failed;
     ri.ua_samples_flag = (h->tables.flags & GORDER_FLAG_UA_SAMPLES) != 0;
-    ri.npf5 = env_flag("GORDER_HIP_NPF5"); ri.tw_gather = env_flag("GORDER_HIP_TW_GATHER"); ri.maps_gather = env_flag("GORDER_HIP_MAPS_GATHER");
+    ri.npf5 = h->sw.npf5; ri.tw_gather = h->sw.tw_gather; ri.maps_gather = h->sw.maps_gather;
     ri.every_frame_assigns = b.aframes.size() == b.n_frames;
     b.route = gorder::choose_order_route(ri);
     if (!b.route.speculative) return;
@@ -2426,7 +2381,7 @@ static int set_batch_normals(gorder_hip_handle *h, Batch &b) {
     a.pbc = b.pbc ? 1 : 0;
     a.nx = h->tables.normal[0]; a.ny = h->tables.normal[1]; a.nz = h->tables.normal[2]; a.n2 = h->n2; a.n2sq = h->n2sq;
     a.leaflets = b.leaflets ? 1 : 0; a.aflags = h->d_aflags; a.arow = h->d_arow; a.n_mol_total = p.n_mol_total;
-    a.acc = h->d_acc; a.rep = h->d_rep; a.n_rep = h->n_rep; a.n_acc = p.n_acc; a.err = h->d_err;
+    a.acc = h->d_acc; a.rep = h->d_rep; a.n_rep = h->sw.replicas; a.n_acc = p.n_acc; a.err = h->d_err;
     h->manual_active = false;
     if (h->manual_frames) {
         const size_t n4 = (size_t)b.n_frames * p.n_mol_total;
@@ -3114,7 +3069,7 @@ int gorder_hip_set_radial_shells(gorder_hip_handle *h, const float *radii, uint3
         for (const Tile &tile : p.tiles) max_slots = std::max(max_slots, tile.n_slots);
         const uint32_t planes = t.leaflets.method != GORDER_LEAFLETS_NONE ? 2u : 1u;
         h->shell_lds_bytes = (size_t)planes * n_radii * max_slots * sizeof(unsigned long long);
-        h->shell_direct = h->shell_force_direct || h->shell_lds_bytes > 64u * 1024u;
+        h->shell_direct = h->sw.radial_direct || h->shell_lds_bytes > 64u * 1024u;
         for (uint32_t k = 0; k < n_radii; k++) h->shell_thr[k] = thr[k];
         h->n_shells = n_radii;
         return GORDER_OK;
@@ -3191,7 +3146,7 @@ int gorder_hip_set_order_histogram(gorder_hip_handle *h, const int32_t *edges, u
     for (const Tile &tile : p.ua_tiles) max_slots = std::max(max_slots, tile.n_slots);     // (only with GORDER_FLAG_UA_SAMPLES: refused above otherwise)
     const uint32_t planes = h->tables.leaflets.method != GORDER_LEAFLETS_NONE ? 2u : 1u;
     h->hist_table_words = (size_t)planes * n_bins * max_slots;
-    h->hist_direct = h->hist_force_direct || kDistEdgeBytes + h->hist_table_words * sizeof(uint32_t) > 64u * 1024u;
+    h->hist_direct = h->sw.dist_direct || kDistEdgeBytes + h->hist_table_words * sizeof(uint32_t) > 64u * 1024u;
     h->hist_edges = n_edges;
     return GORDER_OK;
 }
@@ -3328,7 +3283,7 @@ int gorder_hip_set_neighbour_classes(gorder_hip_handle *h, const uint32_t *centr
     for (const Tile &tile : p.tiles) max_slots = std::max(max_slots, tile.n_slots);
     const uint32_t planes = h->tables.leaflets.method != GORDER_LEAFLETS_NONE ? 2u : 1u;
     nb.lds_bytes = (size_t)gorder::class_table_bytes(planes, n_classes, max_slots);
-    nb.direct = nb.force_direct || !gorder::class_table_fits(planes, n_classes, max_slots);
+    nb.direct = h->sw.nb_direct || !gorder::class_table_fits(planes, n_classes, max_slots);
     nb.radius = radius; nb.thr = local_radius_threshold(radius);
     nb.n_classes = n_classes;
     return GORDER_OK;
@@ -3575,7 +3530,7 @@ int gorder_hip_reset(gorder_hip_handle *h) {
     HIP_TRY(h, hipSetDevice(h->device));
     const Plan &p = h->plan;
     HIP_TRY(h, hipMemsetAsync(h->d_acc, 0, h->acc_words * sizeof(unsigned long long), h->stream));
-    if (h->d_rep) HIP_TRY(h, hipMemsetAsync(h->d_rep, 0, (size_t)h->n_rep * 4u * p.n_acc * sizeof(unsigned long long), h->stream));
+    if (h->d_rep) HIP_TRY(h, hipMemsetAsync(h->d_rep, 0, (size_t)h->sw.replicas * 4u * p.n_acc * sizeof(unsigned long long), h->stream));
     h->rep_dirty = false;
     if (h->n_shells) HIP_TRY(h, h->shells.zero_async(h->stream));       // (the radii stay)
     if (h->hist_edges) HIP_TRY(h, h->hist.zero_async(h->stream));      // (the edges stay)

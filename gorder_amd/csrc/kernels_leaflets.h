@@ -631,13 +631,12 @@ constexpr uint32_t kLocalMaxCells1D = 128;
 // frames/s on the 3 072-lipid membrane, 1 024 gave 1.97 M, 2 048 2.07 M; 256 had measured 4 % slower than 512, 128 20 %.
 // The scratch is sized for every frame of a group being left open; where k_local_decide decides the frames it stays untouched.)
 constexpr uint32_t kLocalSlabMax = 2048;
-inline uint32_t local_slab_frames(size_t n_membrane) {
+inline uint32_t local_slab_frames(size_t n_membrane, uint32_t forced_cap) {      // forced_cap: GORDER_HIP_LOCAL_SLAB, 0 = not set
     // (the heads' to-do list, 8 bytes per head and frame, is on top: heads are a fraction of the membrane atoms)
     // (records twice — the halo copies —, the cell of every atom, two tables of cell counts, the rows' two tables of sums)
     const size_t per_frame = n_membrane * (2u * 12u + 4u) + (size_t)(2 * 4u + 16u + 16u) * kLocalMaxCells1D * (kLocalMaxCells1D + 1u) + 32u;
     const size_t n = ((size_t)4096 << 20) / per_frame;
-    uint32_t cap = kLocalSlabMax;
-    if (const char *ev = getenv("GORDER_HIP_LOCAL_SLAB")) cap = (uint32_t)std::max(4, atoi(ev));      // (A/B: frames per launch group)
+    const uint32_t cap = forced_cap ? forced_cap : kLocalSlabMax;      // (A/B: frames per launch group)
     return (uint32_t)(n < 4 ? 4 : (n > cap ? cap : n));
 }
 

@@ -333,10 +333,10 @@ extern "C" int gorder_hip_run_trajectory(gorder_hip_handle *h, const gorder_traj
     // runs while the blocks of this one are still being copied
     gorder_xtc_pool *pool = nullptr;
     if (dev && gorder_xtc_pool_create(n_threads, &pool) != GORDER_XTC_OK) pool = nullptr;
-    const char *forced_prefix = getenv("GORDER_HIP_PREFIX_Q16");          // test switch: a fixed part, whatever it leads to
+    const uint32_t forced_prefix = h->sw.prefix_q16;          // GORDER_HIP_PREFIX_Q16, a test switch: a fixed part, whatever it leads to
     // (XTC frames only: of a TRR frame exactly the analysed part travels, there is nothing to learn and no SHORT frame)
-    const bool adapt_prefix = dev && has_xtc && !forced_prefix && !env_flag("GORDER_HIP_NO_PREFIX") && n_stop < n_file_atoms;
-    if (dev && forced_prefix) pipe.prefix_q16.store((uint32_t)std::max(1l, std::min(65536l, atol(forced_prefix))));
+    const bool adapt_prefix = dev && has_xtc && !forced_prefix && !h->sw.no_prefix && n_stop < n_file_atoms;      // (GORDER_HIP_NO_PREFIX)
+    if (dev && forced_prefix) pipe.prefix_q16.store(forced_prefix);
     // only a run that copies parts of blocks has anything to look at between the two stages; any other queues stage B
     // right behind stage A and never waits for the device
     const bool verify = dev && has_xtc && (adapt_prefix || forced_prefix);

@@ -276,6 +276,44 @@ typedef struct {
 
 typedef struct gorder_hip_handle gorder_hip_handle;
 
+/* Development switches: environment variables for A/B measurements and for tests that must reach a fallback path.  None
+ * changes results.  They are read once, at gorder_hip_create (and by gorder_hip_plan_tables at its call, which has no
+ * handle): the handle keeps what it found, and a variable changed afterwards — before a submit, before gorder_hip_reset,
+ * from another thread — no longer affects that handle.  A flag is on when set, non-empty and not "0".  The list
+ * (gorder_amd/csrc/switches.h holds it, with the parsing):
+ *   GORDER_HIP_KERNEL                  =gather: the L1-gather order kernel instead of LDS staging (plain bond tiles only)
+ *   GORDER_HIP_WG_TARGET               =N: the workgroup count the frame chunks of a batch aim at
+ *   GORDER_HIP_NPF5                    five prefetch registers in the tiled kernels where four would do
+ *   GORDER_HIP_TW_GATHER               per-frame rows through k_bonds_extras instead of k_bonds_tiled_tw
+ *   GORDER_HIP_MAPS_GATHER             staged ordermaps through k_bonds_extras instead of k_bonds_tiled_maps
+ *   GORDER_HIP_FORCE_DIRECT            every bond a direct item (k_bonds_direct), no tiles
+ *   GORDER_HIP_UA_SLOT_WAVES           united-atom waves of one slot instead of 4 slots x 16 molecules
+ *   GORDER_HIP_REPLICAS                =N in [1, 1024]: copies of the accumulators the kernels add into (32)
+ *   GORDER_HIP_MAP_DIRECT              ordermaps by one atomic per sample even where a slot's map fits LDS
+ *   GORDER_HIP_MAP_CHUNKS              =N: chunks of frames of k_map_accumulate
+ *   GORDER_HIP_MAP_FOLD_LIMIT          =N in [2, 2^21]: samples a packed ordermap word may hold before it is folded (tests)
+ *   GORDER_HIP_NO_SPECULATE            global leaflets by k_leaflets_global first, never one read for leaflets and order parameters
+ *   GORDER_HIP_LEAFLETS_GENERIC        the membrane's index list even where the membrane is every atom of the frame in order
+ *   GORDER_HIP_SPHERICAL_SLAB          =N: at most N assignment frames per launch of k_leaflets_spherical (tests; only lowers the cap)
+ *   GORDER_HIP_CLUSTER_STORED_W        spectral clustering reads W stored once a frame instead of recomputing it
+ *   GORDER_HIP_LOCAL_SLAB              =N >= 4: at most N assignment frames per launch group of local leaflets and dynamic normals
+ *   GORDER_HIP_LOCAL_ATOMS_ONLY        local leaflets without rows of cells: every candidate atom by atom (k_local_flags)
+ *   GORDER_HIP_LOCAL_THREE_KERNELS     the cell list by k_local_bin, k_local_scan and k_local_scatter instead of k_local_build
+ *   GORDER_HIP_LOCAL_NO_DECIDE         local leaflets without k_local_decide: the rows kernel for every frame
+ *   GORDER_HIP_LOCAL_NO_SUMS           local leaflets without k_local_sums: the cell list for every frame
+ *   GORDER_HIP_LOCAL_NO_PRUNE          local leaflets: the exact path for every head, no bound
+ *   GORDER_HIP_LOCAL_DECIDE_NOTHING    local leaflets: the bound leaves every head open (a measuring aid)
+ *   GORDER_HIP_RADIAL_DIRECT           radial shells by per-sample global atomics even where the table fits LDS
+ *   GORDER_HIP_DIST_DIRECT             order distributions by per-sample global atomics even where the table fits LDS
+ *   GORDER_HIP_DIST_SAMPLES_PER_WORD   =N in [0, 65536]: samples per table word the chunks of k_bonds_dist are cut for (8)
+ *   GORDER_HIP_NB_DIRECT               neighbour classes by per-sample global atomics even where the table fits LDS
+ *   GORDER_HIP_NB_SUBRANGE             =N: neighbour classes in sub-ranges of at most N frames
+ *   GORDER_HIP_NB_ROW_BYTES            =N: the most bytes the class rows of one sub-range take (1 GiB; tests set it small)
+ *   GORDER_HIP_CORR_SUBRANGE           =N: bond reorientation in sub-ranges of at most N frames
+ *   GORDER_HIP_CORR_GRID               =chunks: a workgroup of k_bond_corr walks every group of lags of its chunk
+ *   GORDER_HIP_MOL_ROWS_STAGING        =N: bytes of the per-molecule rows' device staging (1 GiB; tests set it small)
+ *   GORDER_HIP_PREFIX_Q16              =N in [1, 65536]: device decode copies N/65536 of every XTC block, whatever it leads to (tests)
+ *   GORDER_HIP_NO_PREFIX               device decode copies whole XTC blocks and learns no part */
 int gorder_hip_create(const gorder_tables_t *tables, gorder_hip_handle **out);
 void gorder_hip_destroy(gorder_hip_handle *h);
 
